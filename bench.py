@@ -128,7 +128,51 @@ def parse_args(argv=None):
                     help="--gpus N launched from this process: seconds a rank may run before all of them are stopped")
     ap.add_argument("--force-process-group", action="store_true",
                     help="initialise torch.distributed (RCCL on a GPU) even with one rank, and run the reductions through it")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's shard) as DIR/<name>.npy in float64: "
+                         "the decoded integers and the units' end offsets, each a fixed seeded sample when larger than fits "
+                         "in 64 MB in all (DIR/decoded_index.npy: which integers)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+# --dump-outputs: at most 64 MB of .npy in all (float64, 8 B a value; the decoded sample is written with its indices)
+DUMP_DECODED_MAX = 3 << 20
+DUMP_ENDS_MAX = 1 << 20
+DUMP_SEED = 20240917
+
+
+def dump_sample_index(n, cap):
+    """Sorted positions of a fixed, seeded sample of [0, n): all of them when n <= cap. A function of n and cap alone, so two
+    runs (and two builds) with the same arguments sample the same positions."""
+    import numpy as np
+
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=cap, dtype=np.int64))
+
+
+def dump_outputs(out_dir, out_dev, end_dev):
+    """What a caller of the timed path receives from a step: the decoded integers (u32) and every unit's end offset in the
+    stream (u64), as float64 (exact below 2^53)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, t, cap in (("decoded", out_dev, DUMP_DECODED_MAX), ("end_offsets", end_dev, DUMP_ENDS_MAX)):
+        idx = dump_sample_index(t.numel(), cap)
+        vals = t if idx.size == t.numel() else t[torch.from_numpy(idx).to(t.device)]
+        vals = vals.cpu().numpy()
+        vals = vals.view(np.uint32) if vals.dtype == np.int32 else vals.view(np.uint64)
+        arrays[name] = vals.astype(np.float64)
+        if name == "decoded":
+            arrays["decoded_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: int(a.size) for name, a in arrays.items()}
 
 
 def log(rank, *a):
@@ -635,6 +679,11 @@ def main():
         total_ints = int(tot.item())
     else:
         total_ints = n_ints
+
+    # ---- what the last timed step computed (before the box probe below overwrites the output buffer) ----------------
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, out_dev, end_dev)
+        log(rank, f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
 
     # ---- correctness: bit-exact against the encoder's input -------------------------
     ends = end_dev.cpu().numpy().view(np.uint64)

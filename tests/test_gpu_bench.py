@@ -106,6 +106,31 @@ def test_config4_shard_of_eight_on_one_gpu(k):
     assert "universe 50000000" in d["config"]["workload"]
 
 
+def test_bench_dump_outputs_are_the_decode_and_repeat(tmp_path):
+    """--dump-outputs: the last timed step's integers are the generator's gaps (one piece, one copy, small enough to be
+    written whole), and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    from dint_amd import host
+
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--postings", "2e6",
+           "--dict-sample", "1e6", "--cpu-seconds", "0", "--placement-trials", "1"]
+    runs = []
+    for k in range(2):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / str(k))], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 4 and d["roofline"]["kernel_launches_timed"] == 4 and d["bit_exact"] is True
+        runs.append({f: np.load(tmp_path / str(k) / f) for f in ("decoded.npy", "decoded_index.npy", "end_offsets.npy")})
+    for f in runs[0]:
+        assert runs[0][f].dtype == np.float64 and np.array_equal(runs[0][f], runs[1][f]), f
+    p = host.synth_params(universe=25_000_000, seed=12345)
+    lens = host.synth_lengths(p, 2_000_000)
+    gaps = host.synth_gaps(p, lens, first_list_id=0)
+    assert np.array_equal(runs[0]["decoded_index.npy"], np.arange(gaps.size))
+    assert np.array_equal(runs[0]["decoded.npy"], gaps.astype(np.float64))
+    assert runs[0]["end_offsets.npy"].size == d["config"]["units_per_gpu"] and np.all(np.diff(runs[0]["end_offsets.npy"]) >= 0)
+
+
 def test_rccl_process_group_initialises_on_hardware():
     """The N > 1 path's collectives (RCCL all-reduce of elapsed / integers / ok, the dictionary broadcast) with a world of
     one: init_process_group("nccl") and every reduction run on the GPU at least once."""

@@ -178,6 +178,37 @@ def test_one_rank_and_two_ranks_decode_the_same_workload_per_gpu():
     assert "decoded x5" in off["config"]["workload"] and "decoded x" not in two["config"]["workload"]
 
 
+def test_bench_steps_are_the_timed_steps_and_dump_outputs(tmp_path):
+    """--steps K: K timed launches and ms_per_step in the line; --steps 0 is refused. --dump-outputs DIR: the last timed
+    step's decoded integers (with the positions sampled) and end offsets as float64 .npy files, 64 MB at most in all."""
+    import json
+
+    r = _stub_bench(["--gpus", "1", "--steps", "5", "--dump-outputs", str(tmp_path / "out")], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert line["steps"] == 5 and line["roofline"]["kernel_launches_timed"] == 5 and line["ms_per_step"] > 0
+    files = {f: np.load(tmp_path / "out" / f) for f in sorted(os.listdir(tmp_path / "out"))}
+    assert sorted(files) == ["decoded.npy", "decoded_index.npy", "end_offsets.npy"]
+    assert all(a.dtype in (np.float32, np.float64) and a.ndim == 1 for a in files.values())
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) <= 64 << 20
+    idx = files["decoded_index.npy"]
+    n = line["config"]["ints_per_gpu_per_step"]
+    assert idx.size == files["decoded.npy"].size == n and np.array_equal(idx, np.arange(n))  # small enough: all of it
+    assert files["end_offsets.npy"].size == line["config"]["units_per_gpu"]
+    assert _stub_bench(["--gpus", "1", "--steps", "0"], {}).returncode != 0
+
+
+def test_bench_dump_sample_is_fixed_and_bounded():
+    import bench
+
+    big = 5_000_000_000
+    a, b = bench.dump_sample_index(big, bench.DUMP_DECODED_MAX), bench.dump_sample_index(big, bench.DUMP_DECODED_MAX)
+    assert np.array_equal(a, b) and a.size <= bench.DUMP_DECODED_MAX and a.size > 0.99 * bench.DUMP_DECODED_MAX
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < big
+    assert 8 * (2 * bench.DUMP_DECODED_MAX + bench.DUMP_ENDS_MAX) <= 64 << 20
+    assert np.array_equal(bench.dump_sample_index(10, 100), np.arange(10))
+
+
 def test_bench_help_renders():
     """argparse formats every help string with %: an unescaped per cent sign in one of them breaks --help."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
