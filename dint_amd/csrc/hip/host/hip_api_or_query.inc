@@ -1,0 +1,176 @@
+// Part of dint_hip.hip (one translation unit; included from there, in order): extern "C": disjunctive queries (queries.hpp:86-130).
+// ---- disjunctive queries ------------------------------------------------------------------------
+// or_query visits every docID some list of the query holds, once, and (with_freqs) reads the freq of every posting: every
+// block of every distinct term is decoded, so there is nothing to skip and nothing to claim. A call is cut into passes of
+// whole queries of at most DINT_OPT_QUERY_OR_PASS_PAGES pages; per pass one copy in, the pages' decode (decode_pages, as
+// the AND path decodes its freqs pages) and ONE probe launch (or_count_kernel, dint_or_query_kernels.hpp) that adds to the
+// call's counters. The counters come back once, at the end. The claim flags and tables of the AND forms are not touched.
+
+static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
+                           size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream) {
+    if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
+    if (freq_blocks) *freq_blocks = 0;
+    if (n_queries == 0) return DINT_OK;
+    if (n_queries >= 0xFFFFFFFFull) return DINT_ERR_ARG;
+    const size_t n_lists = qi->list_len.size();
+    if (query_offsets[0] != 0 && !terms) return DINT_ERR_ARG;
+    for (size_t q = 0; q != n_queries; ++q)
+        if (query_offsets[q + 1] < query_offsets[q] || (query_offsets[q + 1] > query_offsets[q] && !terms)) return DINT_ERR_ARG;
+    const uint64_t t_first = query_offsets[0], t_all = query_offsets[n_queries] - t_first;
+    for (uint64_t i = 0; i != t_all; ++i)
+        if (terms[t_first + i] >= n_lists) return DINT_ERR_ARG;
+    // per query: distinct terms (queries.hpp:92), longest list first — the longest list probes nothing
+    std::vector<uint32_t> plan_terms(terms ? terms + t_first : nullptr, terms ? terms + t_first + t_all : nullptr);
+    std::vector<uint32_t> plan_len(n_queries, 0);
+    std::vector<uint64_t> plan_pages(n_queries, 0);
+    auto plan_of = [&](size_t q) { return plan_terms.data() + (query_offsets[q] - t_first); };
+    auto list_blocks = [&](uint32_t l) { return uint64_t(qi->list_first[l + 1] - qi->list_first[l]); };
+    uint64_t all_pages = 0;
+    for (size_t q = 0; q != n_queries; ++q) {
+        uint32_t* const t = plan_of(q);
+        uint32_t* t_end = t + (query_offsets[q + 1] - query_offsets[q]);
+        std::sort(t, t_end);
+        t_end = std::unique(t, t_end);
+        std::sort(t, t_end, [&](uint32_t a, uint32_t b) {
+            return qi->list_len[a] != qi->list_len[b] ? qi->list_len[a] > qi->list_len[b] : a < b;
+        });
+        counts[q] = 0;
+        if (freq_sums) freq_sums[q] = 0;
+        if (t == t_end) continue;  // queries.hpp:90-91
+        if (t_end - t == 1 && !freqs_dict) {  // one list: every posting is a result
+            counts[q] = qi->list_len[t[0]];
+            continue;
+        }
+        uint64_t pages = 0;
+        for (const uint32_t* p = t; p != t_end; ++p) pages += list_blocks(*p);
+        if (pages == 0) continue;  // (lists without a block)
+        plan_len[q] = uint32_t(t_end - t);
+        plan_pages[q] = pages;
+        all_pages += pages;
+    }
+    if (all_pages == 0) return DINT_OK;
+    // passes: whole queries, at most `limit` pages each — a query larger than that alone, in a pass sized to it
+    const uint64_t limit = uint64_t(opt(DINT_OPT_QUERY_OR_PASS_PAGES));
+    std::vector<size_t> pass_first(1, 0);  // pass k: queries [pass_first[k], pass_first[k + 1])
+    {
+        uint64_t in_pass = 0;
+        for (size_t q = 0; q != n_queries; ++q) {
+            if (in_pass != 0 && in_pass + plan_pages[q] > limit) {
+                pass_first.push_back(q);
+                in_pass = 0;
+            }
+            in_pass += plan_pages[q];
+        }
+        pass_first.push_back(n_queries);
+    }
+
+    std::lock_guard<std::mutex> lock(qi->mutex);
+    HIP_TRY(hipSetDevice(qi->docs->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto ensure_stage = [&](size_t bytes) -> hipError_t {  // (the pinned staging area the AND calls use too)
+        if (qi->h_stage_cap >= bytes) return hipSuccess;
+        if (qi->h_stage) (void)hipHostFree(qi->h_stage);
+        qi->h_stage = nullptr;
+        qi->h_stage_cap = 0;
+        const size_t want = bytes + bytes / 2 + 4096;
+        const hipError_t e = counted_host_malloc(&qi->h_stage, want);
+        if (e != hipSuccess) return e;
+        qi->h_stage_cap = want;
+        qi->d_stage = nullptr;
+        if (hipHostGetDevicePointer(&qi->d_stage, qi->h_stage, 0) != hipSuccess) qi->d_stage = nullptr;
+        return hipSuccess;
+    };
+    // the call's counters: counts[n_queries] then freq sums[n_queries], cleared once, added to by every pass
+    if (!qi->freq_sums.ensure(2 * n_queries)) return DINT_ERR_HIP;
+    unsigned long long* const d_counts = qi->freq_sums.p;
+    unsigned long long* const d_sums = d_counts + n_queries;
+    HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * n_queries * sizeof(unsigned long long), s));
+    auto failed = [&](int st) {
+        (void)hipStreamSynchronize(s);
+        return st;
+    };
+    for (size_t k = 0; k + 1 < pass_first.size(); ++k) {
+        const size_t q0 = pass_first[k], q1 = pass_first[k + 1];
+        uint64_t n_pages = 0, n_terms = 0;
+        for (size_t q = q0; q != q1; ++q) {
+            n_pages += plan_pages[q];
+            n_terms += plan_len[q];
+        }
+        if (n_pages == 0) continue;
+        // inputs: page -> block, page -> term record, then per term record {first block, blocks, first page, query, from}
+        const size_t words = 2 * n_pages + 5 * n_terms;
+        if (k != 0) HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area)
+        if (ensure_stage(std::max<size_t>(words * 4, 2 * n_queries * sizeof(unsigned long long))) != hipSuccess) return failed(DINT_ERR_HIP);
+        uint32_t* const h = static_cast<uint32_t*>(qi->h_stage);
+        uint32_t *page_block = h, *page_term = h + n_pages, *term_first = h + 2 * n_pages, *term_blocks = term_first + n_terms,
+                 *term_page = term_blocks + n_terms, *term_query = term_page + n_terms, *term_from = term_query + n_terms;
+        uint32_t page = 0, rec = 0;
+        for (size_t q = q0; q != q1; ++q) {
+            const uint32_t from = rec;
+            for (uint32_t j = 0; j != plan_len[q]; ++j, ++rec) {
+                const uint32_t l = plan_of(q)[j];
+                term_first[rec] = qi->list_first[l];
+                term_blocks[rec] = uint32_t(list_blocks(l));
+                term_page[rec] = page;
+                term_query[rec] = uint32_t(q);
+                term_from[rec] = from;
+                for (uint32_t b = qi->list_first[l]; b != qi->list_first[l + 1]; ++b, ++page) {
+                    page_block[page] = b;
+                    page_term[page] = rec;
+                }
+            }
+        }
+        if (!qi->inputs.ensure(words) || !qi->sub.ensure(n_pages) || !qi->probe.ensure(n_pages * kPageSlots) ||
+            (freqs_dict && !qi->fprobe.ensure(n_pages * kPageSlots)))
+            return failed(DINT_ERR_HIP);
+        uint32_t* const d_in = qi->inputs.p;
+        HIP_TRY(hipMemcpyAsync(d_in, h, words * 4, hipMemcpyHostToDevice, s));
+        const uint32_t tb = 256;
+        hipLaunchKernelGGL(gather_pages_kernel, dim3(uint32_t((n_pages + tb - 1) / tb)), dim3(tb), 0, s, qi->d_blocks, d_in, n_pages,
+                           qi->sub.p, static_cast<const uint32_t*>(nullptr));
+        const int st = decode_pages(qi, n_pages, qi->probe.p, freqs_dict, freqs_dict ? qi->fprobe.p : nullptr, s);
+        if (st != DINT_OK) return failed(st);
+        or_pass p{};
+        p.page_block = d_in;
+        p.page_term = d_in + n_pages;
+        p.term_first = d_in + 2 * n_pages;
+        p.term_blocks = p.term_first + n_terms;
+        p.term_page = p.term_blocks + n_terms;
+        p.term_query = p.term_page + n_terms;
+        p.term_from = p.term_query + n_terms;
+        p.blocks = qi->d_blocks;
+        p.block_max = qi->d_block_max;
+        p.docs = qi->probe.p;
+        p.freqs = freqs_dict ? qi->fprobe.p : nullptr;
+        p.counts = d_counts;
+        p.freq_sums = d_sums;
+        hipLaunchKernelGGL(or_count_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, p);
+        if (hipGetLastError() != hipSuccess) return failed(DINT_ERR_HIP);
+    }
+    HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area: the results go there)
+    if (ensure_stage(2 * n_queries * sizeof(unsigned long long)) != hipSuccess) return DINT_ERR_HIP;
+    unsigned long long* const h_res = static_cast<unsigned long long*>(qi->h_stage);
+    HIP_TRY(hipMemcpyAsync(h_res, d_counts, (freqs_dict ? 2 : 1) * n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t q = 0; q != n_queries; ++q)
+        if (plan_len[q] != 0) {
+            counts[q] = h_res[q];
+            if (freqs_dict) {
+                freq_sums[q] = h_res[n_queries + q];
+                if (freq_blocks) *freq_blocks += plan_pages[q];
+            }
+        }
+    return DINT_OK;
+}
+
+int dint_or_queries(dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries,
+                    uint64_t* counts, void* stream) {
+    return or_queries_impl(qi, nullptr, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream);
+}
+
+int dint_or_queries_freqs(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
+                          size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks_decoded, void* stream) {
+    if (!freqs_dict || !freq_sums) return DINT_ERR_ARG;
+    if (qi && (freqs_dict->device != qi->docs->device || freqs_dict->kind != qi->docs->kind)) return DINT_ERR_ARG;
+    return or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums, freq_blocks_decoded, stream);
+}

@@ -34,7 +34,7 @@ ABI_SYMBOLS = (
     "dint_decode_block_host", "dint_index_posting_lists", "dint_decode_posting_blocks",
     "dint_list_cache_create", "dint_list_cache_decode", "dint_list_cache_destroy",
     "dint_block_table_create", "dint_block_table_destroy", "dint_block_table_learn", "dint_block_table_ready", "dint_block_table_info_get", "dint_decode_block_table",
-    "dint_query_index_create", "dint_query_index_destroy", "dint_and_queries", "dint_and_queries_freqs", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
+    "dint_query_index_create", "dint_query_index_destroy", "dint_and_queries", "dint_and_queries_freqs", "dint_or_queries", "dint_or_queries_freqs", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
 
 #: dint_block_ref (include/dint_hip.h)
@@ -120,6 +120,8 @@ def _load():
     lib.dint_query_index_destroy.argtypes = [vp]
     lib.dint_and_queries.argtypes = [vp, vp, vp, sz, vp, vp]
     lib.dint_and_queries_freqs.argtypes = [vp, vp, vp, vp, sz, vp, vp, C.POINTER(u64), vp]
+    lib.dint_or_queries.argtypes = [vp, vp, vp, sz, vp, vp]
+    lib.dint_or_queries_freqs.argtypes = [vp, vp, vp, vp, sz, vp, vp, C.POINTER(u64), vp]
     lib.dint_count_ngrams.argtypes = [C.c_int, C.c_int, vp, u64, vp, u64, C.c_uint32, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_float)]
     lib.dint_select_ngrams.argtypes = [C.c_int, vp, u64, u64, vp, sz, C.c_uint32, C.POINTER(sz)]
     lib.dint_debug_wave_scan.argtypes = [vp, vp]
@@ -156,16 +158,24 @@ while _lib.dint_option_name(_i):
     OPTIONS[_lib.dint_option_name(_i).decode()] = _i
     _i += 1
 
+#: the workspace bounds among the options (numbered apart from the switches, include/dint_hip.h): name -> number
+LIMITS = {_lib.dint_option_name(32).decode(): 32}  # DINT_OPT_QUERY_OR_PASS_PAGES
+
+
+def _option_number(name: str) -> int:
+    return OPTIONS[name] if name in OPTIONS else LIMITS[name]
+
 
 def set_option(name: str, value: int) -> None:
     """dint_set_option: a process-wide switch for tests and measurements ("bundles", "index_concurrent",
-    "query_lean_pages", "query_tail_pages", "query_fused_pages", ... : device.OPTIONS lists them)."""
-    _check(_lib.dint_set_option(OPTIONS[name], int(value)), f"dint_set_option({name})")
+    "query_lean_pages", "query_tail_pages", "query_fused_pages", ... : device.OPTIONS lists them) or a workspace
+    bound ("query_or_pass_pages": device.LIMITS)."""
+    _check(_lib.dint_set_option(_option_number(name), int(value)), f"dint_set_option({name})")
 
 
 def get_option(name: str) -> int:
     v = C.c_longlong()
-    _check(_lib.dint_get_option(OPTIONS[name], C.byref(v)), f"dint_get_option({name})")
+    _check(_lib.dint_get_option(_option_number(name), C.byref(v)), f"dint_get_option({name})")
     return int(v.value)
 
 
@@ -481,8 +491,8 @@ class BlockTable:
 
 
 class QueryIndex:
-    """An index resident on the device, ready for conjunctive queries: the reference's
-    `index` + `and_query<false>` pair (include/ds2i/queries.hpp:34-84), a batch per call."""
+    """An index resident on the device, ready for conjunctive and disjunctive queries: the reference's
+    `index` + `and_query` / `or_query` pairs (include/ds2i/queries.hpp:34-130), a batch per call."""
 
     def __init__(self, docs_dict: "Dictionary", index: np.ndarray, list_offsets: np.ndarray):
         import torch
@@ -529,6 +539,35 @@ class QueryIndex:
     def and_queries_with_freqs(self, freqs_dict: "Dictionary", queries):
         """`and_query<true>` for a batch -> (counts, sums of the freqs read at the matches, freqs blocks decoded)."""
         return and_queries_with_freqs(self, freqs_dict, queries)
+
+    def or_queries(self, queries) -> np.ndarray:
+        """or_query<false> (include/ds2i/queries.hpp:86-130) for a batch: queries -> u64 counts of the union, one per query."""
+        import torch
+
+        terms, offs = _pack_queries(queries)
+        counts = np.zeros(len(queries), dtype=np.uint64)
+        stream = torch.cuda.current_stream(torch.device("cuda", self.docs_dict.device)).cuda_stream
+        _check(_lib.dint_or_queries(self._h, terms.ctypes.data, offs.ctypes.data, len(queries), counts.ctypes.data, stream),
+               "dint_or_queries")
+        return counts
+
+    def or_queries_packed(self, terms: np.ndarray, offsets: np.ndarray, counts: np.ndarray, stream: int = 0) -> None:
+        """The bare call, as and_queries_packed."""
+        _check(_lib.dint_or_queries(self._h, terms.ctypes.data, offsets.ctypes.data, counts.size, counts.ctypes.data, stream),
+               "dint_or_queries")
+
+    def or_queries_with_freqs(self, freqs_dict: "Dictionary", queries):
+        """`or_query<true>` for a batch -> (counts, sums of the freqs of every posting of every distinct term, freqs blocks decoded)."""
+        import torch
+
+        terms, offs = _pack_queries(queries)
+        counts = np.zeros(len(queries), dtype=np.uint64)
+        sums = np.zeros(len(queries), dtype=np.uint64)
+        nblocks = C.c_uint64()
+        stream = torch.cuda.current_stream(torch.device("cuda", self.docs_dict.device)).cuda_stream
+        _check(_lib.dint_or_queries_freqs(self._h, freqs_dict._h, terms.ctypes.data, offs.ctypes.data, len(queries),
+                                          counts.ctypes.data, sums.ctypes.data, C.byref(nblocks), stream), "dint_or_queries_freqs")
+        return counts, sums, nblocks.value
 
 
 def _pack_queries(queries):

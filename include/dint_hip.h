@@ -113,7 +113,11 @@ typedef enum dint_option {
     DINT_OPT_REFINE_UNITS = 11,       /* 1 (default): a prepared multi-dictionary unit table whose units hold several 256-integer  */
                                       /* blocks (at most 131072 integers each) finds the blocks once and decodes a table of      */
                                       /* blocks; 0: the units as they came (a wavefront decodes a unit's blocks one after another) */
-    DINT_OPT_COUNT_ = 12
+    DINT_OPT_COUNT_ = 12,
+    /* Workspace bounds, numbered apart from the switches above (dint_option_name enumerates those from 0 up to the first
+     * NULL; a bound's name is asked for by its number): */
+    DINT_OPT_QUERY_OR_PASS_PAGES = 32 /* an OR call decodes at most this many pages (256 docIDs each) at a time, whole queries */
+                                      /* per pass; a larger query runs alone. Default 1048576 (1 GiB of docIDs), 1 .. 2^32-1 */
 } dint_option;
 int dint_set_option(int option, long long value);
 int dint_get_option(int option, long long* value);
@@ -376,6 +380,28 @@ int dint_and_queries(dint_query_index* qi, const uint32_t* terms, const uint64_t
 int dint_and_queries_freqs(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms,
                            const uint64_t* query_offsets, size_t n_queries, uint64_t* counts, uint64_t* freq_sums,
                            uint64_t* freq_blocks_decoded, void* stream);
+
+/* ---- disjunctive queries over the same query index --------------------------------------------
+ * counts[q] = number of distinct documents that contain at least one term of query q: or_query<false>
+ * (include/ds2i/queries.hpp:86-130, driven by src/queries.cpp:15-61 op_perftest), for a batch of queries per call.
+ * Duplicate terms count once (queries.hpp:29-32, :92); an empty query counts 0 (:90-91). Arguments, host arrays, the
+ * handle's lock and the stream are as for dint_and_queries: the call enqueues on `stream` and returns after
+ * synchronising it. A term >= n_lists is DINT_ERR_ARG. A single-term query is answered from the list's length, with no
+ * launch. Otherwise every block of every distinct term is decoded (the reference's loop reads every posting), in
+ * passes of whole queries of at most DINT_OPT_QUERY_OR_PASS_PAGES pages, and ONE probe launch per pass counts every
+ * posting that no earlier (longer) list of its query holds. The workspaces are the AND calls' own;
+ * OR calls leave their claim tables as they found them. */
+int dint_or_queries(dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets,
+                    size_t n_queries, uint64_t* counts, void* stream);
+
+/* or_query<true> (queries.hpp:86-130 with_freqs: freq() is read for every posting of every distinct term, :110-122):
+ * the same counts, and freq_sums[q] = the sum, over the distinct terms of q and over every posting of the term's list,
+ * of the posting's frequency. *freq_blocks_decoded (nullable) = the blocks whose freqs part was decoded: every block of
+ * every distinct term of every query of the call (a block in the lists of several queries counts once per list).
+ * freqs_dict: of the same kind and device as the query index's docs dictionary. */
+int dint_or_queries_freqs(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms,
+                          const uint64_t* query_offsets, size_t n_queries, uint64_t* counts, uint64_t* freq_sums,
+                          uint64_t* freq_blocks_decoded, void* stream);
 
 /* ---- block statistics on the device (dictionary construction, counting half) ----------------------------
  * Counts every aligned 16/8/4/2/1-gram of the given lists — multi != 0: of their whole 256-integer blocks, per block

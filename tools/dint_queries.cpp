@@ -2,7 +2,8 @@
 //
 //   dint_queries <index_type> <query_type> <index_filename> [--batch] [--runs R] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
-//   query_type: and | and_freq, several separated by ':' (src/queries.cpp:93-96); the ranked and OR queries are out of scope
+//   query_type: and | and_freq | or | or_freq, several separated by ':' (src/queries.cpp:93-103); the ranked queries are out of
+//               scope (they print "Unsupported query type", as the reference does for a type it does not know)
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   query_log on stdin: one query per line, term ids separated by blanks (include/ds2i/queries.hpp:15-27)
 //
@@ -99,20 +100,32 @@ int main(int argc, char** argv) {
             a = b + 1;
         }
         for (auto const& t : types) {
-            if (t != "and" && t != "and_freq") {
+            if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq") {
                 std::cerr << "Unsupported query type: " << t << std::endl;  // src/queries.cpp:108-110
                 continue;
             }
-            const bool with_freqs = t == "and_freq";
+            const bool with_freqs = t == "and_freq" || t == "or_freq";
+            const bool is_or = t == "or" || t == "or_freq";
+            // one call of the query type's entry: n queries, packed
+            auto run_queries = [&](const uint32_t* q_terms, const uint64_t* q_offs, size_t n, uint64_t* q_counts, uint64_t* q_fsums) {
+                uint64_t fblocks = 0;
+                if (is_or && with_freqs)
+                    dint_ok(dint_or_queries_freqs(qi, freqs_dict, q_terms, q_offs, n, q_counts, q_fsums, &fblocks, nullptr), "dint_or_queries_freqs");
+                else if (is_or)
+                    dint_ok(dint_or_queries(qi, q_terms, q_offs, n, q_counts, nullptr), "dint_or_queries");
+                else if (with_freqs)
+                    dint_ok(dint_and_queries_freqs(qi, freqs_dict, q_terms, q_offs, n, q_counts, q_fsums, &fblocks, nullptr), "dint_and_queries_freqs");
+                else
+                    dint_ok(dint_and_queries(qi, q_terms, q_offs, n, q_counts, nullptr), "dint_and_queries");
+            };
             std::vector<double> query_times;
             uint64_t total = 0, total_one_run = 0;
             for (size_t run = 0; run != runs; ++run) {  // op_perftest
                 for (auto const& q : queries) {
                     const uint64_t offs[2] = {0, q.size()};
-                    uint64_t results = 0, fsum = 0, fblocks = 0;
+                    uint64_t results = 0, fsum = 0;
                     const double tick = now_us();
-                    if (with_freqs) dint_ok(dint_and_queries_freqs(qi, freqs_dict, q.data(), offs, 1, &results, &fsum, &fblocks, nullptr), "dint_and_queries_freqs");
-                    else dint_ok(dint_and_queries(qi, q.data(), offs, 1, &results, nullptr), "dint_and_queries");
+                    run_queries(q.data(), offs, 1, &results, &fsum);
                     total += results;
                     if (run == 0) total_one_run += results;
                     if (run != 0) query_times.push_back(now_us() - tick);  // first run is not timed
@@ -129,10 +142,8 @@ int main(int argc, char** argv) {
                 }
                 double best = 1e300;
                 for (size_t run = 0; run != std::min<size_t>(runs, 4); ++run) {
-                    uint64_t fblocks = 0;
                     const double tick = now_us();
-                    if (with_freqs) dint_ok(dint_and_queries_freqs(qi, freqs_dict, terms.data(), offs.data(), queries.size(), counts.data(), fsums.data(), &fblocks, nullptr), "dint_and_queries_freqs");
-                    else dint_ok(dint_and_queries(qi, terms.data(), offs.data(), queries.size(), counts.data(), nullptr), "dint_and_queries");
+                    run_queries(terms.data(), offs.data(), queries.size(), counts.data(), fsums.data());
                     if (run != 0) best = std::min(best, now_us() - tick);
                 }
                 batch_us = best / double(queries.size());
