@@ -2,7 +2,7 @@
 // launches. ONE translation unit (the kernels are templates in headers; the handles are shared): its parts live under
 // host/ by subsystem and are included here in order — common helpers and handles first, then the extern "C" block
 // (opened in host/hip_api_common.inc, closed at the end of this file): dictionary, vroom decode, in-index decode,
-// AND and OR queries, statistics, host-pointer calls, list cache.
+// AND, OR and ranked AND queries, statistics, host-pointer calls, list cache.
 #include "dint_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <mutex>
 #include <cstddef>
 #include <cstdio>
@@ -26,6 +27,7 @@
 #include "dint_kernels.hpp"
 #include "dint_query_kernels.hpp"
 #include "dint_or_query_kernels.hpp"
+#include "dint_ranked_query_kernels.hpp"
 #include "dint_stats_kernels.hpp"
 
 #include "host/hip_common.inc"
@@ -38,6 +40,7 @@
 #include "host/hip_api_index.inc"
 #include "host/hip_api_query.inc"
 #include "host/hip_api_or_query.inc"
+#include "host/hip_api_ranked_query.inc"
 #include "host/hip_api_stats.inc"
 #include "host/hip_api_host_calls.inc"
 #include "host/hip_api_list_cache.inc"

@@ -28,6 +28,12 @@ void dint_query_index_destroy(dint_query_index* qi) {
     qi->batch_ctrl.release();
     qi->sub.release();
     qi->units.release();
+    qi->slot_score.release();
+    qi->slot_kden.release();
+    qi->qweights.release();
+    qi->topk_in.release();
+    qi->topk_keys.release();
+    qi->topk_out.release();
     delete qi;
 }
 
@@ -57,6 +63,7 @@ int dint_query_index_create(const dint_dict* docs_dict, const uint8_t* d_index, 
         qi->list_first[l + 1] += 1;
         qi->list_len[l] += blocks[b].n;
         maxs[b] = blocks[b].max;
+        qi->doc_bound = std::max<uint64_t>(qi->doc_bound, uint64_t(blocks[b].max) + 1);
     }
     for (size_t l = 0; l != n_lists; ++l) qi->list_first[l + 1] += qi->list_first[l];
     const size_t nb = std::max<size_t>(1, n_blocks);
@@ -207,8 +214,20 @@ static int decode_pages_lean(dint_query_index* qi, const uint32_t* d_ids, const 
     return DINT_OK;
 }
 
+// dint_ranked_and_queries (hip_api_ranked_query.inc): what the freqs pass scores with, and where the selection goes
+struct ranked_args {
+    const float* norm_lens;    // device, the wand handle's
+    const float* q_weight;     // host: [j * n_queries + q] = q_weight of the j-th term of query q in this path's term order
+    size_t q_weight_len;
+    uint32_t k;
+    unsigned long long* keys;  // host, n_queries * k: the best keys of every query (ranked_topk)
+};
+static int ranked_topk(dint_query_index* qi, const ranked_args& rk, const std::vector<uint32_t>& page_query, size_t n_queries,
+                       hipStream_t s);
+
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
-                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split = true);
+                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split = true,
+                            const ranked_args* rk = nullptr);
 
 int dint_and_queries(dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries,
                      uint64_t* counts, void* stream) {
@@ -223,7 +242,8 @@ int dint_and_queries_freqs(dint_query_index* qi, const dint_dict* freqs_dict, co
 }
 
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
-                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split) {
+                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split,
+                            const ranked_args* rk) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -269,6 +289,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     }
     const size_t n_pages = h_page_block.size();
     if (n_pages == 0) return DINT_OK;
+    if (rk && (!freqs_dict || rk->q_weight_len < (rounds + 1) * n_queries)) return DINT_ERR_ARG;
     // A MIXED call — queries of a few candidate pages among queries of hundreds: the small ones go through the
     // workgroup-per-query launch (below), the others through the round-per-launch form, as two calls of this function over the
     // sorted plans (a single large query no longer takes a log of small ones onto the slow form with it).
@@ -767,6 +788,12 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
         // as in the rounds above. The counts themselves travel to the host with the results.)
         if (!qi->freq_counts.ensure(rounds + 1)) return DINT_ERR_HIP;
         HIP_TRY(hipMemsetAsync(qi->freq_counts.p, 0, (rounds + 1) * 4, s));
+        if (rk) {  // ranked_and: a score per candidate slot, from 0.0f; the q_weights of every term of every query
+            if (!qi->slot_score.ensure(n_slots) || !qi->slot_kden.ensure(n_slots) || !qi->qweights.ensure(rk->q_weight_len))
+                return DINT_ERR_HIP;
+            HIP_TRY(hipMemsetAsync(qi->slot_score.p, 0, n_slots * sizeof(float), s));
+            HIP_TRY(hipMemcpyAsync(qi->qweights.p, rk->q_weight, rk->q_weight_len * sizeof(float), hipMemcpyHostToDevice, s));
+        }
         for (size_t r = 0; r != rounds + 1; ++r) {  // r = 0: the rarest term; r >= 1: the term of round r - 1
             const uint32_t* first = r ? d_term_first + (r - 1) * n_queries : nullptr;
             const uint32_t* nblk = r ? d_term_blocks + (r - 1) * n_queries : nullptr;
@@ -803,11 +830,23 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
                 (void)hipStreamSynchronize(s);
                 return st;
             }
-            hipLaunchKernelGGL(and_freq_gather_kernel, dim3(slot_grid), dim3(tb), 0, s, qi->cand.p, n_slots, d_page_query, nblk,
-                               qi->d_blocks, qi->target.p, qi->d_rank, qi->probe.p, qi->fprobe.p, qi->freq_sums.p);
+            if (rk)  // (the terms in this path's order: the score is summed in the reference's order, DESIGN.md 4d-ranked)
+                hipLaunchKernelGGL(ranked_gather_kernel, dim3(slot_grid), dim3(tb), 0, s, qi->cand.p, n_slots, d_page_query, nblk,
+                                   qi->d_blocks, qi->target.p, qi->d_rank, qi->probe.p, qi->fprobe.p, qi->qweights.p + r * n_queries,
+                                   rk->norm_lens, qi->slot_kden.p, qi->slot_score.p);
+            else
+                hipLaunchKernelGGL(and_freq_gather_kernel, dim3(slot_grid), dim3(tb), 0, s, qi->cand.p, n_slots, d_page_query, nblk,
+                                   qi->d_blocks, qi->target.p, qi->d_rank, qi->probe.p, qi->fprobe.p, qi->freq_sums.p);
             hipLaunchKernelGGL(and_release_kernel, dim3(tgrid), dim3(tb), 0, s, qi->d_touched, uint32_t(bound), qi->d_needed, d_count);
         }
         HIP_TRY(hipGetLastError());
+        if (rk) {
+            st = ranked_topk(qi, *rk, h_page_query, n_queries, s);
+            if (st != DINT_OK) {
+                (void)hipStreamSynchronize(s);
+                return st;
+            }
+        }
         h_sums.resize(n_queries);
         HIP_TRY(hipMemcpyAsync(h_sums.data(), qi->freq_sums.p, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         h_freq_counts.resize(rounds + 1);

@@ -1,0 +1,181 @@
+// Part of dint_hip.hip (one translation unit; included from there, in order): extern "C": ranked conjunctive queries
+// (ranked_and_query, queries.hpp:309-385) and the wand data they read (wand_data.hpp:18-57).
+// ---- ranked conjunctive queries -----------------------------------------------------------------
+// A ranked call is an and_query<true> call (and_queries_impl) whose freqs pass scores instead of summing: per term, in
+// the AND path's order, ranked_gather_kernel adds q_weight * doc_term_weight to every match's slot. Behind the last term,
+// ranked_topk selects the k best of every query (dint_ranked_query_kernels.hpp). The claim tables, workspaces and lock
+// are the AND calls' own.
+
+struct dint_wand_data {
+    int device = 0;
+    uint64_t num_docs = 0;
+    float* d_norm_lens = nullptr;
+};
+
+void dint_wand_data_destroy(dint_wand_data* wd) {
+    if (!wd) return;
+    if (wd->d_norm_lens) {
+        (void)hipSetDevice(wd->device);
+        (void)hipFree(wd->d_norm_lens);
+    }
+    delete wd;
+}
+
+int dint_wand_data_create(int device, const float* norm_lens, uint64_t num_docs, dint_wand_data** out) {
+    if (!out || (num_docs && !norm_lens) || num_docs > 0x100000000ull) return DINT_ERR_ARG;
+    *out = nullptr;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return DINT_ERR_NO_DEVICE;
+    auto* wd = new (std::nothrow) dint_wand_data();
+    if (!wd) return DINT_ERR_NOMEM;
+    wd->device = device;
+    wd->num_docs = num_docs;
+    const bool ok = hip_ok(hipSetDevice(device), "hipSetDevice") &&
+                    hip_ok(counted_malloc(&wd->d_norm_lens, std::max<uint64_t>(1, num_docs) * sizeof(float)), "counted_malloc(norm_lens)") &&
+                    (num_docs == 0 ||
+                     hip_ok(hipMemcpy(wd->d_norm_lens, norm_lens, num_docs * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(norm_lens)"));
+    if (!ok) {
+        dint_wand_data_destroy(wd);
+        return DINT_ERR_HIP;
+    }
+    *out = wd;
+    return DINT_OK;
+}
+
+// The selection of and_queries_impl's ranked form, on its stream, behind the freqs pass: query q's candidate pages are the
+// pages p with page_query[p] == q (consecutive). Its slots are cut into runs of R keys, every run sorted, then the runs
+// merged pairwise, pass after pass (a pass serves every query of the call), until run 0 of every query holds its best R.
+// rk.keys <- the first k of them (copied on the stream: the caller synchronises).
+static int ranked_topk(dint_query_index* qi, const ranked_args& rk, const std::vector<uint32_t>& page_query, size_t n_queries,
+                       hipStream_t s) {
+    uint32_t R = kPageSlots;
+    while (R < rk.k) R <<= 1;
+    std::vector<uint32_t> q_page_first(n_queries, 0), q_pages(n_queries, 0);
+    for (size_t p = 0; p != page_query.size(); ++p) {
+        const uint32_t q = page_query[p];
+        if (q_pages[q] == 0) q_page_first[q] = uint32_t(p);
+        q_pages[q] += 1;
+    }
+    std::vector<unsigned long long> key_base(n_queries, 0);
+    std::vector<uint32_t> runs(n_queries, 0);
+    uint64_t n_keys = 0;
+    uint32_t most_runs = 0;
+    for (size_t q = 0; q != n_queries; ++q) {
+        runs[q] = uint32_t((uint64_t(q_pages[q]) * kPageSlots + R - 1) / R);
+        key_base[q] = n_keys;
+        n_keys += uint64_t(runs[q]) * R;
+        most_runs = std::max(most_runs, runs[q]);
+    }
+    // tasks: pass 0 sorts every run; pass p >= 1 merges run a + 2^(p-1) into run a, a = 0, 2^p, 2 * 2^p, ...
+    std::vector<topk_task> tasks;
+    std::vector<size_t> pass_first(1, 0);
+    for (size_t q = 0; q != n_queries; ++q)
+        for (uint32_t a = 0; a != runs[q]; ++a) tasks.push_back({uint32_t(q), a, 0u});
+    pass_first.push_back(tasks.size());
+    for (uint64_t half = 1; half < most_runs; half <<= 1) {
+        for (size_t q = 0; q != n_queries; ++q)
+            for (uint64_t a = 0; a + half < runs[q]; a += 2 * half) tasks.push_back({uint32_t(q), uint32_t(a), uint32_t(a + half)});
+        pass_first.push_back(tasks.size());
+    }
+    // inputs: the tasks, then per query {first page, pages}, then the key bases (8-byte aligned)
+    const size_t task_words = tasks.size() * 3, base_at = (task_words + 2 * n_queries + 1) / 2 * 2;
+    const size_t words = base_at + 2 * n_queries;
+    std::vector<uint32_t> h(words, 0);
+    std::memcpy(h.data(), tasks.data(), task_words * 4);
+    std::memcpy(h.data() + task_words, q_page_first.data(), n_queries * 4);
+    std::memcpy(h.data() + task_words + n_queries, q_pages.data(), n_queries * 4);
+    std::memcpy(h.data() + base_at, key_base.data(), n_queries * 8);
+    if (!qi->topk_in.ensure(words) || !qi->topk_keys.ensure(std::max<uint64_t>(1, n_keys)) ||
+        !qi->topk_out.ensure(uint64_t(n_queries) * rk.k))
+        return DINT_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(qi->topk_in.p, h.data(), words * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // (h is pageable host memory of this frame)
+    const topk_task* const d_tasks = reinterpret_cast<const topk_task*>(qi->topk_in.p);
+    const uint32_t* const d_page_first = qi->topk_in.p + task_words;
+    const uint32_t* const d_pages = d_page_first + n_queries;
+    const unsigned long long* const d_base = reinterpret_cast<const unsigned long long*>(qi->topk_in.p + base_at);
+    const uint32_t tb = 256;
+    for (size_t p = 0; p + 1 < pass_first.size(); ++p) {
+        const size_t n_tasks = pass_first[p + 1] - pass_first[p];
+        if (n_tasks == 0) continue;
+        if (p == 0)
+            hipLaunchKernelGGL(topk_sort_runs_kernel, dim3(uint32_t(n_tasks)), dim3(tb), R * sizeof(unsigned long long), s, d_tasks,
+                               d_page_first, d_pages, d_base, qi->cand.p, qi->slot_score.p, R, qi->topk_keys.p);
+        else
+            hipLaunchKernelGGL(topk_merge_kernel, dim3(uint32_t(n_tasks)), dim3(tb), R * sizeof(unsigned long long), s,
+                               d_tasks + pass_first[p], d_base, R, qi->topk_keys.p);
+    }
+    const uint64_t n_out = uint64_t(n_queries) * rk.k;
+    hipLaunchKernelGGL(topk_out_kernel, dim3(uint32_t((n_out + tb - 1) / tb)), dim3(tb), 0, s, d_base, d_pages, qi->topk_keys.p,
+                       uint32_t(n_queries), rk.k, qi->topk_out.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rk.keys, qi->topk_out.p, n_out * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    return DINT_OK;
+}
+
+int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                            const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts, float* scores,
+                            uint32_t* docids, void* stream) {
+    if (!qi || !freqs_dict || !wd || k == 0 || k > kRankedMaxK) return DINT_ERR_ARG;
+    if (n_queries && (!query_offsets || !counts || !scores)) return DINT_ERR_ARG;
+    if (freqs_dict->device != qi->docs->device || freqs_dict->kind != qi->docs->kind || wd->device != qi->docs->device)
+        return DINT_ERR_ARG;
+    if (qi->doc_bound > wd->num_docs) return DINT_ERR_ARG;  // (norm_lens[docid] must exist for every docID of the index)
+    if (n_queries == 0) return DINT_OK;
+    if (n_queries >= 0xFFFFFFFFull || uint64_t(n_queries) * k > (uint64_t(1) << 32)) return DINT_ERR_ARG;
+    if (query_offsets[0] != 0 && !terms) return DINT_ERR_ARG;
+    for (size_t q = 0; q != n_queries; ++q)
+        if (query_offsets[q + 1] < query_offsets[q] || (query_offsets[q + 1] > query_offsets[q] && !terms)) return DINT_ERR_ARG;
+    const size_t n_lists = qi->list_len.size();
+    const uint64_t t_first = query_offsets[0], t_all = query_offsets[n_queries] - t_first;
+    for (uint64_t i = 0; i != t_all; ++i)
+        if (terms[t_first + i] >= n_lists) return DINT_ERR_ARG;
+    // per query: distinct terms with their multiplicity (query_freqs, queries.hpp:135-148) in and_queries_impl's order —
+    // by list length, equal lengths by term — and q_weight = bm25::query_term_weight(qf, df, num_docs) in that order
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> tq(n_queries);  // {term, qf}
+    size_t most_terms = 1;
+    for (size_t q = 0; q != n_queries; ++q) {
+        std::vector<uint32_t> t(terms + query_offsets[q], terms + query_offsets[q + 1]);
+        std::sort(t.begin(), t.end());
+        for (size_t i = 0; i != t.size(); ++i) {
+            if (i == 0 || t[i] != t[i - 1]) tq[q].push_back({t[i], 1u});
+            else tq[q].back().second += 1;
+        }
+        std::sort(tq[q].begin(), tq[q].end(), [&](std::pair<uint32_t, uint32_t> a, std::pair<uint32_t, uint32_t> b) {
+            return qi->list_len[a.first] != qi->list_len[b.first] ? qi->list_len[a.first] < qi->list_len[b.first] : a.first < b.first;
+        });
+        most_terms = std::max(most_terms, tq[q].size());
+    }
+    std::vector<float> q_weight(most_terms * n_queries, 0.0f);
+    for (size_t q = 0; q != n_queries; ++q)
+        for (size_t j = 0; j != tq[q].size(); ++j) {
+            // bm25::query_term_weight (bm25.hpp), binary32 in its source order
+            const float f = float(tq[q][j].second);
+            const float fdf = float(qi->list_len[tq[q][j].first]);
+            const float idf = std::log((float(wd->num_docs) - fdf + 0.5f) / (fdf + 0.5f));
+            const float epsilon_score = 1.0E-6f;
+            q_weight[j * n_queries + q] = f * std::max(epsilon_score, idf) * (1.0f + kBm25K1);
+        }
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
+    std::vector<uint64_t> freq_sums(n_queries, 0);
+    ranked_args rk{};
+    rk.norm_lens = wd->d_norm_lens;
+    rk.q_weight = q_weight.data();
+    rk.q_weight_len = q_weight.size();
+    rk.k = k;
+    rk.keys = keys.data();
+    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk);
+    if (st != DINT_OK) return st;
+    for (size_t q = 0; q != n_queries; ++q) {
+        counts[q] = std::min<uint64_t>(counts[q], k);
+        for (uint32_t i = 0; i != k; ++i) {
+            const unsigned long long key = i < counts[q] ? keys[q * k + i] : 0ull;
+            const uint32_t bits = uint32_t(key >> 32);
+            float sc = 0.0f;
+            std::memcpy(&sc, &bits, 4);
+            scores[q * k + i] = key ? sc : 0.0f;
+            if (docids) docids[q * k + i] = key ? 0xFFFFFFFFu - uint32_t(key) : 0xFFFFFFFFu;
+        }
+    }
+    return DINT_OK;
+}

@@ -54,6 +54,12 @@ struct dint_query_index {
     device_buffer<uint32_t> slot_needed, slot_rank, slot_touched, batch_ctrl;
     size_t slot_needed_clean = 0;  // words of slot_needed known to be zero (the buffer grows: a new one is cleared once)
     bool slots_dirty = false;      // a call that did not run to its end may have left claim flags in slot_needed
+    // ranked_and (hip_api_ranked_query.inc): the largest docID of the index + 1 (0: no blocks), per candidate slot the
+    // score and k1 * ((1 - b) + b * norm_len), per term and query the q_weight, the selection's tasks and keys
+    uint64_t doc_bound = 0;
+    device_buffer<float> slot_score, slot_kden, qweights;
+    device_buffer<uint32_t> topk_in;
+    device_buffer<unsigned long long> topk_keys, topk_out;
     std::mutex mutex;
 };
 

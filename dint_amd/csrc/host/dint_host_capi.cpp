@@ -1,7 +1,10 @@
 // C ABI of the offline CPU half (see include/dint_host.h).
 #include "dint_host.h"
 
+#include <algorithm>
+#include <cstdio>
 #include <cstring>
+#include <stdexcept>
 #include <exception>
 #include <string>
 #include <utility>
@@ -245,6 +248,39 @@ int build_dictionary_collection(bool multi, dint::binary_collection const& input
     *out = b;
     return DINT_OK;
 }
+// wand_data (reference include/ds2i/wand_data.hpp:18-57) in binary32, uncontracted: the device's BM25 scores
+// (dint_ranked_and_queries) and these must round alike. len_of(i) / list_of(i) -> list i's size and {docids, freqs}.
+template <typename LenOf, typename ListOf>
+__attribute__((optimize("fp-contract=off"))) void wand_data_of(uint32_t const* sizes, uint64_t num_docs, uint64_t n_lists,
+                                                                LenOf&& len_of, ListOf&& list_of, float* norm_lens,
+                                                                float* max_term_weight) {
+    double lens_sum = 0;
+    for (uint64_t i = 0; i != num_docs; ++i) {
+        const float len = float(sizes[i]);
+        norm_lens[i] = len;
+        lens_sum += len;
+    }
+    const float avg_len = float(lens_sum / double(num_docs));
+    for (uint64_t i = 0; i != num_docs; ++i) norm_lens[i] /= avg_len;
+    const float b = 0.5f, k1 = 1.2f;  // bm25 (bm25.hpp)
+    for (uint64_t t = 0; t != n_lists; ++t) {
+        const uint64_t n = len_of(t);
+        auto const lists = list_of(t);
+        float max_score = 0;
+        for (uint64_t i = 0; i != n; ++i) {
+            const uint64_t docid = lists.first[i];
+            if (docid >= num_docs) throw std::invalid_argument("docID beyond the sizes' documents");
+            const float f = float(lists.second[i]);
+            const float score = f / (f + k1 * (1.0f - b + b * norm_lens[docid]));
+            max_score = std::max(max_score, score);
+        }
+        max_term_weight[t] = max_score;
+    }
+}
+
+constexpr uint32_t kWandMagic = 0x444E5744u;  // "DWND"
+constexpr uint32_t kWandVersion = 1;
+
 }  // namespace
 
 extern "C" {
@@ -461,6 +497,101 @@ int dinth_build_index_collection(int kind, int greedy, const void* docs_dict_fil
             kind, greedy, docs_dict_file, docs_dict_len, freqs_dict_file, freqs_dict_len, d.size(),
             [&](uint64_t i) { return d[i].size(); }, [&](uint64_t i) { return std::make_pair(d[i].begin(), f[i].begin()); },
             threads, index, offsets);
+    });
+}
+
+int dinth_wand_data(const uint32_t* sizes, uint64_t num_docs, const uint32_t* docids, const uint32_t* freqs, const uint32_t* lens,
+                    uint64_t n_lists, float* norm_lens, float* max_term_weight) {
+    if ((num_docs && (!sizes || !norm_lens)) || (n_lists && (!lens || !max_term_weight))) return DINT_ERR_ARG;
+    uint64_t total = 0;
+    for (uint64_t t = 0; t != n_lists; ++t) total += lens[t];
+    if (total && (!docids || !freqs || num_docs == 0)) return DINT_ERR_ARG;
+    return guarded([&] {
+        std::vector<uint64_t> first(n_lists + 1, 0);
+        for (uint64_t t = 0; t != n_lists; ++t) first[t + 1] = first[t] + lens[t];
+        wand_data_of(
+            sizes, num_docs, n_lists, [&](uint64_t t) { return uint64_t(lens[t]); },
+            [&](uint64_t t) { return std::make_pair(docids + first[t], freqs + first[t]); }, norm_lens, max_term_weight);
+        return int(DINT_OK);
+    });
+}
+
+int dinth_read_sizes(const char* path, dinth_blob** sizes) {
+    if (!path || !sizes) return DINT_ERR_ARG;
+    return guarded([&] {
+        dint::binary_collection coll(path);
+        auto seqs = coll.sequences();
+        if (seqs.empty()) throw std::runtime_error("a .sizes file holds one record");
+        *sizes = blob_of(std::vector<uint32_t>(seqs.front().begin(), seqs.front().end()));
+        return int(DINT_OK);
+    });
+}
+
+int dinth_wand_data_collection(const uint32_t* sizes_words, size_t n_sizes_words, const uint32_t* docs_words, size_t n_docs_words,
+                               const uint32_t* freqs_words, size_t n_freqs_words, dinth_blob** norm_lens,
+                               dinth_blob** max_term_weight, uint64_t* num_docs) {
+    if (!sizes_words || !docs_words || !freqs_words || !norm_lens || !max_term_weight) return DINT_ERR_ARG;
+    return guarded([&] {
+        dint::binary_collection sz(sizes_words, n_sizes_words), docs(docs_words, n_docs_words), freqs(freqs_words, n_freqs_words);
+        auto s = sz.sequences();
+        auto d = docs.sequences();
+        auto f = freqs.sequences();
+        if (d.empty() || d.front().size() != 1)
+            throw std::invalid_argument("First sequence should only contain number of documents");
+        const uint64_t nd = *d.front().begin();
+        d.erase(d.begin());
+        if (d.size() != f.size()) throw std::runtime_error("docs and freqs files do not match");
+        for (size_t i = 0; i != d.size(); ++i)
+            if (d[i].size() != f[i].size()) throw std::runtime_error("docs and freqs files do not match");
+        if (s.empty() || s.front().size() < nd) throw std::runtime_error("the .sizes record is shorter than num_docs");
+        std::vector<float> nl(nd), mtw(d.size());
+        wand_data_of(
+            s.front().begin(), nd, d.size(), [&](uint64_t t) { return uint64_t(d[t].size()); },
+            [&](uint64_t t) { return std::make_pair(d[t].begin(), f[t].begin()); }, nl.data(), mtw.data());
+        *norm_lens = blob_of(nl);
+        *max_term_weight = blob_of(mtw);
+        if (num_docs) *num_docs = nd;
+        return int(DINT_OK);
+    });
+}
+
+int dinth_write_wand_data(const char* path, const float* norm_lens, uint64_t num_docs, const float* max_term_weight,
+                          uint64_t n_lists) {
+    if (!path || (num_docs && !norm_lens) || (n_lists && !max_term_weight)) return DINT_ERR_ARG;
+    return guarded([&] {
+        std::FILE* fp = std::fopen(path, "wb");
+        if (!fp) throw std::runtime_error(std::string("cannot write ") + path);
+        const uint32_t head[2] = {kWandMagic, kWandVersion};
+        const uint64_t counts[2] = {num_docs, n_lists};
+        bool ok = std::fwrite(head, 4, 2, fp) == 2 && std::fwrite(counts, 8, 2, fp) == 2 &&
+                  std::fwrite(norm_lens, 4, num_docs, fp) == num_docs && std::fwrite(max_term_weight, 4, n_lists, fp) == n_lists;
+        ok = std::fclose(fp) == 0 && ok;
+        if (!ok) throw std::runtime_error(std::string("cannot write ") + path);
+        return int(DINT_OK);
+    });
+}
+
+int dinth_read_wand_data(const char* path, dinth_blob** norm_lens, dinth_blob** max_term_weight) {
+    if (!path || !norm_lens || !max_term_weight) return DINT_ERR_ARG;
+    return guarded([&] {
+        std::FILE* fp = std::fopen(path, "rb");
+        if (!fp) throw std::runtime_error(std::string("Error opening file ") + path);
+        uint32_t head[2] = {0, 0};
+        uint64_t counts[2] = {0, 0};
+        bool ok = std::fread(head, 4, 2, fp) == 2 && std::fread(counts, 8, 2, fp) == 2 && head[0] == kWandMagic && head[1] == kWandVersion &&
+                  counts[0] <= (uint64_t(1) << 32) && counts[1] <= (uint64_t(1) << 32);
+        std::vector<float> nl, mtw;
+        if (ok) {
+            nl.resize(counts[0]);
+            mtw.resize(counts[1]);
+            ok = std::fread(nl.data(), 4, nl.size(), fp) == nl.size() && std::fread(mtw.data(), 4, mtw.size(), fp) == mtw.size() &&
+                 std::fgetc(fp) == EOF;
+        }
+        std::fclose(fp);
+        if (!ok) throw std::runtime_error(std::string("not a wand data file: ") + path);
+        *norm_lens = blob_of(nl);
+        *max_term_weight = blob_of(mtw);
+        return int(DINT_OK);
     });
 }
 

@@ -86,6 +86,12 @@ def _load():
     lib.dinth_block_selector.argtypes = [vp, C.c_size_t]
     lib.dinth_dict_entry.argtypes = [i32, vp, C.c_size_t, u32, u32, C.POINTER(u32), vp]
     lib.dinth_dict_num_entries.argtypes = [i32, vp, C.c_size_t, u32, C.POINTER(u32)]
+    lib.dinth_wand_data.argtypes = [vp, u64, vp, vp, vp, u64, vp, vp]
+    lib.dinth_read_sizes.argtypes = [C.c_char_p, C.POINTER(vp)]
+    lib.dinth_wand_data_collection.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(vp),
+                                               C.POINTER(u64)]
+    lib.dinth_write_wand_data.argtypes = [C.c_char_p, vp, u64, vp, u64]
+    lib.dinth_read_wand_data.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(vp)]
     return lib
 
 
@@ -315,6 +321,60 @@ def write_collection(basename: str, docid_lists, freq_lists, num_docs: int) -> N
     """<basename>.docs and <basename>.freqs as the reference's tools read them."""
     collection_words(docid_lists, num_docs).tofile(basename + ".docs")
     collection_words(freq_lists).tofile(basename + ".freqs")
+
+
+# ---- wand data (reference include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp; include/dint_host.h) ----
+
+def sizes_from_postings(docids: np.ndarray, freqs: np.ndarray, num_docs: int) -> np.ndarray:
+    """The document sizes of a synthetic corpus: a document's size is the sum of the freqs of its postings (u32[num_docs])."""
+    d = np.asarray(docids, dtype=np.int64)
+    return np.bincount(d, weights=np.asarray(freqs, dtype=np.float64), minlength=num_docs)[:num_docs].astype(np.uint32)
+
+
+def write_sizes(path: str, sizes) -> None:
+    """<basename>.sizes: a collection file of one record, the documents' sizes."""
+    collection_words([sizes]).tofile(path)
+
+
+def read_sizes(path: str) -> np.ndarray:
+    """The sizes of a <basename>.sizes file (dinth_read_sizes) -> u32[]."""
+    h = C.c_void_p()
+    _check(_lib.dinth_read_sizes(os.fsencode(path), C.byref(h)))
+    return _take_blob(h, np.uint32)
+
+
+def wand_data(sizes, docids: np.ndarray, freqs: np.ndarray, lens: np.ndarray):
+    """wand_data's arrays (dinth_wand_data): -> (norm_lens f32[len(sizes)], max_term_weight f32[len(lens)]). docids / freqs:
+    the lists back to back, lens[t] postings each, as for build_index."""
+    sizes, docids, freqs, lens = _u32(sizes), _u32(docids), _u32(freqs), _u32(lens)
+    norm_lens = np.zeros(sizes.size, dtype=np.float32)
+    mtw = np.zeros(lens.size, dtype=np.float32)
+    _check(_lib.dinth_wand_data(sizes.ctypes.data, sizes.size, docids.ctypes.data, freqs.ctypes.data, lens.ctypes.data, lens.size,
+                                norm_lens.ctypes.data, mtw.ctypes.data))
+    return norm_lens, mtw
+
+
+def wand_data_collection(sizes_words: np.ndarray, docs_words: np.ndarray, freqs_words: np.ndarray):
+    """create_wand_data over a collection's words (.sizes, .docs, .freqs) -> (norm_lens, max_term_weight, num_docs)."""
+    s, d, f = _u32(sizes_words), _u32(docs_words), _u32(freqs_words)
+    hn, hm, nd = C.c_void_p(), C.c_void_p(), C.c_uint64()
+    _check(_lib.dinth_wand_data_collection(s.ctypes.data, s.size, d.ctypes.data, d.size, f.ctypes.data, f.size, C.byref(hn),
+                                           C.byref(hm), C.byref(nd)))
+    return _take_blob(hn, np.float32), _take_blob(hm, np.float32), nd.value
+
+
+def write_wand_data(path: str, norm_lens: np.ndarray, max_term_weight: np.ndarray) -> None:
+    """The wand data file of this repository (layout: include/dint_host.h)."""
+    nl = np.ascontiguousarray(norm_lens, dtype=np.float32)
+    mtw = np.ascontiguousarray(max_term_weight, dtype=np.float32)
+    _check(_lib.dinth_write_wand_data(os.fsencode(path), nl.ctypes.data, nl.size, mtw.ctypes.data, mtw.size))
+
+
+def read_wand_data(path: str):
+    """-> (norm_lens f32[num_docs], max_term_weight f32[n_lists]) of a wand data file (dinth_read_wand_data)."""
+    hn, hm = C.c_void_p(), C.c_void_p()
+    _check(_lib.dinth_read_wand_data(os.fsencode(path), C.byref(hn), C.byref(hm)))
+    return _take_blob(hn, np.float32), _take_blob(hm, np.float32)
 
 
 def encode_collection(kind: int, dict_file: bytes, words: np.ndarray, docs: bool, unit_ints: int = 4096, greedy: bool = False,

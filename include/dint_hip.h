@@ -403,6 +403,32 @@ int dint_or_queries_freqs(dint_query_index* qi, const dint_dict* freqs_dict, con
                           const uint64_t* query_offsets, size_t n_queries, uint64_t* counts, uint64_t* freq_sums,
                           uint64_t* freq_blocks_decoded, void* stream);
 
+/* ---- ranked conjunctive queries (BM25 top-k) over the same query index ---------------------------
+ * Replaces: wand_data's norm_lens (include/ds2i/wand_data.hpp:18-57) on the device, and ranked_and_query
+ * (include/ds2i/queries.hpp:309-385, src/queries.cpp:106-108) for a batch of queries per call.
+ * dint_wand_data_create uploads norm_lens (HOST, num_docs floats: dinth_wand_data of include/dint_host.h) to `device` once;
+ * the handle owns its copy. */
+typedef struct dint_wand_data dint_wand_data;
+int dint_wand_data_create(int device, const float* norm_lens, uint64_t num_docs, dint_wand_data** out);
+void dint_wand_data_destroy(dint_wand_data* wd);
+
+#define DINT_RANKED_MAX_K 1024 /* the largest k dint_ranked_and_queries takes */
+
+/* For query q — its distinct terms t with multiplicity qf_t (query_freqs, queries.hpp:135-148) — every document d of the
+ * intersection of their lists scores sum_t q_weight_t * doc_term_weight(freq_t(d), norm_lens[d]) (bm25.hpp), with
+ * q_weight_t = query_term_weight(qf_t, df_t = the list's length, wd's num_docs), the sum taken over the terms in order of
+ * increasing list length, equal lengths by increasing term id, every operation a binary32 one, uncontracted, in the
+ * reference's source order. counts[q] = min(k, size of the intersection); scores[q * k + i] /
+ * docids[q * k + i] for i < counts[q]: the best documents, by descending score, equal scores by ascending docID; past
+ * counts[q]: 0.0f / 0xFFFFFFFF. scores (and docids, nullable) are HOST arrays of n_queries * k. Terms, query_offsets,
+ * counts, the handle's lock and the stream are as for dint_and_queries_freqs; an empty query counts 0. DINT_ERR_ARG: k == 0
+ * or k > DINT_RANKED_MAX_K, a term >= n_lists, a freqs_dict of another kind or device than the docs dictionary, a wand
+ * handle on another device, or one whose num_docs does not exceed the index's largest docID — checked before anything is
+ * launched. Every query takes the round-per-launch form (never the workgroup-per-query batch form of dint_and_queries). */
+int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                            const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts,
+                            float* scores, uint32_t* docids, void* stream);
+
 /* ---- block statistics on the device (dictionary construction, counting half) ----------------------------
  * Counts every aligned 16/8/4/2/1-gram of the given lists — multi != 0: of their whole 256-integer blocks, per block
  * context — keyed by the MurmurHash64A of its integers, as the reference's collectors do.

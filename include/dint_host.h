@@ -123,6 +123,32 @@ int dinth_build_index_collection(int kind, int greedy, const void* docs_dict_fil
                                  size_t freqs_dict_len, const uint32_t* docs_words, size_t n_docs_words, const uint32_t* freqs_words,
                                  size_t n_freqs_words, int threads, dinth_blob** index, dinth_blob** offsets, uint64_t* num_docs);
 
+/* ---- wand data (reference include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp) ----------------------------------
+ * The per-document lengths and per-list maxima of BM25 that ranked queries read (dint_ranked_and_queries takes norm_lens):
+ *   norm_lens[i]       = float(sizes[i]) / avg_len, avg_len = float(sum of the float(sizes[i]) as a double / double(num_docs));
+ *   max_term_weight[t] = the largest bm25::doc_term_weight(freq, norm_lens[docid]) over list t's postings (0 for an empty list).
+ * Every float operation is a binary32 one in the reference's source order, never contracted into an FMA.
+ * docids / freqs / lens as for dinth_build_index; norm_lens: num_docs floats, max_term_weight: n_lists floats, the caller's.
+ * A docID >= num_docs is DINT_ERR_FORMAT. */
+int dinth_wand_data(const uint32_t* sizes, uint64_t num_docs, const uint32_t* docids, const uint32_t* freqs, const uint32_t* lens,
+                    uint64_t n_lists, float* norm_lens, float* max_term_weight);
+/* A <basename>.sizes file: a binary collection (u32 words) of one record — its length, then one size per document.
+ * -> *sizes: the record's values (u32). */
+int dinth_read_sizes(const char* path, dinth_blob** sizes);
+/* create_wand_data over a collection's words (.sizes, .docs, .freqs): num_docs is record 0 of .docs, the first num_docs
+ * values of the .sizes record are the documents' sizes. -> norm_lens (f32[num_docs]), max_term_weight (f32[n_lists]). */
+int dinth_wand_data_collection(const uint32_t* sizes_words, size_t n_sizes_words, const uint32_t* docs_words, size_t n_docs_words,
+                               const uint32_t* freqs_words, size_t n_freqs_words, dinth_blob** norm_lens,
+                               dinth_blob** max_term_weight, uint64_t* num_docs);
+/* The wand data file of this repository (dint_create_wand_data writes it), little-endian:
+ *   u32 magic 0x444E5744 ("DWND"), u32 version 1, u64 num_docs, u64 n_lists,
+ *   f32 norm_lens[num_docs], f32 max_term_weight[n_lists], and nothing after.
+ * It is a layout of our own: byte compatibility with the reference's file (succinct::mapper::freeze of wand_data) is not
+ * a goal. dinth_read_wand_data refuses a file that does not have exactly this shape (DINT_ERR_FORMAT). */
+int dinth_write_wand_data(const char* path, const float* norm_lens, uint64_t num_docs, const float* max_term_weight,
+                          uint64_t n_lists);
+int dinth_read_wand_data(const char* path, dinth_blob** norm_lens, dinth_blob** max_term_weight);
+
 /* MurmurHash64A(seed 0) of n u32 words (reference include/dint/hash_utils.hpp:7-80). */
 uint64_t dinth_hash_u32s(const uint32_t* p, size_t n);
 

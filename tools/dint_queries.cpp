@@ -1,10 +1,12 @@
 // dint_queries — the reference's `queries` tool (src/queries.cpp:15-153) for the DINT index types, on the device path.
 //
-//   dint_queries <index_type> <query_type> <index_filename> [--batch] [--runs R] < query_log
+//   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
-//   query_type: and | and_freq | or | or_freq, several separated by ':' (src/queries.cpp:93-103); the ranked queries are out of
-//               scope (they print "Unsupported query type", as the reference does for a type it does not know)
+//   query_type: and | and_freq | or | or_freq | ranked_and, several separated by ':' (src/queries.cpp:93-111); ranked_and
+//               (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints "Unsupported
+//               query type", as the reference does; wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
+//   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
 //   query_log on stdin: one query per line, term ids separated by blanks (include/ds2i/queries.hpp:15-27)
 //
 // Like op_perftest (src/queries.cpp:15-61): every query on its own, `runs` passes of which the first is not timed, the total
@@ -35,18 +37,21 @@ static double now_us() {
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [--batch] [--runs R] < query_log" << std::endl;
+        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] < query_log"
+                  << std::endl;
         return 1;
     }
     try {
         std::string type = argv[1], query_type = argv[2];
         const char* index_filename = argv[3];
+        const char* wand_filename = nullptr;
         bool batch = false;
         size_t runs = 10 + 1;  // src/queries.cpp:13
         for (int i = 4; i < argc; ++i) {
             std::string a = argv[i];
             if (a == "--batch") batch = true;
             else if (a == "--runs" && i + 1 < argc) runs = size_t(std::max(2, std::atoi(argv[++i])));
+            else if (!wand_filename && a.rfind("--", 0) != 0) wand_filename = argv[i];
             else throw std::runtime_error("unknown parameter");
         }
         const int kind = tool::kind_of_type(type);
@@ -91,6 +96,15 @@ int main(int argc, char** argv) {
             throw std::runtime_error("could not place the index on the device");
         dint_query_index* qi = nullptr;
         dint_ok(dint_query_index_create(docs_dict, d_index, index_bytes, blocks, n_blocks, n_lists, &qi), "dint_query_index_create");
+        dint_wand_data* wand = nullptr;
+        if (wand_filename) {  // (the reference maps the wand data once, src/queries.cpp:84-89)
+            tool::blob norm_lens, max_term_weight;
+            tool::host_ok(dinth_read_wand_data(wand_filename, &norm_lens.h, &max_term_weight.h), "dinth_read_wand_data");
+            dint_ok(dint_wand_data_create(0, static_cast<const float*>(norm_lens.data()), norm_lens.size() / 4, &wand),
+                    "dint_wand_data_create");
+        }
+        constexpr uint32_t kTopK = 10;  // ranked_and_query(wdata, 10), src/queries.cpp:106-108
+        std::vector<float> top_scores;
 
         std::vector<std::string> types;
         for (size_t a = 0; a <= query_type.size();) {
@@ -100,7 +114,8 @@ int main(int argc, char** argv) {
             a = b + 1;
         }
         for (auto const& t : types) {
-            if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq") {
+            const bool is_ranked = t == "ranked_and" && wand;
+            if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
                 std::cerr << "Unsupported query type: " << t << std::endl;  // src/queries.cpp:108-110
                 continue;
             }
@@ -109,7 +124,11 @@ int main(int argc, char** argv) {
             // one call of the query type's entry: n queries, packed
             auto run_queries = [&](const uint32_t* q_terms, const uint64_t* q_offs, size_t n, uint64_t* q_counts, uint64_t* q_fsums) {
                 uint64_t fblocks = 0;
-                if (is_or && with_freqs)
+                if (is_ranked) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    dint_ok(dint_ranked_and_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr, nullptr),
+                            "dint_ranked_and_queries");
+                } else if (is_or && with_freqs)
                     dint_ok(dint_or_queries_freqs(qi, freqs_dict, q_terms, q_offs, n, q_counts, q_fsums, &fblocks, nullptr), "dint_or_queries_freqs");
                 else if (is_or)
                     dint_ok(dint_or_queries(qi, q_terms, q_offs, n, q_counts, nullptr), "dint_or_queries");
@@ -164,6 +183,7 @@ int main(int argc, char** argv) {
             if (batch_us >= 0) std::cout << ", \"batch_us_per_query\": " << batch_us;
             std::cout << ", \"device\": \"" << device_name << "\"}" << std::endl;
         }
+        dint_wand_data_destroy(wand);
         dint_query_index_destroy(qi);
         dint_free(blocks);
         (void)hipFree(d_index);
