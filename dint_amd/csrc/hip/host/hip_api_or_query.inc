@@ -5,9 +5,12 @@
 // whole queries of at most DINT_OPT_QUERY_OR_PASS_PAGES pages; per pass one copy in, the pages' decode (decode_pages, as
 // the AND path decodes its freqs pages) and ONE probe launch (or_count_kernel, dint_or_query_kernels.hpp) that adds to the
 // call's counters. The counters come back once, at the end. The claim flags and tables of the AND forms are not touched.
+// rk (dint_ranked_or_queries, hip_api_ranked_or_query.inc): the pass's probe launch is ranked_or_score_kernel instead, and
+// ranked_topk writes the best keys of the pass's queries to rk->keys at their own offset; the counters are not used.
 
 static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
-                           size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream) {
+                           size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream,
+                           const ranked_args* rk = nullptr) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -21,6 +24,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         if (terms[t_first + i] >= n_lists) return DINT_ERR_ARG;
     // per query: distinct terms (queries.hpp:92), longest list first — the longest list probes nothing
     std::vector<uint32_t> plan_terms(terms ? terms + t_first : nullptr, terms ? terms + t_first + t_all : nullptr);
+    std::vector<uint32_t> plan_qf(rk ? plan_terms.size() : 0);  // (rk) beside plan_terms: the term's multiplicity
     std::vector<uint32_t> plan_len(n_queries, 0);
     std::vector<uint64_t> plan_pages(n_queries, 0);
     auto plan_of = [&](size_t q) { return plan_terms.data() + (query_offsets[q] - t_first); };
@@ -30,10 +34,28 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         uint32_t* const t = plan_of(q);
         uint32_t* t_end = t + (query_offsets[q + 1] - query_offsets[q]);
         std::sort(t, t_end);
-        t_end = std::unique(t, t_end);
-        std::sort(t, t_end, [&](uint32_t a, uint32_t b) {
+        auto longest_first = [&](uint32_t a, uint32_t b) {
             return qi->list_len[a] != qi->list_len[b] ? qi->list_len[a] > qi->list_len[b] : a < b;
-        });
+        };
+        if (rk) {  // distinct terms with their multiplicity (query_freqs, queries.hpp:135-148), longest list first
+            std::vector<std::pair<uint32_t, uint32_t>> tq;
+            for (const uint32_t* r = t; r != t_end; ++r) {
+                if (r == t || *r != r[-1]) tq.push_back({*r, 1u});
+                else tq.back().second += 1;
+            }
+            std::sort(tq.begin(), tq.end(), [&](std::pair<uint32_t, uint32_t> a, std::pair<uint32_t, uint32_t> b) {
+                return longest_first(a.first, b.first);
+            });
+            uint32_t* const qf = plan_qf.data() + (t - plan_terms.data());
+            for (size_t j = 0; j != tq.size(); ++j) {
+                t[j] = tq[j].first;
+                qf[j] = tq[j].second;
+            }
+            t_end = t + tq.size();
+        } else {
+            t_end = std::unique(t, t_end);
+            std::sort(t, t_end, longest_first);
+        }
         counts[q] = 0;
         if (freq_sums) freq_sums[q] = 0;
         if (t == t_end) continue;  // queries.hpp:90-91
@@ -98,15 +120,23 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         }
         if (n_pages == 0) continue;
         // inputs: page -> block, page -> term record, then per term record {first block, blocks, first page, query, from}
-        const size_t words = 2 * n_pages + 5 * n_terms;
+        // (rk: and {the records of its query by term id, its query's terms, q_weight})
+        const size_t words = 2 * n_pages + (rk ? 8 : 5) * n_terms;
         if (k != 0) HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area)
         if (ensure_stage(std::max<size_t>(words * 4, 2 * n_queries * sizeof(unsigned long long))) != hipSuccess) return failed(DINT_ERR_HIP);
         uint32_t* const h = static_cast<uint32_t*>(qi->h_stage);
         uint32_t *page_block = h, *page_term = h + n_pages, *term_first = h + 2 * n_pages, *term_blocks = term_first + n_terms,
-                 *term_page = term_blocks + n_terms, *term_query = term_page + n_terms, *term_from = term_query + n_terms;
+                 *term_page = term_blocks + n_terms, *term_query = term_page + n_terms, *term_from = term_query + n_terms,
+                 *term_order = term_from + n_terms, *term_n = term_order + n_terms;
+        float* const term_weight = reinterpret_cast<float*>(term_n + n_terms);
         uint32_t page = 0, rec = 0;
         for (size_t q = q0; q != q1; ++q) {
             const uint32_t from = rec;
+            if (rk) {  // the query's records by ascending term id: the order its scores are summed in
+                for (uint32_t j = 0; j != plan_len[q]; ++j) term_order[from + j] = from + j;
+                std::sort(term_order + from, term_order + from + plan_len[q],
+                          [&](uint32_t a, uint32_t b) { return plan_of(q)[a - from] < plan_of(q)[b - from]; });
+            }
             for (uint32_t j = 0; j != plan_len[q]; ++j, ++rec) {
                 const uint32_t l = plan_of(q)[j];
                 term_first[rec] = qi->list_first[l];
@@ -114,6 +144,10 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
                 term_page[rec] = page;
                 term_query[rec] = uint32_t(q);
                 term_from[rec] = from;
+                if (rk) {
+                    term_n[rec] = plan_len[q];
+                    term_weight[rec] = bm25_query_term_weight(plan_qf[query_offsets[q] - t_first + j], qi->list_len[l], rk->num_docs);
+                }
                 for (uint32_t b = qi->list_first[l]; b != qi->list_first[l + 1]; ++b, ++page) {
                     page_block[page] = b;
                     page_term[page] = rec;
@@ -144,10 +178,31 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         p.freqs = freqs_dict ? qi->fprobe.p : nullptr;
         p.counts = d_counts;
         p.freq_sums = d_sums;
+        if (rk) {  // score the union's representatives, then select every query's best k (one query: one pass)
+            if (!qi->cand.ensure(n_pages * kPageSlots) || !qi->slot_score.ensure(n_pages * kPageSlots)) return failed(DINT_ERR_HIP);
+            ranked_or_pass rp{};
+            rp.base = p;
+            rp.term_order = p.term_from + n_terms;
+            rp.term_n = rp.term_order + n_terms;
+            rp.term_weight = reinterpret_cast<const float*>(rp.term_n + n_terms);
+            rp.norm_lens = rk->norm_lens;
+            rp.cand = qi->cand.p;
+            rp.score = qi->slot_score.p;
+            hipLaunchKernelGGL(ranked_or_score_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, rp);
+            if (hipGetLastError() != hipSuccess) return failed(DINT_ERR_HIP);
+            std::vector<uint32_t> page_query(n_pages);  // (the pass's queries, from 0)
+            for (uint64_t pg = 0; pg != n_pages; ++pg) page_query[pg] = term_query[page_term[pg]] - uint32_t(q0);
+            ranked_args pass_rk = *rk;
+            pass_rk.keys = rk->keys + uint64_t(q0) * rk->k;
+            const int rst = ranked_topk(qi, pass_rk, page_query, q1 - q0, s);
+            if (rst != DINT_OK) return failed(rst);
+            continue;
+        }
         hipLaunchKernelGGL(or_count_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, p);
         if (hipGetLastError() != hipSuccess) return failed(DINT_ERR_HIP);
     }
     HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area: the results go there)
+    if (rk) return DINT_OK;            // (ranked: the keys are already on the host)
     if (ensure_stage(2 * n_queries * sizeof(unsigned long long)) != hipSuccess) return DINT_ERR_HIP;
     unsigned long long* const h_res = static_cast<unsigned long long*>(qi->h_stage);
     HIP_TRY(hipMemcpyAsync(h_res, d_counts, (freqs_dict ? 2 : 1) * n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));

@@ -215,13 +215,23 @@ static int decode_pages_lean(dint_query_index* qi, const uint32_t* d_ids, const 
 }
 
 // dint_ranked_and_queries (hip_api_ranked_query.inc): what the freqs pass scores with, and where the selection goes
+// (dint_ranked_or_queries: the same, q_weight unused — the OR pass computes its terms' weights from num_docs)
 struct ranked_args {
     const float* norm_lens;    // device, the wand handle's
     const float* q_weight;     // host: [j * n_queries + q] = q_weight of the j-th term of query q in this path's term order
     size_t q_weight_len;
     uint32_t k;
     unsigned long long* keys;  // host, n_queries * k: the best keys of every query (ranked_topk)
+    uint64_t num_docs;         // the wand handle's
 };
+// bm25::query_term_weight (bm25.hpp), binary32 in its source order: qf = the term's multiplicity, df = its list's length
+static float bm25_query_term_weight(uint32_t qf, uint64_t df, uint64_t num_docs) {
+    const float f = float(qf);
+    const float fdf = float(df);
+    const float idf = std::log((float(num_docs) - fdf + 0.5f) / (fdf + 0.5f));
+    const float epsilon_score = 1.0E-6f;
+    return f * std::max(epsilon_score, idf) * (1.0f + kBm25K1);
+}
 static int ranked_topk(dint_query_index* qi, const ranked_args& rk, const std::vector<uint32_t>& page_query, size_t n_queries,
                        hipStream_t s);
 

@@ -148,14 +148,8 @@ int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, c
     }
     std::vector<float> q_weight(most_terms * n_queries, 0.0f);
     for (size_t q = 0; q != n_queries; ++q)
-        for (size_t j = 0; j != tq[q].size(); ++j) {
-            // bm25::query_term_weight (bm25.hpp), binary32 in its source order
-            const float f = float(tq[q][j].second);
-            const float fdf = float(qi->list_len[tq[q][j].first]);
-            const float idf = std::log((float(wd->num_docs) - fdf + 0.5f) / (fdf + 0.5f));
-            const float epsilon_score = 1.0E-6f;
-            q_weight[j * n_queries + q] = f * std::max(epsilon_score, idf) * (1.0f + kBm25K1);
-        }
+        for (size_t j = 0; j != tq[q].size(); ++j)
+            q_weight[j * n_queries + q] = bm25_query_term_weight(tq[q][j].second, qi->list_len[tq[q][j].first], wd->num_docs);
     std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
     std::vector<uint64_t> freq_sums(n_queries, 0);
     ranked_args rk{};
@@ -164,6 +158,7 @@ int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, c
     rk.q_weight_len = q_weight.size();
     rk.k = k;
     rk.keys = keys.data();
+    rk.num_docs = wd->num_docs;
     const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk);
     if (st != DINT_OK) return st;
     for (size_t q = 0; q != n_queries; ++q) {

@@ -35,7 +35,7 @@ ABI_SYMBOLS = (
     "dint_list_cache_create", "dint_list_cache_decode", "dint_list_cache_destroy",
     "dint_block_table_create", "dint_block_table_destroy", "dint_block_table_learn", "dint_block_table_ready", "dint_block_table_info_get", "dint_decode_block_table",
     "dint_query_index_create", "dint_query_index_destroy", "dint_and_queries", "dint_and_queries_freqs", "dint_or_queries", "dint_or_queries_freqs",
-    "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
+    "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_or_queries", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
 
 #: dint_block_ref (include/dint_hip.h)
@@ -127,6 +127,7 @@ def _load():
     lib.dint_wand_data_destroy.restype = None
     lib.dint_wand_data_destroy.argtypes = [vp]
     lib.dint_ranked_and_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, vp]
+    lib.dint_ranked_or_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, vp]
     lib.dint_count_ngrams.argtypes = [C.c_int, C.c_int, vp, u64, vp, u64, C.c_uint32, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_float)]
     lib.dint_select_ngrams.argtypes = [C.c_int, vp, u64, u64, vp, sz, C.c_uint32, C.POINTER(sz)]
     lib.dint_debug_wave_scan.argtypes = [vp, vp]
@@ -496,8 +497,9 @@ class BlockTable:
 
 
 class QueryIndex:
-    """An index resident on the device, ready for conjunctive, disjunctive and ranked conjunctive queries: the reference's
-    `index` + `and_query` / `or_query` / `ranked_and_query` pairs (include/ds2i/queries.hpp:34-130, :309-385), a batch per call."""
+    """An index resident on the device, ready for conjunctive, disjunctive, ranked conjunctive and ranked disjunctive
+    queries: the reference's `index` + `and_query` / `or_query` / `ranked_and_query` / `ranked_or_query` pairs
+    (include/ds2i/queries.hpp:34-130, :309-457), a batch per call."""
 
     def __init__(self, docs_dict: "Dictionary", index: np.ndarray, list_offsets: np.ndarray):
         import torch
@@ -590,6 +592,23 @@ class QueryIndex:
         _check(_lib.dint_ranked_and_queries(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data, n,
                                             counts.ctypes.data, scores.ctypes.data, docids.ctypes.data, stream),
                "dint_ranked_and_queries")
+        return counts, scores, docids
+
+    def ranked_or_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10):
+        """ranked_or_query (include/ds2i/queries.hpp:387-457) for a batch: BM25 top-k of the union, each document's score
+        summed over the query's terms in ascending term id -> (counts u64[n] = min(k, |union|), scores f32[n, k]
+        descending, docids u32[n, k]; equal scores by ascending docID, 0.0 / 0xFFFFFFFF past a query's count)."""
+        import torch
+
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        counts = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        stream = torch.cuda.current_stream(torch.device("cuda", self.docs_dict.device)).cuda_stream
+        _check(_lib.dint_ranked_or_queries(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data, n,
+                                           counts.ctypes.data, scores.ctypes.data, docids.ctypes.data, stream),
+               "dint_ranked_or_queries")
         return counts, scores, docids
 
 

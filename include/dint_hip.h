@@ -412,7 +412,7 @@ typedef struct dint_wand_data dint_wand_data;
 int dint_wand_data_create(int device, const float* norm_lens, uint64_t num_docs, dint_wand_data** out);
 void dint_wand_data_destroy(dint_wand_data* wd);
 
-#define DINT_RANKED_MAX_K 1024 /* the largest k dint_ranked_and_queries takes */
+#define DINT_RANKED_MAX_K 1024 /* the largest k dint_ranked_and_queries and dint_ranked_or_queries take */
 
 /* For query q — its distinct terms t with multiplicity qf_t (query_freqs, queries.hpp:135-148) — every document d of the
  * intersection of their lists scores sum_t q_weight_t * doc_term_weight(freq_t(d), norm_lens[d]) (bm25.hpp), with
@@ -428,6 +428,23 @@ void dint_wand_data_destroy(dint_wand_data* wd);
 int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
                             const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts,
                             float* scores, uint32_t* docids, void* stream);
+
+/* ---- ranked disjunctive queries (BM25 top-k of the union) over the same query index --------------
+ * Replaces: ranked_or_query (include/ds2i/queries.hpp:387-457) for a batch of queries per call. (Not a query type of
+ * the reference's driver, src/queries.cpp:93-111.)
+ * For query q — its distinct terms t with multiplicity qf_t — every document d of the union of their lists scores
+ *     score = 0.0f; for t in ascending term id, if d is in L_t: score = score + q_weight_t * doc_term_weight(freq_t(d), norm_lens[d])
+ * with q_weight_t as for dint_ranked_and_queries, every operation a binary32 one, uncontracted, in the reference's source
+ * order. The sum runs in ascending term id, the order of query_freqs (queries.hpp:135-148) and so
+ * of ranked_or_query, unlike dint_ranked_and_queries, which sums in list-length order. wand_query and maxscore_query
+ * (queries.hpp:190-307, :459-575) return the same documents, but add the same terms in data-dependent orders and may
+ * differ from these scores in the last bits. counts[q] = min(k, size of the union); the arguments, outputs, errors
+ * (all checked before anything is launched), the handle's lock and the stream are exactly those of
+ * dint_ranked_and_queries. The call runs in passes of whole queries of at most DINT_OPT_QUERY_OR_PASS_PAGES pages, as
+ * dint_or_queries_freqs does, and every document of a union is scored by one thread, at its first occurrence. */
+int dint_ranked_or_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                           const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts,
+                           float* scores, uint32_t* docids, void* stream);
 
 /* ---- block statistics on the device (dictionary construction, counting half) ----------------------------
  * Counts every aligned 16/8/4/2/1-gram of the given lists — multi != 0: of their whole 256-integer blocks, per block

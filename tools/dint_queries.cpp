@@ -2,9 +2,11 @@
 //
 //   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
-//   query_type: and | and_freq | or | or_freq | ranked_and, several separated by ':' (src/queries.cpp:93-111); ranked_and
-//               (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints "Unsupported
-//               query type", as the reference does; wand and maxscore are out of scope and always print it
+//   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or, several separated by ':' (src/queries.cpp:93-111);
+//               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
+//               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
+//               BM25 top 10 of the union) is not in the reference driver's list, and is answered as ranked_and is, with
+//               the wand file, and refused the same way without one; wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
 //   query_log on stdin: one query per line, term ids separated by blanks (include/ds2i/queries.hpp:15-27)
@@ -114,7 +116,8 @@ int main(int argc, char** argv) {
             a = b + 1;
         }
         for (auto const& t : types) {
-            const bool is_ranked = t == "ranked_and" && wand;
+            const bool is_ranked_or = t == "ranked_or" && wand;
+            const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
                 std::cerr << "Unsupported query type: " << t << std::endl;  // src/queries.cpp:108-110
                 continue;
@@ -124,7 +127,11 @@ int main(int argc, char** argv) {
             // one call of the query type's entry: n queries, packed
             auto run_queries = [&](const uint32_t* q_terms, const uint64_t* q_offs, size_t n, uint64_t* q_counts, uint64_t* q_fsums) {
                 uint64_t fblocks = 0;
-                if (is_ranked) {
+                if (is_ranked_or) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    dint_ok(dint_ranked_or_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr, nullptr),
+                            "dint_ranked_or_queries");
+                } else if (is_ranked) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_and_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr, nullptr),
                             "dint_ranked_and_queries");
