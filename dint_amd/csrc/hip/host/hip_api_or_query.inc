@@ -15,60 +15,16 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
     if (n_queries >= 0xFFFFFFFFull) return DINT_ERR_ARG;
-    const size_t n_lists = qi->list_len.size();
-    if (query_offsets[0] != 0 && !terms) return DINT_ERR_ARG;
-    for (size_t q = 0; q != n_queries; ++q)
-        if (query_offsets[q + 1] < query_offsets[q] || (query_offsets[q + 1] > query_offsets[q] && !terms)) return DINT_ERR_ARG;
-    const uint64_t t_first = query_offsets[0], t_all = query_offsets[n_queries] - t_first;
-    for (uint64_t i = 0; i != t_all; ++i)
-        if (terms[t_first + i] >= n_lists) return DINT_ERR_ARG;
-    // per query: distinct terms (queries.hpp:92), longest list first — the longest list probes nothing
-    std::vector<uint32_t> plan_terms(terms ? terms + t_first : nullptr, terms ? terms + t_first + t_all : nullptr);
-    std::vector<uint32_t> plan_qf(rk ? plan_terms.size() : 0);  // (rk) beside plan_terms: the term's multiplicity
-    std::vector<uint32_t> plan_len(n_queries, 0);
+    query_plan plan;  // (rk: with multiplicities, for the query weights)
+    const int planned = plan_queries(qi, terms, query_offsets, n_queries, true, rk != nullptr, freqs_dict != nullptr, counts, freq_sums, plan);
+    if (planned != DINT_OK) return planned;
     std::vector<uint64_t> plan_pages(n_queries, 0);
-    auto plan_of = [&](size_t q) { return plan_terms.data() + (query_offsets[q] - t_first); };
     auto list_blocks = [&](uint32_t l) { return uint64_t(qi->list_first[l + 1] - qi->list_first[l]); };
     uint64_t all_pages = 0;
     for (size_t q = 0; q != n_queries; ++q) {
-        uint32_t* const t = plan_of(q);
-        uint32_t* t_end = t + (query_offsets[q + 1] - query_offsets[q]);
-        std::sort(t, t_end);
-        auto longest_first = [&](uint32_t a, uint32_t b) {
-            return qi->list_len[a] != qi->list_len[b] ? qi->list_len[a] > qi->list_len[b] : a < b;
-        };
-        if (rk) {  // distinct terms with their multiplicity (query_freqs, queries.hpp:135-148), longest list first
-            std::vector<std::pair<uint32_t, uint32_t>> tq;
-            for (const uint32_t* r = t; r != t_end; ++r) {
-                if (r == t || *r != r[-1]) tq.push_back({*r, 1u});
-                else tq.back().second += 1;
-            }
-            std::sort(tq.begin(), tq.end(), [&](std::pair<uint32_t, uint32_t> a, std::pair<uint32_t, uint32_t> b) {
-                return longest_first(a.first, b.first);
-            });
-            uint32_t* const qf = plan_qf.data() + (t - plan_terms.data());
-            for (size_t j = 0; j != tq.size(); ++j) {
-                t[j] = tq[j].first;
-                qf[j] = tq[j].second;
-            }
-            t_end = t + tq.size();
-        } else {
-            t_end = std::unique(t, t_end);
-            std::sort(t, t_end, longest_first);
-        }
-        counts[q] = 0;
-        if (freq_sums) freq_sums[q] = 0;
-        if (t == t_end) continue;  // queries.hpp:90-91
-        if (t_end - t == 1 && !freqs_dict) {  // one list: every posting is a result
-            counts[q] = qi->list_len[t[0]];
-            continue;
-        }
-        uint64_t pages = 0;
-        for (const uint32_t* p = t; p != t_end; ++p) pages += list_blocks(*p);
-        if (pages == 0) continue;  // (lists without a block)
-        plan_len[q] = uint32_t(t_end - t);
-        plan_pages[q] = pages;
-        all_pages += pages;
+        for (uint32_t j = 0; j != plan.len[q]; ++j) plan_pages[q] += list_blocks(plan.of(q)[j]);
+        if (plan_pages[q] == 0) plan.len[q] = 0;  // (lists without a block)
+        all_pages += plan_pages[q];
     }
     if (all_pages == 0) return DINT_OK;
     // passes: whole queries, at most `limit` pages each — a query larger than that alone, in a pass sized to it
@@ -89,19 +45,6 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     std::lock_guard<std::mutex> lock(qi->mutex);
     HIP_TRY(hipSetDevice(qi->docs->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    auto ensure_stage = [&](size_t bytes) -> hipError_t {  // (the pinned staging area the AND calls use too)
-        if (qi->h_stage_cap >= bytes) return hipSuccess;
-        if (qi->h_stage) (void)hipHostFree(qi->h_stage);
-        qi->h_stage = nullptr;
-        qi->h_stage_cap = 0;
-        const size_t want = bytes + bytes / 2 + 4096;
-        const hipError_t e = counted_host_malloc(&qi->h_stage, want);
-        if (e != hipSuccess) return e;
-        qi->h_stage_cap = want;
-        qi->d_stage = nullptr;
-        if (hipHostGetDevicePointer(&qi->d_stage, qi->h_stage, 0) != hipSuccess) qi->d_stage = nullptr;
-        return hipSuccess;
-    };
     // the call's counters: counts[n_queries] then freq sums[n_queries], cleared once, added to by every pass
     if (!qi->freq_sums.ensure(2 * n_queries)) return DINT_ERR_HIP;
     unsigned long long* const d_counts = qi->freq_sums.p;
@@ -116,14 +59,14 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         uint64_t n_pages = 0, n_terms = 0;
         for (size_t q = q0; q != q1; ++q) {
             n_pages += plan_pages[q];
-            n_terms += plan_len[q];
+            n_terms += plan.len[q];
         }
         if (n_pages == 0) continue;
         // inputs: page -> block, page -> term record, then per term record {first block, blocks, first page, query, from}
         // (rk: and {the records of its query by term id, its query's terms, q_weight})
         const size_t words = 2 * n_pages + (rk ? 8 : 5) * n_terms;
         if (k != 0) HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area)
-        if (ensure_stage(std::max<size_t>(words * 4, 2 * n_queries * sizeof(unsigned long long))) != hipSuccess) return failed(DINT_ERR_HIP);
+        if (qi->stage(std::max<size_t>(words * 4, 2 * n_queries * sizeof(unsigned long long))) != hipSuccess) return failed(DINT_ERR_HIP);
         uint32_t* const h = static_cast<uint32_t*>(qi->h_stage);
         uint32_t *page_block = h, *page_term = h + n_pages, *term_first = h + 2 * n_pages, *term_blocks = term_first + n_terms,
                  *term_page = term_blocks + n_terms, *term_query = term_page + n_terms, *term_from = term_query + n_terms,
@@ -133,20 +76,20 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         for (size_t q = q0; q != q1; ++q) {
             const uint32_t from = rec;
             if (rk) {  // the query's records by ascending term id: the order its scores are summed in
-                for (uint32_t j = 0; j != plan_len[q]; ++j) term_order[from + j] = from + j;
-                std::sort(term_order + from, term_order + from + plan_len[q],
-                          [&](uint32_t a, uint32_t b) { return plan_of(q)[a - from] < plan_of(q)[b - from]; });
+                for (uint32_t j = 0; j != plan.len[q]; ++j) term_order[from + j] = from + j;
+                std::sort(term_order + from, term_order + from + plan.len[q],
+                          [&](uint32_t a, uint32_t b) { return plan.of(q)[a - from] < plan.of(q)[b - from]; });
             }
-            for (uint32_t j = 0; j != plan_len[q]; ++j, ++rec) {
-                const uint32_t l = plan_of(q)[j];
+            for (uint32_t j = 0; j != plan.len[q]; ++j, ++rec) {
+                const uint32_t l = plan.of(q)[j];
                 term_first[rec] = qi->list_first[l];
                 term_blocks[rec] = uint32_t(list_blocks(l));
                 term_page[rec] = page;
                 term_query[rec] = uint32_t(q);
                 term_from[rec] = from;
                 if (rk) {
-                    term_n[rec] = plan_len[q];
-                    term_weight[rec] = bm25_query_term_weight(plan_qf[query_offsets[q] - t_first + j], qi->list_len[l], rk->num_docs);
+                    term_n[rec] = plan.len[q];
+                    term_weight[rec] = bm25_query_term_weight(plan.qf_of(q)[j], qi->list_len[l], rk->num_docs);
                 }
                 for (uint32_t b = qi->list_first[l]; b != qi->list_first[l + 1]; ++b, ++page) {
                     page_block[page] = b;
@@ -203,12 +146,12 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     }
     HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area: the results go there)
     if (rk) return DINT_OK;            // (ranked: the keys are already on the host)
-    if (ensure_stage(2 * n_queries * sizeof(unsigned long long)) != hipSuccess) return DINT_ERR_HIP;
+    if (qi->stage(2 * n_queries * sizeof(unsigned long long)) != hipSuccess) return DINT_ERR_HIP;
     unsigned long long* const h_res = static_cast<unsigned long long*>(qi->h_stage);
     HIP_TRY(hipMemcpyAsync(h_res, d_counts, (freqs_dict ? 2 : 1) * n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (size_t q = 0; q != n_queries; ++q)
-        if (plan_len[q] != 0) {
+        if (plan.len[q] != 0) {
             counts[q] = h_res[q];
             if (freqs_dict) {
                 freq_sums[q] = h_res[n_queries + q];
@@ -225,7 +168,6 @@ int dint_or_queries(dint_query_index* qi, const uint32_t* terms, const uint64_t*
 
 int dint_or_queries_freqs(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                           size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks_decoded, void* stream) {
-    if (!freqs_dict || !freq_sums) return DINT_ERR_ARG;
-    if (qi && (freqs_dict->device != qi->docs->device || freqs_dict->kind != qi->docs->kind)) return DINT_ERR_ARG;
+    if (!freqs_args_ok(qi, freqs_dict, freq_sums)) return DINT_ERR_ARG;
     return or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums, freq_blocks_decoded, stream);
 }

@@ -3,37 +3,11 @@
 
 void dint_query_index_destroy(dint_query_index* qi) {
     if (!qi) return;
-    if (qi->docs) (void)hipSetDevice(qi->docs->device);
-    for (void* p : {static_cast<void*>(qi->d_blocks), static_cast<void*>(qi->d_block_max),
-                    static_cast<void*>(qi->d_needed), static_cast<void*>(qi->d_rank),
-                    static_cast<void*>(qi->d_touched), static_cast<void*>(qi->d_n_touched)})
+    if (qi->docs) (void)hipSetDevice(qi->docs->device);  // (the workspaces are freed by delete, on this device)
+    for (void* p : {static_cast<void*>(qi->d_blocks), static_cast<void*>(qi->d_block_max), static_cast<void*>(qi->d_needed),
+                    static_cast<void*>(qi->d_rank), static_cast<void*>(qi->d_touched)})
         if (p) (void)hipFree(p);
     if (qi->h_stage) (void)hipHostFree(qi->h_stage);
-    qi->inputs.release();
-    qi->ctrl.release();
-    qi->cand.release();
-    qi->target.release();
-    qi->probe.release();
-    qi->tails.release();
-    qi->fprobe.release();
-    qi->spans.release();
-    qi->bases.release();
-    qi->ends.release();
-    qi->gaps_left.release();
-    qi->freq_sums.release();
-    qi->freq_counts.release();
-    qi->slot_needed.release();
-    qi->slot_rank.release();
-    qi->slot_touched.release();
-    qi->batch_ctrl.release();
-    qi->sub.release();
-    qi->units.release();
-    qi->slot_score.release();
-    qi->slot_kden.release();
-    qi->qweights.release();
-    qi->topk_in.release();
-    qi->topk_keys.release();
-    qi->topk_out.release();
     delete qi;
 }
 
@@ -73,7 +47,6 @@ int dint_query_index_create(const dint_dict* docs_dict, const uint8_t* d_index, 
               hip_ok(counted_malloc(&qi->d_needed, 2 * nb * 4), "counted_malloc(needed)") &&  // (two sets of each: round_tail)
               hip_ok(counted_malloc(&qi->d_rank, 2 * nb * 4), "counted_malloc(rank)") &&
               hip_ok(counted_malloc(&qi->d_touched, 2 * nb * 4), "counted_malloc(touched)") &&
-              hip_ok(counted_malloc(&qi->d_n_touched, 8), "counted_malloc(n_touched)") &&  // {touched blocks, short pages} of a round
               hip_ok(hipMemset(qi->d_needed, 0, 2 * nb * 4), "hipMemset(needed)");
     if (ok && n_blocks)
         ok = hip_ok(hipMemcpy(qi->d_blocks, blocks, n_blocks * sizeof(dint_block_ref), hipMemcpyHostToDevice), "hipMemcpy(blocks)") &&
@@ -214,12 +187,65 @@ static int decode_pages_lean(dint_query_index* qi, const uint32_t* d_ids, const 
     return DINT_OK;
 }
 
-// dint_ranked_and_queries (hip_api_ranked_query.inc): what the freqs pass scores with, and where the selection goes
-// (dint_ranked_or_queries: the same, q_weight unused — the OR pass computes its terms' weights from num_docs)
+// Per query: its distinct terms (queries.hpp:28-31, 49-52, 92) by list length, ascending (AND: the rarest list first) or
+// descending (OR: the longest list probes nothing), equal lengths by term id, and (with_qf) each term's multiplicity
+// beside it (query_freqs, queries.hpp:135-148). One flat copy of the call's terms, every query's part planned in place
+// (a vector per query was an allocation per query: a third of a batch call's host time).
+struct query_plan {
+    const uint64_t* offsets = nullptr;
+    uint64_t first = 0;
+    std::vector<uint32_t> terms, qf;
+    std::vector<uint32_t> len;  // planned terms of query q; 0: none, or nothing to launch (one list, counted on the host)
+    const uint32_t* of(size_t q) const { return terms.data() + (offsets[q] - first); }
+    const uint32_t* qf_of(size_t q) const { return qf.data() + (offsets[q] - first); }
+};
+
+// Checks the offsets and every term before anything is written (DINT_ERR_ARG), then plans the queries: counts[q] and
+// freq_sums[q] (if given) <- 0, and without freqs a query of one list is answered here, counts[q] <- the list's length.
+static int plan_queries(const dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries,
+                        bool longest_first, bool with_qf, bool with_freqs, uint64_t* counts, uint64_t* freq_sums, query_plan& plan) {
+    if (query_offsets[0] != 0 && !terms) return DINT_ERR_ARG;
+    for (size_t q = 0; q != n_queries; ++q)
+        if (query_offsets[q + 1] < query_offsets[q] || (query_offsets[q + 1] > query_offsets[q] && !terms)) return DINT_ERR_ARG;
+    const uint64_t t_first = query_offsets[0], t_all = query_offsets[n_queries] - t_first;
+    for (uint64_t i = 0; i != t_all; ++i)
+        if (terms[t_first + i] >= qi->list_len.size()) return DINT_ERR_ARG;
+    plan.offsets = query_offsets;
+    plan.first = t_first;
+    plan.terms.assign(terms ? terms + t_first : nullptr, terms ? terms + t_first + t_all : nullptr);
+    plan.qf.assign(with_qf ? t_all : 0, 0u);
+    plan.len.assign(n_queries, 0u);
+    const uint32_t* const len = qi->list_len.data();
+    for (size_t q = 0; q != n_queries; ++q) {
+        uint32_t* const t = plan.terms.data() + (query_offsets[q] - t_first);
+        uint32_t* const qf = with_qf ? plan.qf.data() + (query_offsets[q] - t_first) : nullptr;
+        // (equal terms end up side by side in this order: one pass drops them and counts them)
+        std::sort(t, t + (query_offsets[q + 1] - query_offsets[q]), [&](uint32_t a, uint32_t b) {
+            return len[a] != len[b] ? (longest_first ? len[a] > len[b] : len[a] < len[b]) : a < b;
+        });
+        uint32_t n = 0;
+        for (uint64_t i = 0; i != query_offsets[q + 1] - query_offsets[q]; ++i) {
+            if (n != 0 && t[i] == t[n - 1]) {
+                if (qf) qf[n - 1] += 1;
+                continue;
+            }
+            if (qf) qf[n] = 1;
+            t[n++] = t[i];
+        }
+        counts[q] = 0;
+        if (freq_sums) freq_sums[q] = 0;
+        if (n == 1 && !with_freqs)  // one list: every posting is a result (and_query<false> would walk it and count)
+            counts[q] = len[t[0]];
+        else
+            plan.len[q] = n;
+    }
+    return DINT_OK;
+}
+
+// dint_ranked_and_queries (hip_api_ranked_query.inc), dint_ranked_or_queries: what the freqs pass scores with, and where
+// the selection goes
 struct ranked_args {
     const float* norm_lens;    // device, the wand handle's
-    const float* q_weight;     // host: [j * n_queries + q] = q_weight of the j-th term of query q in this path's term order
-    size_t q_weight_len;
     uint32_t k;
     unsigned long long* keys;  // host, n_queries * k: the best keys of every query (ranked_topk)
     uint64_t num_docs;         // the wand handle's
@@ -239,6 +265,11 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split = true,
                             const ranked_args* rk = nullptr);
 
+// the *_queries_freqs entries: a freqs dictionary of the index's device and kind, and somewhere for the sums
+static bool freqs_args_ok(const dint_query_index* qi, const dint_dict* freqs_dict, const uint64_t* freq_sums) {
+    return freqs_dict && freq_sums && (!qi || (freqs_dict->device == qi->docs->device && freqs_dict->kind == qi->docs->kind));
+}
+
 int dint_and_queries(dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries,
                      uint64_t* counts, void* stream) {
     return and_queries_impl(qi, nullptr, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream);
@@ -246,8 +277,7 @@ int dint_and_queries(dint_query_index* qi, const uint32_t* terms, const uint64_t
 
 int dint_and_queries_freqs(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks_decoded, void* stream) {
-    if (!freqs_dict || !freq_sums) return DINT_ERR_ARG;
-    if (qi && (freqs_dict->device != qi->docs->device || freqs_dict->kind != qi->docs->kind)) return DINT_ERR_ARG;
+    if (!freqs_args_ok(qi, freqs_dict, freq_sums)) return DINT_ERR_ARG;
     return and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums, freq_blocks_decoded, stream);
 }
 
@@ -258,56 +288,32 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
     if (n_queries >= 0xFFFFFFFFull) return DINT_ERR_ARG;
-    const size_t n_lists = qi->list_len.size();
-    // per query: distinct terms, rarest list first (queries.hpp:28-31, 49-52) — one flat copy of the log's terms, every
-    // query's part sorted in place (a vector per query was an allocation per query: a third of a batch call's host time)
-    if (query_offsets[0] != 0 && !terms) return DINT_ERR_ARG;
-    for (size_t q = 0; q != n_queries; ++q)
-        if (query_offsets[q + 1] < query_offsets[q] || (query_offsets[q + 1] > query_offsets[q] && !terms)) return DINT_ERR_ARG;
-    const uint64_t t_first = query_offsets[0], t_all = query_offsets[n_queries] - t_first;
-    std::vector<uint32_t> plan_terms(terms ? terms + t_first : nullptr, terms ? terms + t_first + t_all : nullptr);
-    std::vector<uint32_t> plan_len(n_queries, 0);  // terms of query q after that: plan_terms[query_offsets[q] - t_first ..)
-    auto plan_of = [&](size_t q) { return plan_terms.data() + (query_offsets[q] - t_first); };
+    query_plan plan;
+    const int planned = plan_queries(qi, terms, query_offsets, n_queries, false, rk != nullptr, freqs_dict != nullptr, counts, freq_sums, plan);
+    if (planned != DINT_OK) return planned;
     size_t rounds = 0;
     std::vector<uint32_t> h_page_block, h_page_query;
     h_page_block.reserve(n_queries + 64);
     h_page_query.reserve(n_queries + 64);
     for (size_t q = 0; q != n_queries; ++q) {
-        uint32_t* const t = plan_of(q);
-        uint32_t* t_end = t + (query_offsets[q + 1] - query_offsets[q]);
-        for (const uint32_t* p = t; p != t_end; ++p)
-            if (*p >= n_lists) return DINT_ERR_ARG;
-        std::sort(t, t_end);
-        t_end = std::unique(t, t_end);
-        // (by length, equal lengths by term: what a stable sort of the sorted terms gives)
-        std::sort(t, t_end, [&](uint32_t a, uint32_t b) {
-            return qi->list_len[a] != qi->list_len[b] ? qi->list_len[a] < qi->list_len[b] : a < b;
-        });
-        counts[q] = 0;
-        if (freq_sums) freq_sums[q] = 0;
-        if (t == t_end) continue;
-        if (t_end - t == 1 && !freqs_dict) {  // one list: every posting is a result (and_query<false> would walk it and count)
-            counts[q] = qi->list_len[t[0]];
-            continue;
-        }
-        plan_len[q] = uint32_t(t_end - t);
-        rounds = std::max<size_t>(rounds, plan_len[q] - 1);
-        for (uint32_t b = qi->list_first[t[0]]; b != qi->list_first[t[0] + 1]; ++b) {
+        if (plan.len[q] == 0) continue;
+        rounds = std::max<size_t>(rounds, plan.len[q] - 1);
+        const uint32_t rarest = plan.of(q)[0];
+        for (uint32_t b = qi->list_first[rarest]; b != qi->list_first[rarest + 1]; ++b) {
             h_page_block.push_back(b);
             h_page_query.push_back(uint32_t(q));
         }
     }
     const size_t n_pages = h_page_block.size();
     if (n_pages == 0) return DINT_OK;
-    if (rk && (!freqs_dict || rk->q_weight_len < (rounds + 1) * n_queries)) return DINT_ERR_ARG;
     // A MIXED call — queries of a few candidate pages among queries of hundreds: the small ones go through the
     // workgroup-per-query launch (below), the others through the round-per-launch form, as two calls of this function over the
     // sorted plans (a single large query no longer takes a log of small ones onto the slow form with it).
     if (may_split && !freqs_dict && n_queries >= 3 && opt(DINT_OPT_QUERY_BATCH_FUSED) != 0) {
         size_t n_small = 0, n_large = 0;
         for (size_t q = 0; q != n_queries; ++q)
-            if (plan_len[q] != 0) {
-                const uint32_t rarest = plan_of(q)[0];
+            if (plan.len[q] != 0) {
+                const uint32_t rarest = plan.of(q)[0];
                 (qi->list_first[rarest + 1] - qi->list_first[rarest] <= kBatchPages ? n_small : n_large) += 1;
             }
         if (n_small >= 2 && n_large != 0) {
@@ -315,11 +321,11 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
                 std::vector<uint32_t> sub_terms, sub_q;
                 std::vector<uint64_t> sub_offs(1, 0);
                 for (size_t q = 0; q != n_queries; ++q)
-                    if (plan_len[q] != 0) {
-                        const uint32_t rarest = plan_of(q)[0];
+                    if (plan.len[q] != 0) {
+                        const uint32_t rarest = plan.of(q)[0];
                         const bool is_small = qi->list_first[rarest + 1] - qi->list_first[rarest] <= kBatchPages;
                         if (is_small != (part == 0)) continue;
-                        sub_terms.insert(sub_terms.end(), plan_of(q), plan_of(q) + plan_len[q]);
+                        sub_terms.insert(sub_terms.end(), plan.of(q), plan.of(q) + plan.len[q]);
                         sub_offs.push_back(sub_terms.size());
                         sub_q.push_back(uint32_t(q));
                     }
@@ -334,8 +340,8 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     const uint64_t n_slots = uint64_t(n_pages) * kPageSlots;
     std::vector<uint32_t> h_first(std::max<size_t>(1, rounds * n_queries), 0), h_blocks(std::max<size_t>(1, rounds * n_queries), 0);
     for (size_t q = 0; q != n_queries; ++q)
-        for (size_t j = 1; j < plan_len[q]; ++j) {
-            const uint32_t l = plan_of(q)[j];
+        for (size_t j = 1; j < plan.len[q]; ++j) {
+            const uint32_t l = plan.of(q)[j];
             h_first[(j - 1) * n_queries + q] = qi->list_first[l];
             h_blocks[(j - 1) * n_queries + q] = qi->list_first[l + 1] - qi->list_first[l];
         }
@@ -354,18 +360,18 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
             rec.reserve(6 * n_queries);
             size_t page = 0;
             for (size_t q = 0; q != n_queries && small; ++q) {
-                if (plan_len[q] == 0) continue;
-                const uint32_t rarest = plan_of(q)[0];
+                if (plan.len[q] == 0) continue;
+                const uint32_t rarest = plan.of(q)[0];
                 const uint32_t pages_q = qi->list_first[rarest + 1] - qi->list_first[rarest];
-                small = pages_q <= kBatchPages && plan_len[q] >= 2;
+                small = pages_q <= kBatchPages && plan.len[q] >= 2;
                 uint64_t most = 0;
-                for (uint32_t j = 1; j != plan_len[q]; ++j) most = std::max<uint64_t>(most, h_blocks[(j - 1) * n_queries + q]);
-                for (uint32_t j = 0; j != plan_len[q]; ++j) any_full = any_full || qi->list_len[plan_of(q)[j]] >= kBlock;
+                for (uint32_t j = 1; j != plan.len[q]; ++j) most = std::max<uint64_t>(most, h_blocks[(j - 1) * n_queries + q]);
+                for (uint32_t j = 0; j != plan.len[q]; ++j) any_full = any_full || qi->list_len[plan.of(q)[j]] >= kBlock;
                 const uint64_t stretch = std::min<uint64_t>(most, uint64_t(pages_q) * kPageSlots);
-                rec.insert(rec.end(), {uint32_t(q), uint32_t(page), pages_q, plan_len[q], uint32_t(probe_pages), uint32_t(ctrl_at)});
+                rec.insert(rec.end(), {uint32_t(q), uint32_t(page), pages_q, plan.len[q], uint32_t(probe_pages), uint32_t(ctrl_at)});
                 page += pages_q;
                 probe_pages += stretch;
-                ctrl_at += uint64_t(plan_len[q]) * kBatchCtrlWords;
+                ctrl_at += uint64_t(plan.len[q]) * kBatchCtrlWords;
                 small = small && probe_pages < (1ull << 22) && ctrl_at < (1ull << 30);
             }
         }
@@ -379,16 +385,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
             const size_t cnt_words = (2 * n_queries + 3) / 4 * 4;  // the result counters (u64 each): zeros, copied in with the tables
             const size_t up = tab_words + cnt_words + 6 * n_active;
             const size_t stage_bytes = std::max(up * 4, n_queries * sizeof(unsigned long long));
-            if (qi->h_stage_cap < stage_bytes) {
-                if (qi->h_stage) (void)hipHostFree(qi->h_stage);
-                qi->h_stage = nullptr;
-                qi->h_stage_cap = 0;
-                const size_t want = stage_bytes + stage_bytes / 2 + 4096;
-                HIP_TRY(counted_host_malloc(&qi->h_stage, want));
-                qi->h_stage_cap = want;
-                qi->d_stage = nullptr;
-                if (hipHostGetDevicePointer(&qi->d_stage, qi->h_stage, 0) != hipSuccess) qi->d_stage = nullptr;
-            }
+            HIP_TRY(qi->stage(stage_bytes));
             if (qi->d_stage != nullptr) {
                 if (!qi->inputs.ensure(up + 4) || !qi->cand.ensure(n_slots) || !qi->target.ensure(n_slots) ||
                     !qi->probe.ensure(std::max<uint64_t>(1, probe_pages) * kPageSlots) || !qi->gaps_left.ensure(n_pages + probe_pages + 1) ||
@@ -451,7 +448,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
                 qi->slots_dirty = false;
                 const unsigned long long* const h_counts = static_cast<const unsigned long long*>(qi->h_stage);
                 for (size_t q = 0; q != n_queries; ++q)
-                    if (plan_len[q] != 0) counts[q] = h_counts[q];
+                    if (plan.len[q] != 0) counts[q] = h_counts[q];
                 return DINT_OK;
             }
         }
@@ -464,16 +461,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     const size_t step_words = (rounds + 1) * ((sizeof(fused_step) + 7) / 8 * 2);  // (the one-launch form's steps, 8-byte aligned)
     const size_t up_words = in_words + ctrl_words + step_words;
     const size_t stage_bytes = std::max(up_words * 4, n_queries * sizeof(unsigned long long));
-    if (qi->h_stage_cap < stage_bytes) {
-        if (qi->h_stage) (void)hipHostFree(qi->h_stage);
-        qi->h_stage = nullptr;
-        qi->h_stage_cap = 0;
-        const size_t want = stage_bytes + stage_bytes / 2 + 4096;
-        HIP_TRY(counted_host_malloc(&qi->h_stage, want));
-        qi->h_stage_cap = want;
-        qi->d_stage = nullptr;  // the same memory as the kernels see it (the last probe writes the results there)
-        if (hipHostGetDevicePointer(&qi->d_stage, qi->h_stage, 0) != hipSuccess) qi->d_stage = nullptr;
-    }
+    HIP_TRY(qi->stage(stage_bytes));  // (d_stage: the last probe writes the results there)
     if (!qi->inputs.ensure(up_words + 4) || !qi->cand.ensure(n_slots) || !qi->target.ensure(n_slots)) return DINT_ERR_HIP;
     {
         uint32_t* h = static_cast<uint32_t*>(qi->h_stage);
@@ -489,6 +477,41 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     uint32_t* const d_term_blocks = d_term_first + h_first.size();
     uint32_t* const d_ctrl = qi->inputs.p + in_words;
     unsigned long long* const d_counts = reinterpret_cast<unsigned long long*>(d_ctrl + (rounds + 1) * kCtrlWords);
+    // Round r's tail (and_round_tail_kernel, or a one-launch form's step): its probe, the release of its claims, and then
+    // either the next round's block-max search — the two rounds' claim sets alternate — or (last) the count of the
+    // survivors, also written to host_counts unless that is null. Its page decode counts in ctrl = d_ctrl + (r + 1) * kCtrlWords.
+    const size_t nb = std::max<size_t>(1, qi->n_blocks);
+    auto tail_of_round = [&](size_t r, bool last, unsigned long long* host_counts) {
+        const size_t set = r & 1, next_set = set ^ 1;
+        uint32_t* const ctrl = d_ctrl + (r + 1) * kCtrlWords;
+        round_tail t{};
+        t.done = ctrl + 2;  // (not counted in: non-null says "this step has a tail")
+        t.cand = qi->cand.p;
+        t.n_slots = n_slots;
+        t.page_query = d_page_query;
+        t.blocks = qi->d_blocks;
+        t.target = qi->target.p;
+        t.term_blocks = d_term_blocks + r * n_queries;
+        t.rank = qi->d_rank + set * nb;
+        t.probe = qi->probe.p;
+        t.touched = qi->d_touched + set * nb;
+        t.n_touched = ctrl;
+        t.needed = qi->d_needed + set * nb;
+        if (!last) {
+            t.next_first = d_term_first + (r + 1) * n_queries;
+            t.next_blocks = d_term_blocks + (r + 1) * n_queries;
+            t.block_max = qi->d_block_max;
+            t.next_needed = qi->d_needed + next_set * nb;
+            t.next_rank = qi->d_rank + next_set * nb;
+            t.next_touched = qi->d_touched + next_set * nb;
+            t.next_n_touched = d_ctrl + (r + 2) * kCtrlWords;
+        } else {
+            t.counts = d_counts;
+            t.host_counts = host_counts;
+            t.n_queries = uint32_t(n_queries);
+        }
+        return t;
+    };
     // ---- what the host knows of the rounds before anything runs: a bound of the pages each decodes ------------------
     uint64_t round0_blocks = 0;
     if (rounds)
@@ -510,7 +533,6 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
         for (size_t r = 0; r != rounds; ++r) max_pages = std::max(max_pages, round_bound[r]);
         if (!qi->probe.ensure(uint64_t(max_pages) * kPageSlots) || !qi->gaps_left.ensure(max_pages)) return DINT_ERR_HIP;
         fused_step* const h_steps = reinterpret_cast<fused_step*>(static_cast<uint32_t*>(qi->h_stage) + in_words + ctrl_words);
-        const size_t nb = std::max<size_t>(1, qi->n_blocks);
         const bool to_host = !freqs_dict && qi->d_stage != nullptr;
         for (size_t k = 0; k != rounds + 1; ++k) {
             fused_step st{};
@@ -533,40 +555,14 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
                 st.qp.bound = n_pages;
                 st.qp.retire = 1u;
             } else {  // round r: the touched pages, then the tail (the round-per-launch form's round_tail, below)
-                const size_t r = k - 1, set = r & 1, next_set = set ^ 1;
-                uint32_t* const ctrl = d_ctrl + (r + 1) * kCtrlWords;
+                const size_t r = k - 1;
                 st.out = qi->probe.p;
                 st.out_capacity = uint64_t(round_bound[r]) * kPageSlots;
-                st.qp.ids = qi->d_touched + set * nb;
-                st.qp.count = ctrl;
+                st.qp.ids = qi->d_touched + (r & 1) * nb;
+                st.qp.count = d_ctrl + (r + 1) * kCtrlWords;
                 st.qp.bound = round_bound[r];
                 st.qp.retire = 0u;
-                round_tail& t = st.rt;
-                t.done = ctrl + 2;  // (not counted in: non-null says "this step has a tail")
-                t.cand = qi->cand.p;
-                t.n_slots = n_slots;
-                t.page_query = d_page_query;
-                t.blocks = qi->d_blocks;
-                t.target = qi->target.p;
-                t.term_blocks = d_term_blocks + r * n_queries;
-                t.rank = qi->d_rank + set * nb;
-                t.probe = qi->probe.p;
-                t.touched = qi->d_touched + set * nb;
-                t.n_touched = ctrl;
-                t.needed = qi->d_needed + set * nb;
-                if (r + 1 != rounds) {
-                    t.next_first = d_term_first + (r + 1) * n_queries;
-                    t.next_blocks = d_term_blocks + (r + 1) * n_queries;
-                    t.block_max = qi->d_block_max;
-                    t.next_needed = qi->d_needed + next_set * nb;
-                    t.next_rank = qi->d_rank + next_set * nb;
-                    t.next_touched = qi->d_touched + next_set * nb;
-                    t.next_n_touched = d_ctrl + (r + 2) * kCtrlWords;
-                } else {
-                    t.counts = d_counts;
-                    t.host_counts = to_host ? static_cast<unsigned long long*>(qi->d_stage) : nullptr;
-                    t.n_queries = uint32_t(n_queries);
-                }
+                st.rt = tail_of_round(r, r + 1 == rounds, to_host ? static_cast<unsigned long long*>(qi->d_stage) : nullptr);
             }
             std::memcpy(h_steps + k, &st, sizeof st);
         }
@@ -604,7 +600,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
         // only (most of a query log's) runs without the 88 KB LDS image — nothing reads it
         bool any_full = false;
         for (size_t q = 0; q != n_queries; ++q)
-            for (uint32_t j = 0; j != plan_len[q]; ++j) any_full = any_full || qi->list_len[plan_of(q)[j]] >= kBlock;
+            for (uint32_t j = 0; j != plan.len[q]; ++j) any_full = any_full || qi->list_len[plan.of(q)[j]] >= kBlock;
         if (!any_full) a.dict.hot_words = 0;
         const size_t lds_bytes = (size_t(a.dict.hot_words) + kClassTableWords + kWavesPerBlock * kScratchWords) * 4;
         fused_inputs bring{};
@@ -671,41 +667,15 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
         counted = true;  // (the launch above was the whole query)
         results_to_host = results_to_host && qi->d_stage != nullptr;
     }
+    unsigned long long* const host_counts = results_to_host ? static_cast<unsigned long long*>(qi->d_stage) : nullptr;
     if (tail_form && !fused_ok) {
-        const size_t nb = std::max<size_t>(1, qi->n_blocks);
         for (size_t r = 0; r != rounds; ++r) {
-            const size_t set = r & 1, next_set = set ^ 1;
             uint32_t* const ctrl = d_ctrl + (r + 1) * kCtrlWords;
             if (!qi->probe.ensure(uint64_t(round_bound[r]) * kPageSlots)) {
                 (void)hipStreamSynchronize(s);
                 return DINT_ERR_HIP;
             }
-            round_tail t{};
-            t.done = ctrl + 2;
-            t.cand = qi->cand.p;
-            t.n_slots = n_slots;
-            t.page_query = d_page_query;
-            t.blocks = qi->d_blocks;
-            t.target = qi->target.p;
-            t.term_blocks = d_term_blocks + r * n_queries;
-            t.rank = qi->d_rank + set * nb;
-            t.probe = qi->probe.p;
-            t.touched = qi->d_touched + set * nb;
-            t.n_touched = ctrl;
-            t.needed = qi->d_needed + set * nb;
-            if (r + 1 != rounds) {
-                t.next_first = d_term_first + (r + 1) * n_queries;
-                t.next_blocks = d_term_blocks + (r + 1) * n_queries;
-                t.block_max = qi->d_block_max;
-                t.next_needed = qi->d_needed + next_set * nb;
-                t.next_rank = qi->d_rank + next_set * nb;
-                t.next_touched = qi->d_touched + next_set * nb;
-                t.next_n_touched = d_ctrl + (r + 2) * kCtrlWords;
-            } else {
-                t.counts = d_counts;
-                t.host_counts = results_to_host ? static_cast<unsigned long long*>(qi->d_stage) : nullptr;
-                t.n_queries = uint32_t(n_queries);
-            }
+            const round_tail t = tail_of_round(r, r + 1 == rounds, host_counts);
             st = decode_pages_lean(qi, t.touched, ctrl, round_bound[r], qi->probe.p, ctrl, 0u, s, nullptr, &t);
             if (st != DINT_OK) {
                 (void)hipStreamSynchronize(s);
@@ -718,8 +688,6 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     // its claims, the NEXT round's block-max search) — the two rounds' claim sets alternate, as in the tail form. A round
     // in which no query has a term ends the call's rounds (a query's terms are consecutive rounds).
     for (size_t r = 0; r != rounds && !tail_form && !fused_ok; ++r) {
-        const size_t nb = std::max<size_t>(1, qi->n_blocks);
-        const size_t set = r & 1, next_set = set ^ 1;
         const uint32_t* first = d_term_first + r * n_queries;
         const uint32_t* nblk = d_term_blocks + r * n_queries;
         uint32_t* const ctrl = d_ctrl + (r + 1) * kCtrlWords;
@@ -745,39 +713,14 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
             return DINT_ERR_HIP;
         }
         if (!nothing_touched) {
-            st = decode_pages_counted(qi, qi->d_touched + set * nb, d_count, bound, qi->probe.p, ctrl, 0u, s);
+            st = decode_pages_counted(qi, qi->d_touched + (r & 1) * nb, d_count, bound, qi->probe.p, ctrl, 0u, s);
             if (st != DINT_OK) {
                 (void)hipStreamSynchronize(s);
                 return st;
             }
         }
-        round_tail t{};
-        t.done = ctrl + 2;
-        t.cand = qi->cand.p;
-        t.n_slots = n_slots;
-        t.page_query = d_page_query;
-        t.blocks = qi->d_blocks;
-        t.target = qi->target.p;
-        t.term_blocks = nblk;
-        t.rank = qi->d_rank + set * nb;
-        t.probe = qi->probe.p;
-        t.touched = qi->d_touched + set * nb;
-        t.n_touched = ctrl;
-        t.needed = qi->d_needed + set * nb;
-        if (r != last_round) {
-            t.next_first = d_term_first + (r + 1) * n_queries;
-            t.next_blocks = d_term_blocks + (r + 1) * n_queries;
-            t.block_max = qi->d_block_max;
-            t.next_needed = qi->d_needed + next_set * nb;
-            t.next_rank = qi->d_rank + next_set * nb;
-            t.next_touched = qi->d_touched + next_set * nb;
-            t.next_n_touched = d_ctrl + (r + 2) * kCtrlWords;
-        } else {
-            t.counts = d_counts;
-            t.host_counts = results_to_host ? static_cast<unsigned long long*>(qi->d_stage) : nullptr;
-            t.n_queries = uint32_t(n_queries);
-            counted = true;
-        }
+        const round_tail t = tail_of_round(r, r == last_round, host_counts);
+        counted = counted || r == last_round;
         hipLaunchKernelGGL(and_round_tail_kernel, dim3(slot_grid), dim3(tb), 0, s, t);
     }
     results_to_host = results_to_host && counted;
@@ -789,6 +732,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     // every match reads its freq at the position of its docID.
     std::vector<unsigned long long> h_sums;
     std::vector<uint32_t> h_freq_counts;
+    std::vector<float> h_qweights;
     if (freqs_dict) {
         if (!qi->freq_sums.ensure(n_queries)) return DINT_ERR_HIP;
         HIP_TRY(hipMemsetAsync(qi->freq_sums.p, 0, n_queries * sizeof(unsigned long long), s));
@@ -798,11 +742,15 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
         // as in the rounds above. The counts themselves travel to the host with the results.)
         if (!qi->freq_counts.ensure(rounds + 1)) return DINT_ERR_HIP;
         HIP_TRY(hipMemsetAsync(qi->freq_counts.p, 0, (rounds + 1) * 4, s));
-        if (rk) {  // ranked_and: a score per candidate slot, from 0.0f; the q_weights of every term of every query
-            if (!qi->slot_score.ensure(n_slots) || !qi->slot_kden.ensure(n_slots) || !qi->qweights.ensure(rk->q_weight_len))
+        if (rk) {  // ranked_and: a score per candidate slot, from 0.0f; [j * n_queries + q] = q_weight of query q's j-th term
+            h_qweights.assign((rounds + 1) * n_queries, 0.0f);
+            for (size_t q = 0; q != n_queries; ++q)
+                for (uint32_t j = 0; j != plan.len[q]; ++j)
+                    h_qweights[j * n_queries + q] = bm25_query_term_weight(plan.qf_of(q)[j], qi->list_len[plan.of(q)[j]], rk->num_docs);
+            if (!qi->slot_score.ensure(n_slots) || !qi->slot_kden.ensure(n_slots) || !qi->qweights.ensure(h_qweights.size()))
                 return DINT_ERR_HIP;
             HIP_TRY(hipMemsetAsync(qi->slot_score.p, 0, n_slots * sizeof(float), s));
-            HIP_TRY(hipMemcpyAsync(qi->qweights.p, rk->q_weight, rk->q_weight_len * sizeof(float), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(qi->qweights.p, h_qweights.data(), h_qweights.size() * sizeof(float), hipMemcpyHostToDevice, s));
         }
         for (size_t r = 0; r != rounds + 1; ++r) {  // r = 0: the rarest term; r >= 1: the term of round r - 1
             const uint32_t* first = r ? d_term_first + (r - 1) * n_queries : nullptr;
@@ -868,7 +816,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     HIP_TRY(hipStreamSynchronize(s));
     qi->claims_dirty = false;
     for (size_t q = 0; q != n_queries; ++q)
-        if (plan_len[q] != 0) counts[q] = h_counts[q];
+        if (plan.len[q] != 0) counts[q] = h_counts[q];
     if (freqs_dict) {
         for (size_t q = 0; q != n_queries; ++q) freq_sums[q] = h_sums[q];
         if (freq_blocks)

@@ -9,13 +9,7 @@
 int dint_ranked_or_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
                            const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts, float* scores,
                            uint32_t* docids, void* stream) {
-    if (!qi || !freqs_dict || !wd || k == 0 || k > kRankedMaxK) return DINT_ERR_ARG;
-    if (n_queries && (!query_offsets || !counts || !scores)) return DINT_ERR_ARG;
-    if (freqs_dict->device != qi->docs->device || freqs_dict->kind != qi->docs->kind || wd->device != qi->docs->device)
-        return DINT_ERR_ARG;
-    if (qi->doc_bound > wd->num_docs) return DINT_ERR_ARG;  // (norm_lens[docid] must exist for every docID of the index)
-    if (n_queries == 0) return DINT_OK;
-    if (n_queries >= 0xFFFFFFFFull || uint64_t(n_queries) * k > (uint64_t(1) << 32)) return DINT_ERR_ARG;
+    if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores)) return DINT_ERR_ARG;
     std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
     ranked_args rk{};
     rk.norm_lens = wd->d_norm_lens;
@@ -30,14 +24,7 @@ int dint_ranked_or_queries(dint_query_index* qi, const dint_dict* freqs_dict, co
         uint64_t c = 0;
         while (c != k && keys[q * k + c] != 0) ++c;
         counts[q] = c;
-        for (uint32_t i = 0; i != k; ++i) {
-            const unsigned long long key = keys[q * k + i];
-            const uint32_t bits = uint32_t(key >> 32);
-            float sc = 0.0f;
-            std::memcpy(&sc, &bits, 4);
-            scores[q * k + i] = key ? sc : 0.0f;
-            if (docids) docids[q * k + i] = key ? 0xFFFFFFFFu - uint32_t(key) : 0xFFFFFFFFu;
-        }
     }
+    unpack_keys(keys, n_queries, k, counts, scores, docids);
     return DINT_OK;
 }

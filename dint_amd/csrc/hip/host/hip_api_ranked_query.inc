@@ -113,56 +113,21 @@ static int ranked_topk(dint_query_index* qi, const ranked_args& rk, const std::v
     return DINT_OK;
 }
 
-int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
-                            const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts, float* scores,
-                            uint32_t* docids, void* stream) {
-    if (!qi || !freqs_dict || !wd || k == 0 || k > kRankedMaxK) return DINT_ERR_ARG;
-    if (n_queries && (!query_offsets || !counts || !scores)) return DINT_ERR_ARG;
-    if (freqs_dict->device != qi->docs->device || freqs_dict->kind != qi->docs->kind || wd->device != qi->docs->device)
-        return DINT_ERR_ARG;
-    if (qi->doc_bound > wd->num_docs) return DINT_ERR_ARG;  // (norm_lens[docid] must exist for every docID of the index)
-    if (n_queries == 0) return DINT_OK;
-    if (n_queries >= 0xFFFFFFFFull || uint64_t(n_queries) * k > (uint64_t(1) << 32)) return DINT_ERR_ARG;
-    if (query_offsets[0] != 0 && !terms) return DINT_ERR_ARG;
+// Both ranked entries' own checks (null handles and a bad k are refused before anything is dereferenced)
+static bool ranked_args_ok(const dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                           const uint64_t* query_offsets, size_t n_queries, const uint64_t* counts, const float* scores) {
+    if (!qi || !freqs_dict || !wd || k == 0 || k > kRankedMaxK) return false;
+    if (n_queries && (!query_offsets || !counts || !scores)) return false;
+    if (freqs_dict->device != qi->docs->device || freqs_dict->kind != qi->docs->kind || wd->device != qi->docs->device) return false;
+    if (qi->doc_bound > wd->num_docs) return false;  // (norm_lens[docid] must exist for every docID of the index)
+    return n_queries < 0xFFFFFFFFull && uint64_t(n_queries) * k <= (uint64_t(1) << 32);
+}
+
+// ranked_topk's keys (score bits, then the inverted docID; sorted descending) -> the first counts[q] scores and docIDs of
+// every query, 0.0f and 0xFFFFFFFF past them
+static void unpack_keys(const std::vector<unsigned long long>& keys, size_t n_queries, uint32_t k, const uint64_t* counts,
+                        float* scores, uint32_t* docids) {
     for (size_t q = 0; q != n_queries; ++q)
-        if (query_offsets[q + 1] < query_offsets[q] || (query_offsets[q + 1] > query_offsets[q] && !terms)) return DINT_ERR_ARG;
-    const size_t n_lists = qi->list_len.size();
-    const uint64_t t_first = query_offsets[0], t_all = query_offsets[n_queries] - t_first;
-    for (uint64_t i = 0; i != t_all; ++i)
-        if (terms[t_first + i] >= n_lists) return DINT_ERR_ARG;
-    // per query: distinct terms with their multiplicity (query_freqs, queries.hpp:135-148) in and_queries_impl's order —
-    // by list length, equal lengths by term — and q_weight = bm25::query_term_weight(qf, df, num_docs) in that order
-    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> tq(n_queries);  // {term, qf}
-    size_t most_terms = 1;
-    for (size_t q = 0; q != n_queries; ++q) {
-        std::vector<uint32_t> t(terms + query_offsets[q], terms + query_offsets[q + 1]);
-        std::sort(t.begin(), t.end());
-        for (size_t i = 0; i != t.size(); ++i) {
-            if (i == 0 || t[i] != t[i - 1]) tq[q].push_back({t[i], 1u});
-            else tq[q].back().second += 1;
-        }
-        std::sort(tq[q].begin(), tq[q].end(), [&](std::pair<uint32_t, uint32_t> a, std::pair<uint32_t, uint32_t> b) {
-            return qi->list_len[a.first] != qi->list_len[b.first] ? qi->list_len[a.first] < qi->list_len[b.first] : a.first < b.first;
-        });
-        most_terms = std::max(most_terms, tq[q].size());
-    }
-    std::vector<float> q_weight(most_terms * n_queries, 0.0f);
-    for (size_t q = 0; q != n_queries; ++q)
-        for (size_t j = 0; j != tq[q].size(); ++j)
-            q_weight[j * n_queries + q] = bm25_query_term_weight(tq[q][j].second, qi->list_len[tq[q][j].first], wd->num_docs);
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    std::vector<uint64_t> freq_sums(n_queries, 0);
-    ranked_args rk{};
-    rk.norm_lens = wd->d_norm_lens;
-    rk.q_weight = q_weight.data();
-    rk.q_weight_len = q_weight.size();
-    rk.k = k;
-    rk.keys = keys.data();
-    rk.num_docs = wd->num_docs;
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk);
-    if (st != DINT_OK) return st;
-    for (size_t q = 0; q != n_queries; ++q) {
-        counts[q] = std::min<uint64_t>(counts[q], k);
         for (uint32_t i = 0; i != k; ++i) {
             const unsigned long long key = i < counts[q] ? keys[q * k + i] : 0ull;
             const uint32_t bits = uint32_t(key >> 32);
@@ -171,6 +136,23 @@ int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, c
             scores[q * k + i] = key ? sc : 0.0f;
             if (docids) docids[q * k + i] = key ? 0xFFFFFFFFu - uint32_t(key) : 0xFFFFFFFFu;
         }
-    }
+}
+
+int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                            const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts, float* scores,
+                            uint32_t* docids, void* stream) {
+    if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores)) return DINT_ERR_ARG;
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
+    std::vector<uint64_t> freq_sums(n_queries, 0);
+    ranked_args rk{};
+    rk.norm_lens = wd->d_norm_lens;
+    rk.k = k;
+    rk.keys = keys.data();
+    rk.num_docs = wd->num_docs;
+    // (and_queries_impl checks the offsets and the terms before anything is launched)
+    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk);
+    if (st != DINT_OK) return st;
+    for (size_t q = 0; q != n_queries; ++q) counts[q] = std::min<uint64_t>(counts[q], k);
+    unpack_keys(keys, n_queries, k, counts, scores, docids);
     return DINT_OK;
 }

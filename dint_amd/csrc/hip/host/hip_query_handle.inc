@@ -1,9 +1,15 @@
 // Part of dint_hip.hip (one translation unit; included from there, in order): grow-only device workspaces; the query index handle.
 namespace {
 template <class T>
-struct device_buffer {  // grow-only workspace
+struct device_buffer {  // grow-only workspace, freed with its owner (on the current device: the owner sets it)
     T* p = nullptr;
     size_t cap = 0;
+    device_buffer() = default;
+    device_buffer(const device_buffer&) = delete;
+    device_buffer& operator=(const device_buffer&) = delete;
+    ~device_buffer() {
+        if (p) (void)hipFree(p);
+    }
     bool ensure(size_t need) {
         if (need <= cap) return true;
         if (p) (void)hipFree(p);
@@ -13,11 +19,6 @@ struct device_buffer {  // grow-only workspace
         if (!hip_ok(counted_malloc(&p, want * sizeof(T)), "counted_malloc(workspace)")) return false;
         cap = want;
         return true;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
     }
 };
 }  // namespace
@@ -34,14 +35,13 @@ struct dint_query_index {
     uint32_t* d_needed = nullptr;   // n_blocks, zero between rounds
     uint32_t* d_rank = nullptr;     // n_blocks
     uint32_t* d_touched = nullptr;  // n_blocks
-    uint32_t* d_n_touched = nullptr;  // two counters: {blocks a round touched, short pages of a page decode}
     bool claims_dirty = false;        // d_needed may hold claim flags of a call that did not run to its end
     // one call = one host-to-device copy (everything the call's kernels read from the host, staged in pinned memory),
     // one clear (every counter the call's launches count in), the launches, one copy back
     void* h_stage = nullptr;
     void* d_stage = nullptr;
     size_t h_stage_cap = 0;
-    device_buffer<uint32_t> inputs, ctrl;
+    device_buffer<uint32_t> inputs;
     device_buffer<uint32_t> cand, target, probe, fprobe, tails, spans, bases;
     device_buffer<dint_block_ref> sub;
     device_buffer<dint_unit> units;
@@ -61,5 +61,21 @@ struct dint_query_index {
     device_buffer<uint32_t> topk_in;
     device_buffer<unsigned long long> topk_keys, topk_out;
     std::mutex mutex;
+
+    // h_stage of at least `bytes` (grown by half again), d_stage the same memory as the kernels see it (null where it
+    // cannot be mapped)
+    hipError_t stage(size_t bytes) {
+        if (h_stage_cap >= bytes) return hipSuccess;
+        if (h_stage) (void)hipHostFree(h_stage);
+        h_stage = nullptr;
+        h_stage_cap = 0;
+        const size_t want = bytes + bytes / 2 + 4096;
+        const hipError_t e = counted_host_malloc(&h_stage, want);
+        if (e != hipSuccess) return e;
+        h_stage_cap = want;
+        d_stage = nullptr;
+        if (hipHostGetDevicePointer(&d_stage, h_stage, 0) != hipSuccess) d_stage = nullptr;
+        return hipSuccess;
+    }
 };
 

@@ -522,19 +522,18 @@ class QueryIndex:
 
     __del__ = close
 
-    def and_queries(self, queries) -> np.ndarray:
-        """queries: sequence of term-id sequences -> u64 result counts, one per query."""
+    def _stream(self) -> int:
+        """The current stream of this index's device."""
         import torch
 
-        lens = np.fromiter((len(q) for q in queries), dtype=np.uint64, count=len(queries))
-        offs = np.zeros(len(queries) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offs[1:])
-        terms = np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.uint32) for q in queries])
-                                     if len(queries) else np.zeros(0, np.uint32), dtype=np.uint32)
+        return torch.cuda.current_stream(torch.device("cuda", self.docs_dict.device)).cuda_stream
+
+    def and_queries(self, queries) -> np.ndarray:
+        """queries: sequence of term-id sequences -> u64 result counts, one per query."""
+        terms, offs = _pack_queries(queries)
         counts = np.zeros(len(queries), dtype=np.uint64)
-        stream = torch.cuda.current_stream(torch.device("cuda", self.docs_dict.device)).cuda_stream
-        _check(_lib.dint_and_queries(self._h, terms.ctypes.data, offs.ctypes.data, len(queries),
-                                     counts.ctypes.data, stream), "dint_and_queries")
+        _check(_lib.dint_and_queries(self._h, terms.ctypes.data, offs.ctypes.data, len(queries), counts.ctypes.data,
+                                     self._stream()), "dint_and_queries")
         return counts
 
     def and_queries_packed(self, terms: np.ndarray, offsets: np.ndarray, counts: np.ndarray, stream: int = 0) -> None:
@@ -544,18 +543,22 @@ class QueryIndex:
                "dint_and_queries")
 
     def and_queries_with_freqs(self, freqs_dict: "Dictionary", queries):
-        """`and_query<true>` for a batch -> (counts, sums of the freqs read at the matches, freqs blocks decoded)."""
-        return and_queries_with_freqs(self, freqs_dict, queries)
+        """`and_query<true>` for a batch -> (counts u64[], sums of the freqs read at the matches u64[], freqs blocks decoded)."""
+        terms, offs = _pack_queries(queries)
+        counts = np.zeros(len(queries), dtype=np.uint64)
+        sums = np.zeros(len(queries), dtype=np.uint64)
+        nblocks = C.c_uint64()
+        _check(_lib.dint_and_queries_freqs(self._h, freqs_dict._h, terms.ctypes.data, offs.ctypes.data, len(queries),
+                                           counts.ctypes.data, sums.ctypes.data, C.byref(nblocks), self._stream()),
+               "dint_and_queries_freqs")
+        return counts, sums, nblocks.value
 
     def or_queries(self, queries) -> np.ndarray:
         """or_query<false> (include/ds2i/queries.hpp:86-130) for a batch: queries -> u64 counts of the union, one per query."""
-        import torch
-
         terms, offs = _pack_queries(queries)
         counts = np.zeros(len(queries), dtype=np.uint64)
-        stream = torch.cuda.current_stream(torch.device("cuda", self.docs_dict.device)).cuda_stream
-        _check(_lib.dint_or_queries(self._h, terms.ctypes.data, offs.ctypes.data, len(queries), counts.ctypes.data, stream),
-               "dint_or_queries")
+        _check(_lib.dint_or_queries(self._h, terms.ctypes.data, offs.ctypes.data, len(queries), counts.ctypes.data,
+                                    self._stream()), "dint_or_queries")
         return counts
 
     def or_queries_packed(self, terms: np.ndarray, offsets: np.ndarray, counts: np.ndarray, stream: int = 0) -> None:
@@ -565,51 +568,36 @@ class QueryIndex:
 
     def or_queries_with_freqs(self, freqs_dict: "Dictionary", queries):
         """`or_query<true>` for a batch -> (counts, sums of the freqs of every posting of every distinct term, freqs blocks decoded)."""
-        import torch
-
         terms, offs = _pack_queries(queries)
         counts = np.zeros(len(queries), dtype=np.uint64)
         sums = np.zeros(len(queries), dtype=np.uint64)
         nblocks = C.c_uint64()
-        stream = torch.cuda.current_stream(torch.device("cuda", self.docs_dict.device)).cuda_stream
         _check(_lib.dint_or_queries_freqs(self._h, freqs_dict._h, terms.ctypes.data, offs.ctypes.data, len(queries),
-                                          counts.ctypes.data, sums.ctypes.data, C.byref(nblocks), stream), "dint_or_queries_freqs")
+                                          counts.ctypes.data, sums.ctypes.data, C.byref(nblocks), self._stream()),
+               "dint_or_queries_freqs")
         return counts, sums, nblocks.value
 
+    def _ranked(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, k: int):
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        counts = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data, n,
+                                 counts.ctypes.data, scores.ctypes.data, docids.ctypes.data, self._stream()), fn)
+        return counts, scores, docids
 
     def ranked_and_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10):
         """ranked_and_query (include/ds2i/queries.hpp:309-385) for a batch: BM25 top-k of the intersection ->
         (counts u64[n] = min(k, matches), scores f32[n, k] descending, docids u32[n, k]; equal scores by ascending docID,
         0.0 / 0xFFFFFFFF past a query's count)."""
-        import torch
-
-        terms, offs = _pack_queries(queries)
-        n = len(queries)
-        counts = np.zeros(n, dtype=np.uint64)
-        scores = np.zeros((n, k), dtype=np.float32)
-        docids = np.zeros((n, k), dtype=np.uint32)
-        stream = torch.cuda.current_stream(torch.device("cuda", self.docs_dict.device)).cuda_stream
-        _check(_lib.dint_ranked_and_queries(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data, n,
-                                            counts.ctypes.data, scores.ctypes.data, docids.ctypes.data, stream),
-               "dint_ranked_and_queries")
-        return counts, scores, docids
+        return self._ranked("dint_ranked_and_queries", freqs_dict, wand, queries, k)
 
     def ranked_or_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10):
         """ranked_or_query (include/ds2i/queries.hpp:387-457) for a batch: BM25 top-k of the union, each document's score
         summed over the query's terms in ascending term id -> (counts u64[n] = min(k, |union|), scores f32[n, k]
         descending, docids u32[n, k]; equal scores by ascending docID, 0.0 / 0xFFFFFFFF past a query's count)."""
-        import torch
-
-        terms, offs = _pack_queries(queries)
-        n = len(queries)
-        counts = np.zeros(n, dtype=np.uint64)
-        scores = np.zeros((n, k), dtype=np.float32)
-        docids = np.zeros((n, k), dtype=np.uint32)
-        stream = torch.cuda.current_stream(torch.device("cuda", self.docs_dict.device)).cuda_stream
-        _check(_lib.dint_ranked_or_queries(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data, n,
-                                           counts.ctypes.data, scores.ctypes.data, docids.ctypes.data, stream),
-               "dint_ranked_or_queries")
-        return counts, scores, docids
+        return self._ranked("dint_ranked_or_queries", freqs_dict, wand, queries, k)
 
 
 class WandData:
@@ -640,20 +628,6 @@ def _pack_queries(queries):
     terms = np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.uint32) for q in queries])
                                  if len(queries) else np.zeros(0, np.uint32), dtype=np.uint32)
     return terms, offs
-
-
-def and_queries_with_freqs(qi: "QueryIndex", freqs_dict: "Dictionary", queries):
-    """and_query<true> for a batch: -> (counts u64[], freq sums u64[], freqs blocks decoded)."""
-    import torch
-
-    terms, offs = _pack_queries(queries)
-    counts = np.zeros(len(queries), dtype=np.uint64)
-    sums = np.zeros(len(queries), dtype=np.uint64)
-    nblocks = C.c_uint64()
-    stream = torch.cuda.current_stream(torch.device("cuda", qi.docs_dict.device)).cuda_stream
-    _check(_lib.dint_and_queries_freqs(qi._h, freqs_dict._h, terms.ctypes.data, offs.ctypes.data, len(queries),
-                                       counts.ctypes.data, sums.ctypes.data, C.byref(nblocks), stream), "dint_and_queries_freqs")
-    return counts, sums, nblocks.value
 
 
 NGRAM_DTYPE = np.dtype([("pos", "<u8"), ("freq", "<u4"), ("len", "u1"), ("ctx", "u1"), ("pad", "<u2")])  # dint_ngram
