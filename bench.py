@@ -18,6 +18,11 @@ the driver puts the pair; what the process's FIRST
 allocation reaches is reported next to it (value_first_allocation,
 roofline.frac_first_allocation). --placement-trials 1: the first allocation only.
 
+A plain run does what the headline needs: set-up (placement and the upload of the expected gaps included), warm-up, the timed
+steps, --dump-outputs, the bit-exact check and the line. --full adds what is measured beside it: the CPU baseline
+(cpu_baseline), the stream statistics of the first piece (config.ints_per_codeword, ...), the box probe (roofline.box_probe)
+and the profiler's traffic file (roofline.traffic); without it those are null or absent.
+
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").
 """
 from __future__ import annotations
@@ -30,6 +35,7 @@ import subprocess
 import sys
 import time
 
+T_START = time.time()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -109,10 +115,13 @@ def parse_args(argv=None):
     ap.add_argument("--dict-sample", type=float, default=2.0e7,
                     help="postings the DSF dictionary statistics are collected from")
     ap.add_argument("--seed", type=int, default=12345)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline (--cpu-seconds), the stream statistics, "
+                         "the box probe and the traffic file (--traffic-file)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="decode time budget of each leg of the CPU baseline sample (0 = skip)")
+                    help="with --full: decode time budget of each leg of the CPU baseline sample (0 = skip)")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
-                    help="JSON written by tools/pmc_traffic.py from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of THIS command "
+                    help="with --full: JSON written by tools/pmc_traffic.py from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of THIS command "
                          "(HBM counters cannot be read from inside the run). Default: the round's committed measurement, attached only "
                          "if it was taken for the same type, the same integers per launch AND the same build of libdint_hip.so "
                          "(its lib_sha16 = this process's library); otherwise roofline.traffic is null and the note says why")
@@ -177,7 +186,7 @@ def dump_outputs(out_dir, out_dev, end_dev):
 
 def log(rank, *a):
     if rank == 0:
-        print("[bench]", *a, file=sys.stderr, flush=True)
+        print(f"[bench {time.time() - T_START:5.1f}s]", *a, file=sys.stderr, flush=True)
 
 
 def launch_ranks(args) -> int:
@@ -308,6 +317,13 @@ def cpu_quota():
         return None
 
 
+def usable_cpus() -> int:
+    """CPUs this process can keep busy: its affinity mask, cut down to the container's CPU-time quota (cgroup cpu.max) —
+    more runnable threads than that are throttled, and a pool sized by the mask alone waits for the throttle."""
+    affinity, quota = len(os.sched_getaffinity(0)), cpu_quota()
+    return affinity if quota is None else max(1, min(affinity, int(quota)))
+
+
 def cpu_baseline(kind, dict_file, enc, list_byte_starts, seconds):
     """The oracle's restatement of the reference decode, timed on this host: (i) one thread, per-list timing
     summed exactly like vroom_env/decode.cpp:139-150; (ii) every core, the lists statically partitioned by
@@ -328,7 +344,7 @@ def cpu_baseline(kind, dict_file, enc, list_byte_starts, seconds):
     # "every core" = every CPU this process may use: its affinity mask, cut down to the container's CPU-time quota
     # (cgroup cpu.max) — more runnable threads than that are throttled, which measures the throttle, not the host
     affinity, quota = len(os.sched_getaffinity(0)), cpu_quota()
-    threads = affinity if quota is None else max(1, min(affinity, int(quota)))
+    threads = usable_cpus()
     phys = min(physical_cores(), threads)
     # thread k takes the lists that begin in [k, k + 1) / threads of the stream's bytes (a thread may get none): one
     # pthread each inside liboracle, a persistent decode buffer per thread, all looping until `seconds` have passed
@@ -411,8 +427,10 @@ def main():
                 os.environ["MASTER_PORT"] = str(sk.getsockname()[1])
         dist.init_process_group(backend, rank=rank, world_size=world, **({"device_id": dev} if backend == "nccl" else {}))
 
+    log(rank, f"{'stub' if stub else 'device'} layer on {dev}")
     kind = host.KIND_BY_TYPE[args.type]
-    threads = max(1, host.default_threads() // world)
+    # the set-up's generator and encoder threads (their output does not depend on the count): the ranks share the usable CPUs
+    threads = max(1, usable_cpus() // world)
 
     # ---- set-up (untimed): collection shard, dictionary, encode, upload ----------
     t0 = time.time()
@@ -666,6 +684,7 @@ def main():
         step()
     sync_all()
     elapsed = time.perf_counter() - t_start
+    log(rank, f"timed region: {args.steps} steps in {elapsed:.3f}s")
     # per-launch kernel time of the timed launches themselves: the event pairs the library recorded around them
     kernel_ms = np.asarray(d.recent_kernel_ms(min(args.steps, 64)), dtype=np.float64)
     # the clock the last timed launch actually ran at (its first wave's cycle count over its duration)
@@ -705,10 +724,10 @@ def main():
         if not bit_exact:
             raise SystemExit("FATAL: decoded integers differ from the encoder's input")
 
-    # ---- the box: what plain fill and copy kernels reach on the same output buffer, after the timed region (boxes of
-    # one pool differ by 15 % in the decode kernel's time at equal clocks: this says whether their HBM does too) -----
+    # ---- --full: the box, what plain fill and copy kernels reach on the same output buffer, after the timed region (boxes
+    # of one pool differ by 15 % in the decode kernel's time at equal clocks: this says whether their HBM does too) ----
     box_probe = None
-    if dev.type == "cuda" and rank == 0:
+    if args.full and dev.type == "cuda" and rank == 0:
         half = (n_ints // 2) & ~1023
         probe = {}
         for name, fn, nbytes in (("fill_gbps", lambda: out_dev.zero_(), 4 * n_ints),
@@ -745,22 +764,25 @@ def main():
         box_probe = probe
 
     if rank == 0:
-        # ---- what the stream is made of (host pre-pass over one replica) -------------
-        st = d.stream_stats(enc)  # (the first piece of the shard: a sample)
-        slots = st.codewords + st.exceptions16 + st.exceptions32
-        stream = {
-            "ints_per_codeword": round(st.ints / max(1, slots), 3),
-            "exception_pct": round(100.0 * (st.exceptions16 + st.exceptions32) / max(1, slots), 4),
-            "exception32_pct": round(100.0 * st.exceptions32 / max(1, slots), 4),
-            "lds_hit_pct": round(100.0 * st.hot_codewords / max(1, st.codewords), 2),
-            "lds_hit_pct_of_ints": round(100.0 * st.hot_ints / max(1, st.ints), 2),
-        }
-        if kind == host.MULTI_PACKED:
-            stream["blocks_16bit_pct"] = round(100.0 * st.wide_blocks / max(1, st.wide_blocks + st.narrow_blocks), 2)
+        # ---- --full: what the stream is made of (host pre-pass over one replica) -------------
+        stream, stream_sample = {}, None
+        if args.full:
+            st = d.stream_stats(enc)  # (the first piece of the shard: a sample)
+            slots = st.codewords + st.exceptions16 + st.exceptions32
+            stream = {
+                "ints_per_codeword": round(st.ints / max(1, slots), 3),
+                "exception_pct": round(100.0 * (st.exceptions16 + st.exceptions32) / max(1, slots), 4),
+                "exception32_pct": round(100.0 * st.exceptions32 / max(1, slots), 4),
+                "lds_hit_pct": round(100.0 * st.hot_codewords / max(1, st.codewords), 2),
+                "lds_hit_pct_of_ints": round(100.0 * st.hot_ints / max(1, st.ints), 2),
+            }
+            if kind == host.MULTI_PACKED:
+                stream["blocks_16bit_pct"] = round(100.0 * st.wide_blocks / max(1, st.wide_blocks + st.narrow_blocks), 2)
+            stream_sample = f"the first {int(st.ints)} postings of the shard"
 
-        # ---- CPU baseline (N=1 only): the oracle timed like vroom_env/decode.cpp ------
+        # ---- --full, N=1 only: the CPU baseline, the oracle timed like the reference's decode ------
         cpu = None
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             first = np.r_[True, units["list"][1:] != units["list"][:-1]]
             # a list's header starts where the previous list's payload ended
             prev_end = np.r_[np.uint64(0), ends[: len(units)][np.flatnonzero(np.r_[first[1:], True])][:-1]]  # (the first piece's lists)
@@ -768,7 +790,9 @@ def main():
 
         algo_bytes = 4 * n_ints + payload_bytes  # per launch, this rank
         traffic, traffic_note = None, "not measured in this process (rocprofv3 --pmc passes: tools/profile_round.sh)"
-        if args.traffic_file and os.path.exists(args.traffic_file):
+        if not args.full:
+            traffic_note += "; a traffic file is read with --full only"
+        elif args.traffic_file and os.path.exists(args.traffic_file):
             with open(args.traffic_file) as f:
                 tf = json.load(f)
             lib_now = lib_sha16()
@@ -825,7 +849,7 @@ def main():
                 "distinct_postings_per_gpu": n_shard,
                 "ints_per_gpu_per_step": n_ints,
                 "lists_per_gpu": int(np.count_nonzero(lens)) * R,
-                "stream_statistics_sample": f"the first {int(st.ints)} postings of the shard",
+                "stream_statistics_sample": stream_sample,
                 "units_per_gpu": n_units,
                 "unit_ints": args.unit_ints,
                 "schedule": "prepared unit table (set-up)" if unit_table is not None else "per launch (timed)",
@@ -878,6 +902,7 @@ def main():
                 "algorithmic_bytes_per_launch": algo_bytes,
             },
             "cpu_baseline": cpu,
+            "full": bool(args.full),
         }
         result = json.dumps(line)
 
@@ -886,6 +911,7 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         # (printed last: RCCL writes a line of its own to stdout when it is first used)
+        log(rank, "result line")
         sys.stdout.flush()
         print(result, flush=True)
 

@@ -13,8 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("extra", [[], ["--type", "multi_packed_dint", "--unit-ints", "256"], ["--type", "single_rect_dint", "--workload", "clueweb"]],
                          ids=["single_packed", "multi_block_units", "single_rect_clueweb"])
 def test_bench_line_contract(extra):
+    """--full: the line with everything beside the headline too (CPU baseline, stream statistics, box probe)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--postings", "3e6",
-           "--replicate", "2", "--dict-sample", "1e6", "--cpu-seconds", "0.5"] + extra
+           "--replicate", "2", "--dict-sample", "1e6", "--cpu-seconds", "0.5", "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -40,6 +41,22 @@ def test_bench_line_contract(extra):
     assert rf["traffic"] is None  # not measured in this process: only a same-command PMC file may fill it
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0 and cb["all_cores"]["cores"] >= 1 and cb["cpu_model"]
+    assert d["full"] is True and rf["box_probe"]["fill_gbps"] > 0 and rf["box_probe"]["compute_units"] > 0
+    assert 0 < d["config"]["lds_hit_pct"] <= 100 and d["config"]["ints_per_codeword"] > 0 and d["config"]["stream_statistics_sample"]
+
+
+def test_plain_bench_run_measures_the_headline_only():
+    """Without --full the line carries the headline, the roofline of the timed launches and the bit-exact check, and none of
+    what --full adds: no CPU baseline (even with a --cpu-seconds budget), no stream statistics, no box probe."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--postings", "3e6",
+           "--dict-sample", "1e6", "--cpu-seconds", "5"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["full"] is False and d["bit_exact"] is True and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["cpu_baseline"] is None and d["roofline"]["box_probe"] is None and d["roofline"]["traffic"] is None
+    assert "lds_hit_pct" not in d["config"] and d["config"]["stream_statistics_sample"] is None
+    assert len(d["config"]["placement_trial_kernel_ms"]["output_buffers"]) == 6 and d["roofline"]["kernel_launches_timed"] == 3
 
 
 def test_bench_placement_trials_are_in_the_line():

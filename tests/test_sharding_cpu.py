@@ -198,6 +198,46 @@ def test_bench_steps_are_the_timed_steps_and_dump_outputs(tmp_path):
     assert _stub_bench(["--gpus", "1", "--steps", "0"], {}).returncode != 0
 
 
+def test_bench_full_adds_what_the_headline_does_not_need():
+    """A plain run skips the CPU baseline (whatever --cpu-seconds says), the stream statistics and the traffic file; --full
+    runs them, and the line says which it was."""
+    import json
+
+    def line_of(extra):
+        r = _stub_bench(["--gpus", "1"] + extra, {})
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+
+    plain = line_of(["--cpu-seconds", "5"])
+    assert plain["full"] is False and plain["cpu_baseline"] is None and plain["roofline"]["box_probe"] is None
+    assert "ints_per_codeword" not in plain["config"] and plain["config"]["stream_statistics_sample"] is None
+    assert plain["roofline"]["traffic"] is None and "--full" in plain["roofline"]["traffic_note"]
+    full = line_of(["--full"])
+    assert full["full"] is True and "ints_per_codeword" in full["config"] and full["config"]["stream_statistics_sample"]
+    assert "--full" not in full["roofline"]["traffic_note"]
+    for key in ("value", "ms_per_step", "steps", "warmup", "metric", "unit", "higher_is_better", "dtype"):
+        assert key in plain and key in full, key
+
+
+def test_bench_setup_is_the_same_bytes_on_any_thread_count():
+    """bench.py sizes the set-up's thread pool by the CPUs it can use (usable_cpus: affinity cut to the cgroup quota): the
+    generated gaps, the host-built dictionary, the encoded stream and the unit table must not depend on that count."""
+    import bench
+
+    assert 1 <= bench.usable_cpus() <= len(os.sched_getaffinity(0))
+    p = host.synth_params(universe=3_000_000, seed=12345)
+    lens = host.synth_lengths(p, 3_000_000)
+    runs = []
+    for threads in (1, 3, 16):
+        coll = host.Collection(host.synth_gaps(p, lens, first_list_id=0, threads=threads), lens)
+        dict_file = host.build_dictionary(host.SINGLE_PACKED, coll, max_sample_ints=1_000_000, threads=threads)
+        enc, units = host.encode_vroom(host.SINGLE_PACKED, dict_file, coll, unit_ints=16384, threads=threads)
+        runs.append((coll.gaps, dict_file, enc, units.tobytes()))
+    for other in runs[1:]:
+        assert np.array_equal(runs[0][0], other[0]) and runs[0][1] == other[1]
+        assert np.array_equal(runs[0][2], other[2]) and runs[0][3] == other[3]
+
+
 def test_bench_dump_sample_is_fixed_and_bounded():
     import bench
 

@@ -7,7 +7,7 @@ TAG=${1:-r03}; shift
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 cd $R
 if [ -z "$SKIP_TESTS" ]; then python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; tail -3 $OUT/pytest_gpu.log; fi
-python3 bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err; cat $OUT/bench.json
+python3 bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err; cat $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
 BENCH="python3 $R/bench.py --steps 5 --warmup 2 --cpu-seconds 0 --no-verify $*"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH > $OUT/stats.log 2>&1
@@ -20,7 +20,7 @@ INTS=$(python3 -c "import json; print(json.load(open('$OUT/bench.json'))['config
 TYPE=$(python3 -c "import json; print(json.load(open('$OUT/bench.json'))['metric'].split('vroom ')[1].rstrip(')'))")
 python3 tools/pmc_traffic.py $OUT/fetch $OUT/write $TYPE $INTS $OUT/traffic.json | tee $OUT/traffic.log
 python3 tools/pmc_sq_summary.py $OUT $INTS | tee $OUT/sq.txt
-python3 bench.py --cpu-seconds 0 --traffic-file $OUT/traffic.json "$@" > $OUT/bench_with_traffic.json 2>> $OUT/bench.err; cat $OUT/bench_with_traffic.json
+python3 bench.py --full --cpu-seconds 0 --traffic-file $OUT/traffic.json "$@" > $OUT/bench_with_traffic.json 2>> $OUT/bench.err; cat $OUT/bench_with_traffic.json
 find $OUT/stats -name "*kernel_stats.csv" -exec cat {} \; | head -8 | tee $OUT/kernel_stats_head.csv
 # (the stats average over EVERY launch of the decode kernel in the profiled process — bench.py's placement trials during
 # set-up included, some of them into buffers the bench then drops; the timed region's launches are the last ones)

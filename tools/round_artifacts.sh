@@ -6,7 +6,7 @@
 TAG=${1:-r04}; R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/${TAG}x; mkdir -p $OUT
 cd $R
 MULTI="--type multi_packed_dint --unit-ints 256"
-timeout 600 python3 bench.py $MULTI --steps 20 --warmup 5 > $OUT/bench_multi.json 2> $OUT/bench_multi.err; cat $OUT/bench_multi.json | cut -c1-300
+timeout 600 python3 bench.py $MULTI --full --steps 20 --warmup 5 > $OUT/bench_multi.json 2> $OUT/bench_multi.err; cat $OUT/bench_multi.json | cut -c1-300
 cd /tmp && export TMPDIR=/tmp
 B="python3 $R/bench.py $MULTI --steps 5 --warmup 2 --cpu-seconds 0 --no-verify"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_multi -- $B > $OUT/stats_multi.log 2>&1

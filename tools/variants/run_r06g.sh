@@ -1,10 +1,10 @@
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/r06g; mkdir -p $OUT
 cd $R
 for wl in gov2-bpi59 gov2-exceptions gov2-freqs; do
-  timeout 600 python3 bench.py --workload $wl --steps 20 --warmup 5 --cpu-seconds 8 > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err
+  timeout 600 python3 bench.py --full --workload $wl --steps 20 --warmup 5 --cpu-seconds 8 > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err
 done
-timeout 600 python3 bench.py --type single_rect_dint --steps 20 --warmup 5 --cpu-seconds 8 > $OUT/bench_rect.json 2> $OUT/bench_rect.err
-timeout 600 python3 bench.py --workload clueweb --steps 20 --warmup 5 --cpu-seconds 8 > $OUT/bench_clueweb.json 2> $OUT/bench_clueweb.err
+timeout 600 python3 bench.py --full --type single_rect_dint --steps 20 --warmup 5 --cpu-seconds 8 > $OUT/bench_rect.json 2> $OUT/bench_rect.err
+timeout 600 python3 bench.py --full --workload clueweb --steps 20 --warmup 5 --cpu-seconds 8 > $OUT/bench_clueweb.json 2> $OUT/bench_clueweb.err
 timeout 300 python3 tools/index_stream_rate.py 5e8 $OUT/index_stream_rate.json > $OUT/index_stream_rate.log 2>&1
 timeout 1500 python3 tools/inindex_scale.py $OUT/inindex_scale.json 1e8,1e9,5e9 single_packed_dint,multi_packed_dint > $OUT/inindex_scale.log 2>&1
 timeout 1200 python3 tools/emulate_ranks.py --world 8 --out $OUT/config4_emulated.json -- --workload clueweb --type single_packed_dint --steps 10 --warmup 3 --cpu-seconds 0 > $OUT/config4.log 2>&1

@@ -8,4 +8,4 @@ timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OU
 timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- $B > $OUT/write.log 2>&1
 cd $R
 python3 tools/pmc_traffic.py $OUT/fetch $OUT/write multi_packed_dint 5000000000 $OUT/traffic_multi.json decode_multi | tee $OUT/traffic_multi.log
-timeout 600 python3 bench.py $MULTI --steps 20 --warmup 5 --traffic-file $OUT/traffic_multi.json > $OUT/bench_multi.json 2> $OUT/bench_multi.err; cut -c1-400 $OUT/bench_multi.json
+timeout 600 python3 bench.py $MULTI --full --steps 20 --warmup 5 --traffic-file $OUT/traffic_multi.json > $OUT/bench_multi.json 2> $OUT/bench_multi.err; cut -c1-400 $OUT/bench_multi.json
