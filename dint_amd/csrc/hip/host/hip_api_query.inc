@@ -3,7 +3,7 @@
 
 void dint_query_index_destroy(dint_query_index* qi) {
     if (!qi) return;
-    if (qi->docs) (void)hipSetDevice(qi->docs->device);  // (the workspaces are freed by delete, on this device)
+    (void)hipSetDevice(qi->device);  // (the workspaces are freed by delete, on this device; qi->docs may be gone already)
     for (void* p : {static_cast<void*>(qi->d_blocks), static_cast<void*>(qi->d_block_max), static_cast<void*>(qi->d_needed),
                     static_cast<void*>(qi->d_rank), static_cast<void*>(qi->d_touched)})
         if (p) (void)hipFree(p);
@@ -19,6 +19,7 @@ int dint_query_index_create(const dint_dict* docs_dict, const uint8_t* d_index, 
     auto* qi = new (std::nothrow) dint_query_index();
     if (!qi) return DINT_ERR_NOMEM;
     qi->docs = docs_dict;
+    qi->device = docs_dict->device;
     qi->d_index = d_index;
     qi->index_bytes = index_bytes;
     qi->n_blocks = n_blocks;
@@ -28,8 +29,9 @@ int dint_query_index_create(const dint_dict* docs_dict, const uint8_t* d_index, 
     uint32_t prev_list = 0;
     for (size_t b = 0; b != n_blocks; ++b) {
         const uint32_t l = blocks[b].list;
-        if (l >= n_lists || l < prev_list || blocks[b].n == 0 || blocks[b].n > 256 ||
-            blocks[b].in_off > index_bytes) {  // lists in order, each list's blocks contiguous
+        // lists in order, each list's blocks contiguous; docID 0xFFFFFFFF is kDeadCandidate, no docID (num_docs <= 2^32 - 1)
+        if (l >= n_lists || l < prev_list || blocks[b].n == 0 || blocks[b].n > 256 || blocks[b].in_off > index_bytes ||
+            blocks[b].max == 0xFFFFFFFFu) {
             delete qi;
             return DINT_ERR_FORMAT;
         }

@@ -25,6 +25,7 @@ struct device_buffer {  // grow-only workspace, freed with its owner (on the cur
 
 struct dint_query_index {
     const dint_dict* docs = nullptr;
+    int device = 0;  // docs->device, kept: the handle may be destroyed after its dictionary
     const uint8_t* d_index = nullptr;
     size_t index_bytes = 0;
     size_t n_blocks = 0;

@@ -354,7 +354,9 @@ int dint_decode_posting_blocks(const dint_dict* docs_dict, const dint_dict* freq
 typedef struct dint_query_index dint_query_index;
 
 /* blocks: HOST block table of ALL lists as produced by dint_index_posting_lists (lists in order,
- * each list's blocks contiguous); d_index: the index bytes on docs_dict's device. */
+ * each list's blocks contiguous); d_index: the index bytes on docs_dict's device. DocIDs must be
+ * below 0xFFFFFFFF (the reference's num_docs is a u32 and docIDs < num_docs; the query kernels use
+ * 0xFFFFFFFF as their dead-slot mark): a block whose max is 0xFFFFFFFF is DINT_ERR_FORMAT. */
 int dint_query_index_create(const dint_dict* docs_dict, const uint8_t* d_index, size_t index_bytes,
                             const dint_block_ref* blocks, size_t n_blocks, size_t n_lists,
                             dint_query_index** out);

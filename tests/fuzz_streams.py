@@ -513,16 +513,20 @@ def _block_part(r, D, n, profile, lit_cap):
     return body, expand(D, d, ids, lits)
 
 
-def make_index(r, Dd, Df, n_lists, max_n=1500, profiles=STREAM_PROFILES, value_cap=1 << 17):
+def make_index(r, Dd, Df, n_lists, max_n=1500, profiles=STREAM_PROFILES, value_cap=1 << 17, lengths=None):
     """Posting lists over a docs dictionary Dd (values below value_cap: docIDs of a list stay far below 2^32) and a freqs
-    dictionary Df (any values)."""
+    dictionary Df (any values). lengths: the postings of every list (n_lists of them) instead of drawn ones."""
     assert int(Dd.table.max(initial=0)) < value_cap
+    assert lengths is None or len(lengths) == n_lists
     lists, offsets, docids, freqs, bounds = [], [0], [], [], [0]
-    for _ in range(n_lists):
-        u = r.random()
-        n = int(r.integers(1, 256)) if u < 0.45 else int(r.integers(256, max_n + 1))
-        if r.random() < 0.2:
-            n = int(r.choice([1, 2, 255, 256, 257, 511, 512, 513]))
+    for li in range(n_lists):
+        if lengths is not None:
+            n = int(lengths[li])
+        else:
+            u = r.random()
+            n = int(r.integers(1, 256)) if u < 0.45 else int(r.integers(256, max_n + 1))
+            if r.random() < 0.2:
+                n = int(r.choice([1, 2, 255, 256, 257, 511, 512, 513]))
         blocks = (n + 255) // 256
         profile = profiles[int(r.integers(0, len(profiles)))]
         maxs, ends, body = [], [], []
@@ -602,3 +606,64 @@ def index_digest(Dd, Df, X):
               X.offsets.view(np.uint8), X.docids, X.freqs):
         h.update(np.ascontiguousarray(a).tobytes())
     return h.hexdigest()[:16]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the query plan: posting lists long enough to cross the query paths' page thresholds (a page = a block = 256 postings):
+# the workgroup-per-query batch form takes queries of at most 16 candidate pages (kBatchPages), the one-launch and
+# round-per-launch forms calls of at most 2 / 4 pages (query_fused_pages / query_tail_pages), a mixed call splits at 16
+# ---------------------------------------------------------------------------------------------------------------
+QUERY_EDGES = (767, 768, 769, 4095, 4096, 4097, 4353)
+QUERY_DOC_BOUND = 1 << 27  # ranked queries read norm_lens[docID]: 512 MiB of them at most
+
+
+def query_lengths(r, n_lists):
+    """The exact edges, two lists within a page of 2, 3, 4, 5, 16 and 17 pages each, three of 40 to 80 pages, the rest
+    short (1 to 511 postings), shuffled."""
+    out = list(QUERY_EDGES)
+    for pages in (2, 3, 4, 5, 16, 17):
+        out += [int(256 * pages + r.integers(-255, 256)) for _ in range(2)]
+    out += [int(r.integers(40 * 256, 80 * 256 + 1)) for _ in range(3)]
+    assert n_lists >= len(out)
+    out += [int(r.integers(1, 512)) for _ in range(n_lists - len(out))]
+    return [int(n) for n in r.permutation(out)]
+
+
+def query_plan(n_per_kind, lists_each):
+    """(seed, kind, docs dictionary shape, freqs dictionary shape, lists): docs dictionaries of small values only (with
+    docs literals below 2^12 the doc bound stays below QUERY_DOC_BOUND), freqs dictionaries of any values (wrapped freqs
+    of 0 and freqs near 2^32 included)."""
+    docs_shapes = [
+        dict(m_entries=8, value_profile="tiny", size_profile="pow2"),
+        dict(m_entries=300, value_profile="byte_edge", size_profile="any"),
+        dict(m_entries=65536, value_profile="tiny", size_profile="long", nest_p=0.3),
+        dict(m_entries=256, value_profile="zeros", size_profile="sixteen"),
+    ]
+    freqs_shapes = [
+        dict(m_entries=9, value_profile="wide", size_profile="pow2"),
+        dict(m_entries=3000, value_profile="mixed", size_profile="any"),
+        dict(m_entries=700, value_profile="tiny", size_profile="short"),
+        dict(m_entries=257, value_profile="zeros", size_profile="pow2"),
+    ]
+    out = []
+    for kind in (SINGLE, RECT, MULTI):
+        for k in range(n_per_kind):
+            ds, fs = dict(docs_shapes[k % len(docs_shapes)]), dict(freqs_shapes[(k + kind) % len(freqs_shapes)])
+            if kind == MULTI:
+                for s in (ds, fs):
+                    s["m_entries"] = min(s["m_entries"], 20000)
+                if k % 2:
+                    m = ds["m_entries"]
+                    ds["context_entries"] = [m, 7, 300, 7, max(7, m // 10), 40]
+            out.append((9000 * (kind + 1) + k, kind, ds, fs, lists_each))
+    return out
+
+
+def build_query_case(case):
+    seed, kind, ds, fs, n_lists = case
+    r = np.random.default_rng(seed)
+    Dd = make_dictionary(r, kind, **ds)
+    Df = make_dictionary(r, kind, **fs)
+    X = make_index(r, Dd, Df, n_lists, value_cap=1 << 12, lengths=query_lengths(r, n_lists))
+    assert int(X.docids.max()) < QUERY_DOC_BOUND
+    return Dd, Df, X

@@ -15,6 +15,7 @@ GOLDEN = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)),
 PARSE = {F.RECT: pydecode.parse_rectangular, F.SINGLE: pydecode.parse_single_packed, F.MULTI: pydecode.parse_multi_packed}
 VROOM = F.plan(*GOLDEN["vroom_plan"])
 INDEX = F.index_plan(*GOLDEN["index_plan"])
+QUERY = F.query_plan(*GOLDEN["query_plan"])
 
 
 @pytest.mark.parametrize("case", VROOM, ids=lambda c: f"seed{c[0]}")
@@ -60,6 +61,26 @@ def test_index_case(case):
         if i % 10 == 0:
             pd, pf = pydecode.decode_posting_list(ed, ef, raw, int(X.offsets[i]), Dd.kind == F.MULTI)
             assert pd == X.docids[lo:hi].tolist() and pf == X.freqs[lo:hi].tolist()
+
+
+@pytest.mark.parametrize("case", QUERY, ids=lambda c: f"seed{c[0]}")
+def test_query_case(case):
+    """The query plan (tests/test_gpu_query_fuzz.py): pinned, its lists cross the page thresholds of the query forms, its
+    doc bound leaves room for norm_lens, and the oracle decodes every list to the generator's postings."""
+    Dd, Df, X = F.build_query_case(case)
+    want = GOLDEN["query"][str(case[0])]
+    assert F.index_digest(Dd, Df, X) == want["digest"] and len(X.offsets) - 1 == want["lists"]
+    assert int(X.docids.max()) + 1 == want["doc_bound"] <= F.QUERY_DOC_BOUND
+    lens = np.diff(X.bounds)
+    assert set(F.QUERY_EDGES) <= set(lens.tolist())
+    pages = (lens + 255) // 256
+    assert (pages > 16).sum() >= 3 and ((pages >= 2) & (pages <= 5)).sum() >= 8 and pages.max() >= 40
+    assert (X.freqs == 0).any() or (X.freqs > 0xF0000000).any()
+    od, of = oracle.OracleDict(Dd.kind, Dd.file), oracle.OracleDict(Df.kind, Df.file)
+    for i in range(len(X.offsets) - 1):
+        d, f = oracle.posting_list_decode(od, of, X.index, int(X.offsets[i]))
+        lo, hi = int(X.bounds[i]), int(X.bounds[i + 1])
+        assert np.array_equal(d, X.docids[lo:hi]) and np.array_equal(f, X.freqs[lo:hi]), f"list {i}"
 
 
 def test_interpolative_writer_against_the_oracle():
