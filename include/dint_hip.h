@@ -154,10 +154,20 @@ void dint_free(void* p);
  * overflow area — unlike the reference, dint_codecs.hpp:11). If d_end_off is
  * not NULL, d_end_off[u] receives the byte offset one past unit u's last
  * consumed byte (the reference's returned `in` pointer).
- * Units may come in any order; runs of table-consecutive tiny units (<= 256
- * integers, <= 256 stream bytes up to the next unit's start, consecutive
- * outputs — the long tail of short posting lists) are decoded several to a
- * wavefront tile, which changes the speed, never the result.
+ * Units may come in any order and any subset: a permutation or a subset of
+ * dint_index_stream's table, units repeated (one in_off in several entries),
+ * outputs anywhere in d_out (holes between them are left as they were; the
+ * outputs of two entries must not overlap). A unit's stream bytes are bounded
+ * by where the NEXT table entry starts when that lies above the unit's own
+ * start, so no unit may begin strictly inside an earlier table entry's bytes
+ * (a whole list followed by its own later pieces): such a table returns
+ * DINT_OK and writes every unit only inside its own [out_off, out_off + n),
+ * but the unit it cuts into may decode wrong, its end offset too. Tables of
+ * dint_index_stream, and every subset or permutation of them, satisfy this.
+ * Runs of table-consecutive tiny units (<= 256 integers, <= 256 stream bytes
+ * up to the next unit's start, consecutive outputs — the long tail of short
+ * posting lists) are decoded several to a wavefront tile, which changes the
+ * speed, never the result.
  * Replaces: single_dint::decode / multi_opt_dint::decode
  *           (vroom_env/dint_codecs.hpp:37-107, :521-619). */
 int dint_decode_units(const dint_dict* dict, const uint8_t* d_enc, size_t enc_bytes,
@@ -170,7 +180,8 @@ int dint_decode_units(const dint_dict* dict, const uint8_t* d_enc, size_t enc_by
  * runs before EVERY launch) — is computed once, here, like the sidecar itself (it is a property of the encoded
  * collection, not of a decode). The handle borrows `dict`, `d_enc` and `d_units`: they must outlive it and keep
  * their contents. `out_capacity` is the smallest output capacity later decodes may pass (the schedule's bounds
- * checks are made against it). Synchronises `stream`.
+ * checks are made against it). The table may be shaped as dint_decode_units allows — any order, subsets, repeats, outputs
+ * with holes — under the same rule: no unit begins strictly inside an earlier entry's bytes. Synchronises `stream`.
  * A multi-dictionary table whose units hold SEVERAL 256-integer blocks (at most 131072 integers each) is refined here: blocks
  * carry no length, so a unit of several is one wavefront's sequential work (242 G ints/s on the bench stream), where a table of
  * blocks packs three blocks into a tile (472-526 G). A lane per unit walks the unit's codewords once and the handle keeps a
@@ -259,7 +270,11 @@ void dint_list_cache_destroy(dint_list_cache* cache);
  * reference include/dint/dict_posting_list.hpp:10-56:
  *   vbyte(n) | u32 block_max[B] | u32 block_endpoint[B-1] | { docs part, freqs part } x B
  * The block-max / endpoint arrays already make every block independently addressable, so no
- * sidecar is needed here: this table is just those arrays flattened over many lists. */
+ * sidecar is needed here: this table is just those arrays flattened over many lists.
+ * dint_decode_posting_blocks and dint_block_table_create take any table of such refs, each carrying
+ * its own in_off / out_off / base / max: blocks and lists in any order, any subset of them (the lists
+ * a query touches), a block repeated in several entries, outputs anywhere below out_capacity (holes
+ * between them are left as they were; the outputs of two entries must not overlap). */
 typedef struct dint_block_ref {
     uint64_t in_off;  /* byte offset of the block's docs part in the index buffer            */
     uint64_t out_off; /* index of the block's first posting in the output arrays             */

@@ -2,7 +2,8 @@
 """Test infrastructure (GPU box; lives in tests/ because it checks against the oracle): the differential fuzzer of tests/test_gpu_fuzz.py over seeds of its OWN — the committed plan's
 dictionary and stream shapes, fresh random numbers — for as long as asked. Every case runs the same checks as the pinned
 ones (integers, docIDs, freqs, end offsets, canaries, prepared tables, AND queries against the generator's substitution
-and the oracle; the query plan's cases: all six query types, tests/test_gpu_query_fuzz.py); the first failure stops the run and names the seed, which then reproduces with
+and the oracle; the query plan's cases: all six query types, tests/test_gpu_query_fuzz.py; every case's unit or block table reshaped —
+permuted, subsets, scattered outputs, repeated and overlapping entries — tests/test_gpu_table_shapes.py); the first failure stops the run and names the seed, which then reproduces with
 `tests/fuzz_soak.py --rounds 1 --first-round R`.
 
 --random-options: every case under a random legal setting of the library's switches (dint_set_option: bundles, chunk_split,
@@ -16,6 +17,7 @@ sys.path[:0] = [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), ROOT]
 import numpy as np
 import test_gpu_fuzz as T
 import test_gpu_query_fuzz as Q
+import test_gpu_table_shapes as TG
 import fuzz_streams as F
 from dint_amd import device
 
@@ -47,6 +49,15 @@ for rnd in range(args.first_round, args.first_round + args.rounds):
                 Q.run_query_case(device, case, setting if args.random_options else None)
             else:
                 (T.test_vroom_case if what == "vroom" else T.test_index_case)(device, case)
+            # the case's own tables reshaped (tests/table_shapes.py)
+            if what == "vroom":
+                D, _, d, enc_dev, shapes = TG.build_unit_case(case)
+                for sh in shapes.values():
+                    TG.check_unit_shape(device, D.kind, d, enc_dev, sh, str(setting))
+            else:
+                dd, fd, padded, index_dev, shapes = TG.build_block_case(case, F.build_query_case if what == "query" else F.build_index_case)
+                for sh in shapes.values():
+                    TG.check_block_shape(device, dd, fd, padded, index_dev, sh, str(setting))
         except Exception:
             traceback.print_exc()
             print(f"FAILED: round {rnd}, {what} case seed {case[0]}, options {setting}", flush=True)
