@@ -8,6 +8,44 @@
 // rk (dint_ranked_or_queries, hip_api_ranked_or_query.inc): the pass's probe launch is ranked_or_score_kernel instead, and
 // ranked_topk writes the best keys of the pass's queries to rk->keys at their own offset; the counters are not used.
 
+// The set-up of an OR call, shared with the pruned ranked call (hip_api_ranked_or_maxscore.inc): the plan (longest list
+// first, with multiplicities if with_qf), every query's pages (every block of its distinct terms; a query without any
+// has len 0) and the passes: whole queries, at most `limit` pages each — a query larger than that alone, in a pass sized to it.
+struct or_passes {
+    query_plan plan;
+    std::vector<uint64_t> pages;  // per query
+    std::vector<size_t> first;    // pass k: queries [first[k], first[k + 1])
+    uint64_t all = 0;
+};
+static int plan_or_passes(const dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries,
+                          bool with_qf, bool with_freqs, uint64_t* counts, uint64_t* freq_sums, or_passes& op) {
+    query_plan& plan = op.plan;
+    const int planned = plan_queries(qi, terms, query_offsets, n_queries, true, with_qf, with_freqs, counts, freq_sums, plan);
+    if (planned != DINT_OK) return planned;
+    op.pages.assign(n_queries, 0);
+    op.all = 0;
+    for (size_t q = 0; q != n_queries; ++q) {
+        for (uint32_t j = 0; j != plan.len[q]; ++j) {
+            const uint32_t l = plan.of(q)[j];
+            op.pages[q] += qi->list_first[l + 1] - qi->list_first[l];
+        }
+        if (op.pages[q] == 0) plan.len[q] = 0;  // (lists without a block)
+        op.all += op.pages[q];
+    }
+    const uint64_t limit = uint64_t(opt(DINT_OPT_QUERY_OR_PASS_PAGES));
+    op.first.assign(1, 0);
+    uint64_t in_pass = 0;
+    for (size_t q = 0; q != n_queries; ++q) {
+        if (in_pass != 0 && in_pass + op.pages[q] > limit) {
+            op.first.push_back(q);
+            in_pass = 0;
+        }
+        in_pass += op.pages[q];
+    }
+    op.first.push_back(n_queries);
+    return DINT_OK;
+}
+
 static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream,
                            const ranked_args* rk = nullptr) {
@@ -15,32 +53,14 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
     if (n_queries >= 0xFFFFFFFFull) return DINT_ERR_ARG;
-    query_plan plan;  // (rk: with multiplicities, for the query weights)
-    const int planned = plan_queries(qi, terms, query_offsets, n_queries, true, rk != nullptr, freqs_dict != nullptr, counts, freq_sums, plan);
+    or_passes op;  // (rk: with multiplicities, for the query weights)
+    const int planned = plan_or_passes(qi, terms, query_offsets, n_queries, rk != nullptr, freqs_dict != nullptr, counts, freq_sums, op);
     if (planned != DINT_OK) return planned;
-    std::vector<uint64_t> plan_pages(n_queries, 0);
+    const query_plan& plan = op.plan;
+    const std::vector<uint64_t>& plan_pages = op.pages;
+    const std::vector<size_t>& pass_first = op.first;
     auto list_blocks = [&](uint32_t l) { return uint64_t(qi->list_first[l + 1] - qi->list_first[l]); };
-    uint64_t all_pages = 0;
-    for (size_t q = 0; q != n_queries; ++q) {
-        for (uint32_t j = 0; j != plan.len[q]; ++j) plan_pages[q] += list_blocks(plan.of(q)[j]);
-        if (plan_pages[q] == 0) plan.len[q] = 0;  // (lists without a block)
-        all_pages += plan_pages[q];
-    }
-    if (all_pages == 0) return DINT_OK;
-    // passes: whole queries, at most `limit` pages each — a query larger than that alone, in a pass sized to it
-    const uint64_t limit = uint64_t(opt(DINT_OPT_QUERY_OR_PASS_PAGES));
-    std::vector<size_t> pass_first(1, 0);  // pass k: queries [pass_first[k], pass_first[k + 1])
-    {
-        uint64_t in_pass = 0;
-        for (size_t q = 0; q != n_queries; ++q) {
-            if (in_pass != 0 && in_pass + plan_pages[q] > limit) {
-                pass_first.push_back(q);
-                in_pass = 0;
-            }
-            in_pass += plan_pages[q];
-        }
-        pass_first.push_back(n_queries);
-    }
+    if (op.all == 0) return DINT_OK;
 
     std::lock_guard<std::mutex> lock(qi->mutex);
     HIP_TRY(hipSetDevice(qi->docs->device));

@@ -10,6 +10,9 @@ struct dint_wand_data {
     int device = 0;
     uint64_t num_docs = 0;
     float* d_norm_lens = nullptr;
+    // dint_wand_data_create_with_max_weights: max_term_weight[n_lists], on the host (only the pruned ranked call reads it)
+    bool has_max_weights = false;
+    std::vector<float> max_term_weight;
 };
 
 void dint_wand_data_destroy(dint_wand_data* wd) {
@@ -39,6 +42,23 @@ int dint_wand_data_create(int device, const float* norm_lens, uint64_t num_docs,
         return DINT_ERR_HIP;
     }
     *out = wd;
+    return DINT_OK;
+}
+
+int dint_wand_data_create_with_max_weights(int device, const float* norm_lens, uint64_t num_docs, const float* max_term_weight,
+                                           size_t n_lists, dint_wand_data** out) {
+    if (!out || (n_lists && !max_term_weight)) return DINT_ERR_ARG;
+    const int st = dint_wand_data_create(device, norm_lens, num_docs, out);
+    if (st != DINT_OK) return st;
+    dint_wand_data* wd = *out;
+    try {
+        wd->max_term_weight.assign(max_term_weight, max_term_weight + n_lists);
+    } catch (const std::bad_alloc&) {
+        dint_wand_data_destroy(wd);
+        *out = nullptr;
+        return DINT_ERR_NOMEM;
+    }
+    wd->has_max_weights = true;
     return DINT_OK;
 }
 

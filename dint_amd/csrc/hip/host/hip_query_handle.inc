@@ -61,6 +61,9 @@ struct dint_query_index {
     device_buffer<float> slot_score, slot_kden, qweights;
     device_buffer<uint32_t> topk_in;
     device_buffer<unsigned long long> topk_keys, topk_out;
+    // the pruned ranked OR call (hip_api_ranked_or_maxscore.inc): per claim flag of a pass, the flag and its place in the
+    // touched list; the touched blocks; {touched count, per query of the pass its claims}
+    device_buffer<uint32_t> ms_flag, ms_rank, ms_touched, ms_count;
     std::mutex mutex;
 
     // h_stage of at least `bytes` (grown by half again), d_stage the same memory as the kernels see it (null where it

@@ -35,7 +35,8 @@ ABI_SYMBOLS = (
     "dint_list_cache_create", "dint_list_cache_decode", "dint_list_cache_destroy",
     "dint_block_table_create", "dint_block_table_destroy", "dint_block_table_learn", "dint_block_table_ready", "dint_block_table_info_get", "dint_decode_block_table",
     "dint_query_index_create", "dint_query_index_destroy", "dint_and_queries", "dint_and_queries_freqs", "dint_or_queries", "dint_or_queries_freqs",
-    "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_or_queries", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
+    "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_or_queries",
+    "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
 
 #: dint_block_ref (include/dint_hip.h)
@@ -128,6 +129,8 @@ def _load():
     lib.dint_wand_data_destroy.argtypes = [vp]
     lib.dint_ranked_and_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, vp]
     lib.dint_ranked_or_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, vp]
+    lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
+    lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_count_ngrams.argtypes = [C.c_int, C.c_int, vp, u64, vp, u64, C.c_uint32, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_float)]
     lib.dint_select_ngrams.argtypes = [C.c_int, vp, u64, u64, vp, sz, C.c_uint32, C.POINTER(sz)]
     lib.dint_debug_wave_scan.argtypes = [vp, vp]
@@ -599,19 +602,40 @@ class QueryIndex:
         descending, docids u32[n, k]; equal scores by ascending docID, 0.0 / 0xFFFFFFFF past a query's count)."""
         return self._ranked("dint_ranked_or_queries", freqs_dict, wand, queries, k)
 
+    def ranked_or_maxscore_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10):
+        """ranked_or_queries' answer, bit for bit, with MaxScore's pruning: the blocks of low-weight
+        lists that no candidate able to reach the top k falls in are not decoded. `wand` must carry max_term_weight ->
+        (counts, scores, docids as ranked_or_queries, blocks read: the distinct index blocks the queries decoded, summed)."""
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        counts = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        blocks = C.c_uint64()
+        _check(_lib.dint_ranked_or_maxscore_queries(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data, n,
+                                                    counts.ctypes.data, scores.ctypes.data, docids.ctypes.data, C.byref(blocks),
+                                                    self._stream()), "dint_ranked_or_maxscore_queries")
+        return counts, scores, docids, blocks.value
+
 
 class WandData:
     """The wand data's document lengths on the device (dint_wand_data_create): norm_lens f32[num_docs], as
-    host.wand_data / host.read_wand_data give them."""
+    host.wand_data / host.read_wand_data give them; with max_term_weight f32[n_lists] (the same functions' second array)
+    the handle also carries the term maxima that ranked_or_maxscore_queries needs (dint_wand_data_create_with_max_weights)."""
 
     MAX_K = 1024  # DINT_RANKED_MAX_K (include/dint_hip.h)
 
-    def __init__(self, norm_lens: np.ndarray, device: int = 0):
+    def __init__(self, norm_lens: np.ndarray, device: int = 0, max_term_weight=None):
         nl = np.ascontiguousarray(norm_lens, dtype=np.float32)
         self.num_docs = nl.size
         self.device = device
         self._h = C.c_void_p()
-        _check(_lib.dint_wand_data_create(device, nl.ctypes.data, nl.size, C.byref(self._h)), "dint_wand_data_create")
+        if max_term_weight is None:
+            _check(_lib.dint_wand_data_create(device, nl.ctypes.data, nl.size, C.byref(self._h)), "dint_wand_data_create")
+        else:
+            mw = np.ascontiguousarray(max_term_weight, dtype=np.float32)
+            _check(_lib.dint_wand_data_create_with_max_weights(device, nl.ctypes.data, nl.size, mw.ctypes.data, mw.size,
+                                                               C.byref(self._h)), "dint_wand_data_create_with_max_weights")
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None

@@ -429,7 +429,7 @@ typedef struct dint_wand_data dint_wand_data;
 int dint_wand_data_create(int device, const float* norm_lens, uint64_t num_docs, dint_wand_data** out);
 void dint_wand_data_destroy(dint_wand_data* wd);
 
-#define DINT_RANKED_MAX_K 1024 /* the largest k dint_ranked_and_queries and dint_ranked_or_queries take */
+#define DINT_RANKED_MAX_K 1024 /* the largest k the ranked calls (AND, OR, pruned OR) take */
 
 /* For query q — its distinct terms t with multiplicity qf_t (query_freqs, queries.hpp:135-148) — every document d of the
  * intersection of their lists scores sum_t q_weight_t * doc_term_weight(freq_t(d), norm_lens[d]) (bm25.hpp), with
@@ -462,6 +462,28 @@ int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, c
 int dint_ranked_or_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
                            const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts,
                            float* scores, uint32_t* docids, void* stream);
+
+/* ---- MaxScore-pruned ranked disjunctive queries over the same query index ---------------------------
+ * Replaces: the dynamic pruning of maxscore_query (include/ds2i/queries.hpp:459-573), with ranked_or_query's sums.
+ * dint_wand_data_create_with_max_weights is dint_wand_data_create plus a HOST copy of wand_data's max_term_weight[n_lists]
+ * (dinth_wand_data / dinth_read_wand_data of include/dint_host.h); max_term_weight may be null only if n_lists is 0.
+ * dint_ranked_or_maxscore_queries returns exactly what dint_ranked_or_queries returns — counts, scores and docIDs, bit for
+ * bit — but does not decode the blocks of the low-weight lists that no candidate able to reach the top k falls in
+ * (DESIGN.md 4d-maxscore): per query a threshold from its shortest list of at least k postings, the terms whose summed
+ * maxima stay below it left out of the candidates, each candidate's upper bound checked, and the blocks of those terms
+ * claimed by the surviving candidates only. SAFETY ASSUMPTION: max_term_weight[t] >= f / (f + k1 * ((1 - b) + b * norm_len))
+ * of every posting of list t, as the kernels compute it in binary32; dinth_wand_data and dint_create_wand_data compute
+ * max_term_weight with that very expression, so their files and arrays hold it. Smaller maxima may drop documents.
+ * *blocks_read (nullable) = the sum over the call's queries of the distinct index blocks whose docs and freqs parts the
+ * query's evaluation decoded (the unit of dint_or_queries_freqs' freq_blocks_decoded; dint_ranked_or_queries reads every
+ * block of every distinct term). Arguments, outputs, errors, lock, stream and passes are those of dint_ranked_or_queries;
+ * besides, DINT_ERR_ARG before anything is launched: a wand handle without maxima (dint_wand_data_create), or with fewer
+ * than the index's n_lists of them. */
+int dint_wand_data_create_with_max_weights(int device, const float* norm_lens, uint64_t num_docs, const float* max_term_weight,
+                                           size_t n_lists, dint_wand_data** out);
+int dint_ranked_or_maxscore_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                    const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts,
+                                    float* scores, uint32_t* docids, uint64_t* blocks_read, void* stream);
 
 /* ---- block statistics on the device (dictionary construction, counting half) ----------------------------
  * Counts every aligned 16/8/4/2/1-gram of the given lists — multi != 0: of their whole 256-integer blocks, per block

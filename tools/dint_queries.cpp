@@ -2,11 +2,14 @@
 //
 //   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
-//   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or, several separated by ':' (src/queries.cpp:93-111);
+//   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore, several separated by ':'
+//               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
 //               BM25 top 10 of the union) is not in the reference driver's list, and is answered as ranked_and is, with
-//               the wand file, and refused the same way without one; wand and maxscore are out of scope and always print it
+//               the wand file, and refused the same way without one; ranked_or_maxscore is ranked_or with MaxScore's pruning
+//               (the same results; the wand file's max_term_weight goes to the device handle), also only with a wand file;
+//               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
 //   query_log on stdin: one query per line, term ids separated by blanks (include/ds2i/queries.hpp:15-27)
@@ -102,8 +105,9 @@ int main(int argc, char** argv) {
         if (wand_filename) {  // (the reference maps the wand data once, src/queries.cpp:84-89)
             tool::blob norm_lens, max_term_weight;
             tool::host_ok(dinth_read_wand_data(wand_filename, &norm_lens.h, &max_term_weight.h), "dinth_read_wand_data");
-            dint_ok(dint_wand_data_create(0, static_cast<const float*>(norm_lens.data()), norm_lens.size() / 4, &wand),
-                    "dint_wand_data_create");
+            dint_ok(dint_wand_data_create_with_max_weights(0, static_cast<const float*>(norm_lens.data()), norm_lens.size() / 4,
+                                                           static_cast<const float*>(max_term_weight.data()), max_term_weight.size() / 4, &wand),
+                    "dint_wand_data_create_with_max_weights");
         }
         constexpr uint32_t kTopK = 10;  // ranked_and_query(wdata, 10), src/queries.cpp:106-108
         std::vector<float> top_scores;
@@ -116,8 +120,9 @@ int main(int argc, char** argv) {
             a = b + 1;
         }
         for (auto const& t : types) {
+            const bool is_maxscore = t == "ranked_or_maxscore" && wand;
             const bool is_ranked_or = t == "ranked_or" && wand;
-            const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or;
+            const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
                 std::cerr << "Unsupported query type: " << t << std::endl;  // src/queries.cpp:108-110
                 continue;
@@ -127,7 +132,12 @@ int main(int argc, char** argv) {
             // one call of the query type's entry: n queries, packed
             auto run_queries = [&](const uint32_t* q_terms, const uint64_t* q_offs, size_t n, uint64_t* q_counts, uint64_t* q_fsums) {
                 uint64_t fblocks = 0;
-                if (is_ranked_or) {
+                if (is_maxscore) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
+                                                            nullptr, nullptr),
+                            "dint_ranked_or_maxscore_queries");
+                } else if (is_ranked_or) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr, nullptr),
                             "dint_ranked_or_queries");
