@@ -48,6 +48,11 @@ int dint_wand_data_create(int device, const float* norm_lens, uint64_t num_docs,
 int dint_wand_data_create_with_max_weights(int device, const float* norm_lens, uint64_t num_docs, const float* max_term_weight,
                                            size_t n_lists, dint_wand_data** out) {
     if (!out || (n_lists && !max_term_weight)) return DINT_ERR_ARG;
+    *out = nullptr;
+    // a NaN or negative maximum is refused: the pruned call orders a query's terms by q_weight * maximum, and a NaN there
+    // is no strict weak ordering for std::sort (+inf is a legal upper bound: its term is never left out)
+    for (size_t t = 0; t != n_lists; ++t)
+        if (!(max_term_weight[t] >= 0.0f)) return DINT_ERR_ARG;
     const int st = dint_wand_data_create(device, norm_lens, num_docs, out);
     if (st != DINT_OK) return st;
     dint_wand_data* wd = *out;

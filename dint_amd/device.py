@@ -621,7 +621,9 @@ class QueryIndex:
 class WandData:
     """The wand data's document lengths on the device (dint_wand_data_create): norm_lens f32[num_docs], as
     host.wand_data / host.read_wand_data give them; with max_term_weight f32[n_lists] (the same functions' second array)
-    the handle also carries the term maxima that ranked_or_maxscore_queries needs (dint_wand_data_create_with_max_weights)."""
+    the handle also carries the term maxima that ranked_or_maxscore_queries needs (dint_wand_data_create_with_max_weights).
+    Creation raises DintError (DINT_ERR_ARG) for a NaN or negative maximum; maxima above the true ones, up to +inf, are
+    legal and only make the pruned call read more blocks."""
 
     MAX_K = 1024  # DINT_RANKED_MAX_K (include/dint_hip.h)
 

@@ -467,13 +467,18 @@ int dint_ranked_or_queries(dint_query_index* qi, const dint_dict* freqs_dict, co
  * Replaces: the dynamic pruning of maxscore_query (include/ds2i/queries.hpp:459-573), with ranked_or_query's sums.
  * dint_wand_data_create_with_max_weights is dint_wand_data_create plus a HOST copy of wand_data's max_term_weight[n_lists]
  * (dinth_wand_data / dinth_read_wand_data of include/dint_host.h); max_term_weight may be null only if n_lists is 0.
+ * A NaN or negative maximum is DINT_ERR_ARG, checked before the device is touched (*out is null then); -0.0f, +inf and
+ * FLT_MAX are accepted.
  * dint_ranked_or_maxscore_queries returns exactly what dint_ranked_or_queries returns — counts, scores and docIDs, bit for
  * bit — but does not decode the blocks of the low-weight lists that no candidate able to reach the top k falls in
  * (DESIGN.md 4d-maxscore): per query a threshold from its shortest list of at least k postings, the terms whose summed
  * maxima stay below it left out of the candidates, each candidate's upper bound checked, and the blocks of those terms
  * claimed by the surviving candidates only. SAFETY ASSUMPTION: max_term_weight[t] >= f / (f + k1 * ((1 - b) + b * norm_len))
  * of every posting of list t, as the kernels compute it in binary32; dinth_wand_data and dint_create_wand_data compute
- * max_term_weight with that very expression, so their files and arrays hold it. Smaller maxima may drop documents.
+ * max_term_weight with that very expression, so their files and arrays hold it. Any larger maxima (up to +inf) give the same
+ * answer and only read more blocks; with +inf nothing is left out and every block is read. Smaller maxima may drop
+ * documents and nothing else: the call still returns DINT_OK, every (docID, score) it returns is a document of the union
+ * with its exact dint_ranked_or_queries score, in that call's order, and counts[q] is at most that call's.
  * *blocks_read (nullable) = the sum over the call's queries of the distinct index blocks whose docs and freqs parts the
  * query's evaluation decoded (the unit of dint_or_queries_freqs' freq_blocks_decoded; dint_ranked_or_queries reads every
  * block of every distinct term). Arguments, outputs, errors, lock, stream and passes are those of dint_ranked_or_queries;

@@ -2,7 +2,7 @@
 """Test infrastructure (GPU box; lives in tests/ because it checks against the oracle): the differential fuzzer of tests/test_gpu_fuzz.py over seeds of its OWN — the committed plan's
 dictionary and stream shapes, fresh random numbers — for as long as asked. Every case runs the same checks as the pinned
 ones (integers, docIDs, freqs, end offsets, canaries, prepared tables, AND queries against the generator's substitution
-and the oracle; the query plan's cases: all six query types, tests/test_gpu_query_fuzz.py; every case's unit or block table reshaped —
+and the oracle; the query plan's cases: all seven query types, the MaxScore-pruned ranked OR with its blocks read among them, tests/test_gpu_query_fuzz.py; every case's unit or block table reshaped —
 permuted, subsets, scattered outputs, repeated and overlapping entries — tests/test_gpu_table_shapes.py); the first failure stops the run and names the seed, which then reproduces with
 `tests/fuzz_soak.py --rounds 1 --first-round R`.
 

@@ -80,7 +80,8 @@ def maxscore(lists, terms, norm_lens_, max_term_weight, num_docs: int, k: int) -
         theta = np.sort(addend(seed))[::-1][k - 1]
     # 2. the split
     margin = 1.0 + (n + 1) * 2.0 ** -23
-    m = [np.float32(qw[j] * np.float32(max_term_weight[int(t[j])])) for j in range(n)]
+    with np.errstate(over="ignore"):  # (maxima up to FLT_MAX and +inf are legal upper bounds: m_t = +inf keeps t in E)
+        m = [np.float32(qw[j] * np.float32(max_term_weight[int(t[j])])) for j in range(n)]
     in_n = np.zeros(n, dtype=bool)
     rest = 0.0
     if theta > 0:
@@ -117,6 +118,21 @@ def maxscore(lists, terms, norm_lens_, max_term_weight, num_docs: int, k: int) -
     scores[:c] = sc[best]
     ids[:c] = live[best]
     return Result(c, scores, ids, read, float(theta), live, union, union_scores, len(e_plan), int(nb.sum()))
+
+
+def assert_degraded(count, scores, ids, res: Result, want_count: int):
+    """What maxima below the true ones may do to an answer (include/dint_hip.h) and nothing else: `count` (docID, score) pairs,
+    each a document of the query's union with its exact ranked_or score (res.union / res.union_scores: any model run of the
+    query has them), strictly ordered by (score descending, docID ascending), no more of them than ranked_or returns."""
+    count = int(count)
+    assert count <= want_count <= scores.size
+    got_ids, got_scores = ids[:count], scores[:count]
+    pos = np.searchsorted(res.union, got_ids)
+    assert (pos < res.union.size).all() and np.array_equal(res.union[np.minimum(pos, max(res.union.size - 1, 0))], got_ids)
+    assert np.array_equal(res.union_scores[pos].view(np.uint32), got_scores.view(np.uint32))
+    later = (got_scores[1:] < got_scores[:-1]) | ((got_scores[1:] == got_scores[:-1]) & (got_ids[1:] > got_ids[:-1]))
+    assert later.all()
+    assert (scores[count:] == 0).all() and (ids[count:] == 0xFFFFFFFF).all()
 
 
 def mixed_queries(lens: np.ndarray, n_queries: int, seed: int = 9, pool: int = 48, lo: int = 16, hi: int = 4096):

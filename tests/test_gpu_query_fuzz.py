@@ -1,11 +1,13 @@
-"""Differential fuzzing of the six query types on the GPU: AND, AND with freqs, OR, OR with freqs, ranked AND and ranked OR
-over the query plan of tests/fuzz_streams.py (random dictionary files, random decoder-legal posting lists of up to 80
-pages, wrapped freqs of 0 and freqs near 2^32) — against plain set arithmetic over the generator's postings, the binary32
-models of tests/ranked.py / tests/ranked_or.py, and on a sample the lists the CPU oracle decodes from the index bytes.
-Every case runs a seeded query mix (empty, single-term, repeated-term, 8-32-term, small and large queries in one call) in
-one call and, on a sample, one query per call, under a seeded setting of the query options. Then hand-made lists for the
-ranked selection's edges: ties across the k-th place over 3, 5, 7 and 33 runs, k = 257 and 1024, scores of 0.0 and
-subnormal scores."""
+"""Differential fuzzing of the seven query types on the GPU: AND, AND with freqs, OR, OR with freqs, ranked AND, ranked OR
+and MaxScore-pruned ranked OR over the query plan of tests/fuzz_streams.py (random dictionary files, random decoder-legal
+posting lists of up to 80 pages, wrapped freqs of 0 and freqs near 2^32) — against plain set arithmetic over the generator's
+postings, the binary32 models of tests/ranked.py / tests/ranked_or.py, the pruned call's model (tests/maxscore.py: the same
+answer as ranked OR and its blocks read, block for block) and on a sample the lists the CPU oracle decodes from the index
+bytes. Every case runs a seeded query mix (empty, single-term, repeated-term, 8-32-term, small and large queries in one
+call) in one call and, on a sample, one query per call, under a seeded setting of the query options; the pruned call also
+with its queries reversed and with every query twice in the call. The draws are tests/query_fuzz_draws.py's, which
+tests/test_ranked_or_maxscore_cpu.py replays without a GPU. Then hand-made lists for the ranked selection's edges: ties
+across the k-th place over 3, 5, 7 and 33 runs, k = 257 and 1024, scores of 0.0 and subnormal scores."""
 import json
 import os
 
@@ -13,23 +15,19 @@ import numpy as np
 import pytest
 
 import fuzz_streams as F
+import maxscore
 import ranked
 import ranked_or
 from dint_amd import host
 from or_union import OracleLists, union_freqs
 from queries import intersect_freqs
+from query_fuzz_draws import CHOICES, KS, NORM_LENS, draw_case, draw_norm_lens, query_mix  # noqa: F401 (the draws live there)
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fuzz_digests.json")))
 QUERY = F.query_plan(*GOLDEN["query_plan"])
 assert all(str(c[0]) in GOLDEN["query"] for c in QUERY)
-
-KS = (1, 2, 255, 256, 257, 511, 512, 513, 1000, 1023, 1024)
-CHOICES = {"query_batch_fused": [0, 1, 1], "query_fused_pages": [0, 2, 8], "query_tail_pages": [0, 1, 4, 16],
-           "query_lean_pages": [-1, -1, 0, 1, 3], "query_fused_copy": [0, 1],
-           "query_or_pass_pages": [1, 2, 3, 5, 8, 64, 1 << 20]}
-NORM_LENS = ("random", "equal", "zeros", "large")
 
 
 @pytest.fixture(scope="module")
@@ -48,35 +46,6 @@ def _options_back_to_default(device):
     device.reset_options()
 
 
-def query_mix(r, lens):
-    """Empty and single-term queries, repeated terms (qf > 1), small queries of any lists (the workgroup-per-query form)
-    and large ones over the longest lists in the same call (the mixed-call split), queries of 8 to 32 terms; shuffled."""
-    n = len(lens)
-    big = np.argsort(-lens.astype(np.int64), kind="stable")[:14]
-    qs = [[], []]
-    qs += [[int(t)] for t in r.choice(n, 6, replace=False)] + [[int(t)] for t in r.choice(big, 3)]
-    for _ in range(6):
-        a, b = (int(t) for t in r.choice(big, 2))
-        qs.append([a, b, a] if r.random() < 0.5 else [a, a])
-    qs += [r.integers(0, n, int(r.integers(2, 5))).tolist() for _ in range(24)]
-    qs += [r.choice(big, int(r.integers(2, 5))).tolist() for _ in range(10)]
-    qs += [r.choice(big[:6], int(r.integers(8, 33))).tolist() for _ in range(5)]
-    qs += [r.integers(0, n, int(r.integers(8, 33))).tolist() for _ in range(4)]
-    return [qs[i] for i in r.permutation(len(qs))]
-
-
-def draw_norm_lens(r, num_docs, cls):
-    nl = (r.random(num_docs) * 3 + 0.05).astype(np.float32)
-    if cls == "equal":  # mass ties
-        nl[:] = 1.0
-    elif cls == "zeros":
-        nl[r.random(num_docs) < 0.3] = 0.0
-    elif cls == "large":  # q_weight * w down to subnormal floats
-        big = r.random(num_docs) < 0.02
-        nl[big] = (10.0 ** r.uniform(30, 38.4, int(big.sum()))).astype(np.float32)
-    return nl
-
-
 def assert_ranked(got, want, what):
     assert np.array_equal(got[0], want[0]), what
     assert np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32)), what  # bit-equal scores
@@ -93,13 +62,10 @@ def run_query_case(device, case, setting=None):
     Dd, Df, X = F.build_query_case(case)
     pinned = GOLDEN["query"].get(str(case[0]))
     assert pinned is None or F.index_digest(Dd, Df, X) == pinned["digest"]
-    r = np.random.default_rng(case[0] + 17)
-    if setting is None:
-        setting = {k: int(r.choice(v)) for k, v in CHOICES.items()}
+    setting, qs, nl, ks = draw_case(case[0], X, setting)
     for k, v in setting.items():
         device.set_option(k, v)
     lens = np.diff(X.bounds)
-    qs = query_mix(r, lens)
     dd, fd = device.Dictionary(Dd.kind, Dd.file), device.Dictionary(Df.kind, Df.file)
     qi = device.QueryIndex(dd, X.index, X.offsets)
     uq = [np.unique(np.asarray(q, dtype=np.int64)) for q in qs]
@@ -119,16 +85,30 @@ def run_query_case(device, case, setting=None):
     assert nblocks == sum(int(((lens[t] + 255) // 256).sum()) for t in uq), setting
     # ranked AND / OR at two k, over norm_lens of one class
     num_docs = int(X.docids.max()) + 1
-    nl = draw_norm_lens(r, num_docs, NORM_LENS[int(r.integers(0, len(NORM_LENS)))])
     wand = device.WandData(nl)
     lists = ranked.BuilderLists(X.docids, X.freqs, X.bounds)
-    ks = [int(k) for k in r.choice(KS, 2, replace=False)]
     wants = {}
     for k in ks:
         for name, fn in (("ranked_and", ranked.ranked_and), ("ranked_or", ranked_or.ranked_or)):
             want = ranked_want(fn, lists, qs, nl, num_docs, k)
             assert_ranked(getattr(qi, name + "_queries")(fd, wand, qs, k=k), want, (name, k, setting))
             wants[name, k] = want
+    # pruned ranked OR: ranked OR's answer bit for bit, the blocks read those of the model; the call reversed and with every
+    # query twice changes no query's answer (claims are per query, even where two queries of a pass share an N term)
+    mtw = ranked.max_term_weights(X.docids, X.freqs, X.bounds, nl)
+    mwand = device.WandData(nl, max_term_weight=mtw)
+    models = {k: [maxscore.maxscore(lists, q, nl, mtw, num_docs, k) for q in qs] for k in ks}
+    for k in ks:
+        want, blocks = wants["ranked_or", k], sum(m.blocks_read for m in models[k])
+        got = qi.ranked_or_maxscore_queries(fd, mwand, qs, k=k)
+        assert_ranked(got[:3], want, ("ranked_or_maxscore", k, setting))
+        assert got[3] == blocks, ("ranked_or_maxscore blocks", k, setting)
+        got = qi.ranked_or_maxscore_queries(fd, mwand, qs[::-1], k=k)
+        assert_ranked(got[:3], tuple(a[::-1] for a in want), ("ranked_or_maxscore reversed", k, setting))
+        assert got[3] == blocks, ("ranked_or_maxscore reversed blocks", k, setting)
+        got = qi.ranked_or_maxscore_queries(fd, mwand, [q for q in qs for _ in range(2)], k=k)
+        assert_ranked(got[:3], tuple(np.repeat(a, 2, axis=0) for a in want), ("ranked_or_maxscore twice", k, setting))
+        assert got[3] == 2 * blocks, ("ranked_or_maxscore twice blocks", k, setting)
     # one query per call, on a sample
     sample = list(range(0, len(qs), 7))
     for i in sample:
@@ -141,6 +121,10 @@ def run_query_case(device, case, setting=None):
             k = ks[i % 2]
             want = tuple(a[i:i + 1] for a in wants[name, k])
             assert_ranked(getattr(qi, name + "_queries")(fd, wand, [q], k=k), want, (name, k, i))
+        k = ks[i % 2]
+        got = qi.ranked_or_maxscore_queries(fd, mwand, [q], k=k)
+        assert_ranked(got[:3], tuple(a[i:i + 1] for a in wants["ranked_or", k]), ("ranked_or_maxscore", k, i))
+        assert got[3] == models[k][i].blocks_read, ("ranked_or_maxscore blocks", k, i)
     # the lists as the oracle decodes them from the index bytes, on a sample
     ol = OracleLists(Dd.kind, Dd.file, Df.file, X.index, X.offsets)
     for i in sample:
@@ -148,8 +132,13 @@ def run_query_case(device, case, setting=None):
         for name, fn in (("ranked_and", ranked.ranked_and), ("ranked_or", ranked_or.ranked_or)):
             want = ranked_want(fn, ol, [qs[i]], nl, num_docs, ks[0])
             assert_ranked(tuple(a[i:i + 1] for a in wants[name, ks[0]]), want, (name, "oracle", i))
+        m = maxscore.maxscore(ol, qs[i], nl, mtw, num_docs, ks[0])
+        assert_ranked(tuple(a[i:i + 1] for a in wants["ranked_or", ks[0]]),
+                      (np.array([m.count], dtype=np.uint64), m.scores[None], m.ids[None]), ("ranked_or_maxscore", "oracle", i))
+        assert m.blocks_read == models[ks[0]][i].blocks_read, ("ranked_or_maxscore blocks", "oracle", i)
     qi.close()
     wand.close()
+    mwand.close()
 
 
 @pytest.mark.parametrize("case", QUERY, ids=lambda c: f"seed{c[0]}")

@@ -54,6 +54,15 @@ def test_argument_errors_need_no_device():
     assert create(0, nl.ctypes.data, 4, None, 3, C.byref(out)) == DINT_ERR_ARG  # maxima of 3 lists, none given
     assert create(0, nl.ctypes.data, 4, nl.ctypes.data, 3, None) == DINT_ERR_ARG
     assert not out.value
+    # a NaN or negative maximum, anywhere in the array: refused before the device is looked for (no std::sort over NaNs later)
+    for bad in (np.nan, -np.nan, -1.0, -np.inf, -1e-45):
+        for at in range(3):
+            mw = np.array([0.5, 0.25, 1.0], dtype=np.float32)
+            mw[at] = bad
+            out = C.c_void_p(8)
+            assert create(0, nl.ctypes.data, 4, mw.ctypes.data, 3, C.byref(out)) == DINT_ERR_ARG
+            assert not out.value
+    assert create(0, None, 0, np.array([np.nan], dtype=np.float32).ctypes.data, 1, C.byref(out)) == DINT_ERR_ARG
 
 
 class Model:
@@ -131,3 +140,153 @@ def test_ties_with_theta_are_kept_in_docid_order():
     for k in (1, 10, 100, 101, 200):
         mod.check([0, 1], k)
         mod.check([1, 0, 1], k)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the query fuzz plan (tests/test_gpu_query_fuzz.py's run_query_case) replayed on the model: the draws are the GPU test's
+# own (tests/query_fuzz_draws.py). The floors are conditions of the plan: thin the plan or the mix until the pruned
+# path idles and this test fails, whatever the device does.
+# ---------------------------------------------------------------------------------------------------------------
+import fuzz_streams as F  # noqa: E402
+from query_fuzz_draws import draw_case  # noqa: E402
+from test_fuzz_cpu import GOLDEN, QUERY  # noqa: E402
+
+PLAN_FLOORS = {"non_empty_n": 250, "fewer_blocks": 200, "kth_is_theta": 200, "theta_zero": 100}
+CASE_FLOOR_NON_EMPTY_N = 5
+
+
+def plan_case_stats(case):
+    """One case of the plan through the model, every (query, k) bit for bit against ranked_or -> its counts."""
+    _, _, X = F.build_query_case(case)
+    _, qs, nl, ks = draw_case(case[0], X)
+    num_docs = int(X.docids.max()) + 1
+    mod = Model(X.docids, X.freqs, X.bounds, num_docs=num_docs, norm_lens=nl)
+    st = dict.fromkeys(("pairs", "pruned", *PLAN_FLOORS), 0)
+    for k in ks:
+        for q in qs:
+            got = mod.check(q, k)
+            n_terms = np.unique(np.asarray(q, dtype=np.int64)).size
+            st["pairs"] += 1
+            st["pruned"] += got.candidates.size < got.union.size
+            st["non_empty_n"] += got.n_essential < n_terms
+            st["fewer_blocks"] += got.blocks_read < got.all_blocks
+            st["kth_is_theta"] += int(got.count == k and np.float32(got.theta) == got.scores[k - 1])
+            st["theta_zero"] += n_terms > 0 and got.union.size > 0 and got.theta == 0.0
+    return st
+
+
+@pytest.fixture(scope="module")
+def plan_stats():
+    return {}
+
+
+@pytest.mark.parametrize("case", QUERY, ids=lambda c: f"seed{c[0]}")
+def test_the_fuzz_plan_case_on_the_model(case, plan_stats):
+    assert str(case[0]) in GOLDEN["query"]
+    st = plan_case_stats(case)
+    print(f"seed {case[0]}: {st}")
+    assert st["pairs"] == 2 * 60
+    assert st["non_empty_n"] >= CASE_FLOOR_NON_EMPTY_N, st
+    plan_stats[case[0]] = st
+
+
+def test_the_fuzz_plan_drives_the_pruning(plan_stats):
+    """Over the whole plan (measured when the floors were set: 1440 pairs, 1151 with a pruned document, 343 with a non-empty
+    N, 307 reading fewer blocks, 295 with the k-th score equal to theta, 186 with theta 0)."""
+    for case in QUERY:  # (a run of this test alone)
+        if case[0] not in plan_stats:
+            plan_stats[case[0]] = plan_case_stats(case)
+    total = {key: sum(st[key] for st in plan_stats.values()) for key in next(iter(plan_stats.values()))}
+    print(f"plan: {total}")
+    assert total["pairs"] == 120 * len(QUERY)
+    for key, floor in PLAN_FLOORS.items():
+        assert total[key] >= floor, (key, total)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the hand-made edges (tests/maxscore_edges.py): the model against what every query does by construction
+# ---------------------------------------------------------------------------------------------------------------
+import maxscore_edges as E  # noqa: E402
+
+
+def _check_spec(spec):
+    mod = Model(spec.docids, spec.all_freqs, spec.bounds, num_docs=spec.num_docs, norm_lens=spec.nl)
+    out = []
+    for q in spec.queries:
+        mod.check(q.terms, q.k)
+        out.append(spec.check_model(q))
+    return out
+
+
+@pytest.mark.parametrize("k,equal", E.LENGTH_CASES, ids=lambda v: str(v))
+def test_list_lengths_on_k(k, equal):
+    out = _check_spec(E.lengths_on_k(k, equal))
+    assert out[0].n_essential == 1 and out[0].blocks_read < out[0].all_blocks  # (the rare seed alone is essential)
+
+
+def test_seed_ties_go_to_the_smaller_term_id():
+    spec = E.seed_ties()
+    out = _check_spec(spec)
+    # the two choices differ where they can be seen: theta, and with it the blocks read
+    assert out[0].theta > out[2].theta and out[0].blocks_read < out[2].blocks_read
+    assert out[0].blocks_read == out[1].blocks_read and out[2].blocks_read == out[3].blocks_read
+
+
+def test_a_seed_with_theta_zero_prunes_nothing_and_counts_the_zero_score():
+    spec = E.zero_theta()
+    out = _check_spec(spec)
+    assert [m.theta == 0.0 for m in out] == [True] * 5 + [False]
+    assert out[3].count == 256 and out[3].scores[255] == 0.0 and out[3].ids[255] == spec.zero_doc
+
+
+def test_a_subnormal_theta():
+    out = _check_spec(E.subnormal_theta())
+    tiny = float(np.finfo(np.float32).tiny)
+    assert sum(0.0 < m.theta < tiny for m in out) >= 5, [m.theta for m in out]
+
+
+def test_claim_geometry():
+    out = _check_spec(E.claim_geometry())
+    assert all(m.n_essential < len(set(q.terms)) for m, q in zip(out, E.claim_geometry().queries))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# maxima other than the exact ones, on the model: any upper bounds give ranked_or's answer (mod.check asserts it) and
+# +inf reads every block; under-estimates only drop documents (maxscore.assert_degraded), and do drop some
+# ---------------------------------------------------------------------------------------------------------------
+def _maxima_case(which, request):
+    if which == "small_corpus":
+        ix = get_index(request.getfixturevalue(which), host.SINGLE_PACKED)
+        mod = _model(ix)
+        qs = reference_queries(len(ix.lens))[:40] + heavy_queries(ix.lens, 10) + maxscore.mixed_queries(ix.lens, 20)
+        return mod, qs, (10, 257)
+    case = QUERY[which]
+    _, _, X = F.build_query_case(case)
+    _, qs, nl, ks = draw_case(case[0], X)
+    return Model(X.docids, X.freqs, X.bounds, num_docs=int(X.docids.max()) + 1, norm_lens=nl), qs, (10, ks[0])
+
+
+@pytest.mark.parametrize("which", list(E.MAXIMA_FUZZ_CASES) + ["small_corpus"], ids=str)
+def test_maxima_other_than_the_exact_ones_on_the_model(which, request):
+    mod, qs, ks = _maxima_case(which, request)
+    exact = mod.mtw
+    for k in ks:
+        want = [ranked_or.ranked_or(mod.lists, q, mod.nl, mod.num_docs, k) for q in qs]
+        for name, mtw in E.upper_bounds(exact).items():
+            mod.mtw = mtw
+            for q in qs:
+                got = mod.check(q, k)
+                if name == "inf":
+                    assert got.blocks_read == got.all_blocks and got.n_essential == np.unique(np.asarray(q, dtype=np.int64)).size
+        for name, mtw in E.under_estimates(exact).items():
+            mod.mtw = mtw
+            differ = 0
+            for q, w in zip(qs, want):
+                got = maxscore.maxscore(mod.lists, q, mod.nl, mtw, mod.num_docs, k)
+                maxscore.assert_degraded(got.count, got.scores, got.ids, got, int(w[0]))
+                assert got.blocks_read <= got.all_blocks
+                differ += not (got.count == w[0] and np.array_equal(got.ids, w[2]))
+            print(f"{which}, k = {k}, {name}: {differ} of {len(qs)} answers differ from ranked_or's")
+            if name == "zeros":
+                assert differ > 0, "the under-estimates do drop documents here"
+    mod.mtw = exact
