@@ -2,7 +2,8 @@
 // launches. ONE translation unit (the kernels are templates in headers; the handles are shared): its parts live under
 // host/ by subsystem and are included here in order — common helpers and handles first, then the extern "C" block
 // (opened in host/hip_api_common.inc, closed at the end of this file): dictionary, vroom decode, in-index decode,
-// AND, OR, ranked AND, ranked OR and pruned ranked OR queries, statistics, host-pointer calls, list cache.
+// AND, OR, ranked AND, ranked OR and pruned ranked OR queries, scores of given documents, statistics, host-pointer calls,
+// list cache.
 #include "dint_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -30,6 +31,7 @@
 #include "dint_ranked_query_kernels.hpp"
 #include "dint_ranked_or_query_kernels.hpp"
 #include "dint_ranked_or_maxscore_kernels.hpp"
+#include "dint_score_documents_kernels.hpp"
 #include "dint_stats_kernels.hpp"
 
 #include "host/hip_common.inc"
@@ -45,6 +47,7 @@
 #include "host/hip_api_ranked_query.inc"
 #include "host/hip_api_ranked_or_query.inc"
 #include "host/hip_api_ranked_or_maxscore.inc"
+#include "host/hip_api_score_documents.inc"
 #include "host/hip_api_stats.inc"
 #include "host/hip_api_host_calls.inc"
 #include "host/hip_api_list_cache.inc"

@@ -36,7 +36,7 @@ ABI_SYMBOLS = (
     "dint_block_table_create", "dint_block_table_destroy", "dint_block_table_learn", "dint_block_table_ready", "dint_block_table_info_get", "dint_decode_block_table",
     "dint_query_index_create", "dint_query_index_destroy", "dint_and_queries", "dint_and_queries_freqs", "dint_or_queries", "dint_or_queries_freqs",
     "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_or_queries",
-    "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
+    "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
 
 #: dint_block_ref (include/dint_hip.h)
@@ -131,6 +131,7 @@ def _load():
     lib.dint_ranked_or_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_count_ngrams.argtypes = [C.c_int, C.c_int, vp, u64, vp, u64, C.c_uint32, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_float)]
     lib.dint_select_ngrams.argtypes = [C.c_int, vp, u64, u64, vp, sz, C.c_uint32, C.POINTER(sz)]
     lib.dint_debug_wave_scan.argtypes = [vp, vp]
@@ -616,6 +617,31 @@ class QueryIndex:
                                                     counts.ctypes.data, scores.ctypes.data, docids.ctypes.data, C.byref(blocks),
                                                     self._stream()), "dint_ranked_or_maxscore_queries")
         return counts, scores, docids, blocks.value
+
+    def score_documents(self, freqs_dict: "Dictionary", wand: "WandData", queries, docs, with_freqs: bool = False):
+        """next_geq(d) + freq() (include/dint/dict_posting_list.hpp:126-169) with ranked_or_query's sums, for documents the
+        caller names (dint_score_documents): docs[q] — any u32 docIDs, in any order, repeated or not — are
+        scored for queries[q] -> (scores: a list of f32 arrays, one per query, each the ranked_or_queries score of that
+        document, 0.0 if no list of the query holds it; freqs: with_freqs, a list of u32 [n_docs, T] arrays, T the query's
+        distinct terms in ascending id, 0 = not in the list, else None; blocks read: the distinct (term, block) pairs decoded)."""
+        assert len(docs) == len(queries)
+        terms, offs = _pack_queries(queries)
+        ids, doc_offs = _pack_queries(docs)
+        n = len(queries)
+        scores = np.zeros(max(1, ids.size), dtype=np.float32)
+        n_terms = [len(set(int(t) for t in q)) for q in queries]
+        sizes = [int(doc_offs[q + 1] - doc_offs[q]) * n_terms[q] for q in range(n)]
+        freqs = np.zeros(max(1, sum(sizes)), dtype=np.uint32) if with_freqs else None
+        blocks = C.c_uint64()
+        _check(_lib.dint_score_documents(self._h, freqs_dict._h, wand._h, terms.ctypes.data, offs.ctypes.data, n, ids.ctypes.data,
+                                         doc_offs.ctypes.data, scores.ctypes.data, freqs.ctypes.data if with_freqs else None,
+                                         C.byref(blocks), self._stream()), "dint_score_documents")
+        out = [scores[int(doc_offs[q]):int(doc_offs[q + 1])] for q in range(n)]
+        mats = None
+        if with_freqs:
+            at = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+            mats = [freqs[at[q]:at[q + 1]].reshape(int(doc_offs[q + 1] - doc_offs[q]), n_terms[q]) for q in range(n)]
+        return out, mats, blocks.value
 
 
 class WandData:

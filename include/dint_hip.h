@@ -490,6 +490,33 @@ int dint_ranked_or_maxscore_queries(dint_query_index* qi, const dint_dict* freqs
                                     const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts,
                                     float* scores, uint32_t* docids, uint64_t* blocks_read, void* stream);
 
+/* ---- BM25 scores and term frequencies of caller-given documents over the same query index -----------
+ * Replaces: the cursor primitive under every query, document_enumerator::next_geq(d) then freq()
+ * (include/dint/dict_posting_list.hpp:126-169), with ranked_or_query's sums (include/ds2i/queries.hpp:387-457), for a batch
+ * of (query, document set) pairs per call: "is document d in list t, with what frequency, and what does d score?".
+ * terms / query_offsets are as in every query call (repeated terms give qf; an empty query is legal). Query q's documents
+ * are docids[doc_offsets[q] .. doc_offsets[q + 1]) (HOST; doc_offsets has n_queries + 1 entries, non-decreasing): in any
+ * order, repeated or not, any u32 — a docID above the index's largest, 0xFFFFFFFF included, is in no list.
+ * scores (HOST, laid out like docids: scores[i] belongs to docids[i]): dint_ranked_or_queries' score of that document for
+ * that query, bit for bit — from 0.0f, for each distinct term in ascending term id whose list holds d,
+ * score = score + q_weight_t * doc_term_weight(freq_t(d), norm_lens[d]), binary32, uncontracted. A
+ * document in none of the query's lists scores 0.0f; norm_lens[d] is read only after a hit, so the wand handle need only
+ * cover the index's largest docID, as for the ranked calls (one created without max_term_weight will do).
+ * freqs (HOST, nullable: not wanted): for query q with T_q distinct terms, a row-major matrix [documents of q][T_q], the
+ * terms in ascending term id, 0 for "not in the list", otherwise freq(); the queries' matrices back to back in query order.
+ * *blocks_read (nullable) = the sum over the queries of the distinct (term, block) pairs whose docs and freqs parts the call
+ * decoded: a document claims, in each term of its query, the first block whose last docID is >= it, if there is one. No
+ * other block is read. The call runs in passes of whole queries of at most DINT_OPT_QUERY_OR_PASS_PAGES pages of the bound
+ * sum_t min(blocks of t, documents of q) (a larger query alone); a query without documents launches nothing. The handle's
+ * lock and the stream are as for dint_and_queries. DINT_ERR_ARG, before any device is touched: a null handle, null scores,
+ * null offsets with n_queries != 0, decreasing doc_offsets, more than 2^30 documents for one query, null docids with a
+ * document to score; then, before anything is launched: a freqs_dict of another kind or device than the docs dictionary, a
+ * wand handle on another device or one whose num_docs does not exceed the index's largest docID, decreasing
+ * query_offsets, a term >= n_lists. */
+int dint_score_documents(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, const uint32_t* terms,
+                         const uint64_t* query_offsets, size_t n_queries, const uint32_t* docids, const uint64_t* doc_offsets,
+                         float* scores, uint32_t* freqs, uint64_t* blocks_read, void* stream);
+
 /* ---- block statistics on the device (dictionary construction, counting half) ----------------------------
  * Counts every aligned 16/8/4/2/1-gram of the given lists — multi != 0: of their whole 256-integer blocks, per block
  * context — keyed by the MurmurHash64A of its integers, as the reference's collectors do.
