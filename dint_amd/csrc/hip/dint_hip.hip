@@ -1,9 +1,9 @@
 // C ABI of the device decode path (include/dint_hip.h): dictionary staging, the host indexing pre-pass, and the kernel
 // launches. ONE translation unit (the kernels are templates in headers; the handles are shared): its parts live under
-// host/ by subsystem and are included here in order — common helpers and handles first, then the extern "C" block
-// (opened in host/hip_api_common.inc, closed at the end of this file): dictionary, vroom decode, in-index decode,
-// AND, OR, ranked AND, ranked OR and pruned ranked OR queries, scores of given documents, statistics, host-pointer calls,
-// list cache.
+// host/ by subsystem and are included here in order — common helpers, handles and the query calls' staged layouts first,
+// then the extern "C" block (opened in host/hip_api_common.inc, closed at the end of this file): dictionary, vroom
+// decode, in-index decode, the query index and its page decodes, query planning, AND, OR, ranked AND, ranked OR and
+// pruned ranked OR queries, scores of given documents, statistics, host-pointer calls, list cache.
 #include "dint_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -37,12 +37,15 @@
 #include "host/hip_common.inc"
 #include "host/hip_handles.inc"
 #include "host/hip_dictionary.inc"
+#include "host/hip_stage_layout.inc"
 #include "host/hip_query_handle.inc"
 #include "host/hip_api_common.inc"
 #include "host/hip_api_dictionary.inc"
 #include "host/hip_api_vroom.inc"
 #include "host/hip_api_index.inc"
 #include "host/hip_api_query.inc"
+#include "host/hip_api_query_plan.inc"
+#include "host/hip_api_query_and.inc"
 #include "host/hip_api_or_query.inc"
 #include "host/hip_api_ranked_query.inc"
 #include "host/hip_api_ranked_or_query.inc"

@@ -25,25 +25,95 @@ static int plan_or_passes(const dint_query_index* qi, const uint32_t* terms, con
     op.pages.assign(n_queries, 0);
     op.all = 0;
     for (size_t q = 0; q != n_queries; ++q) {
-        for (uint32_t j = 0; j != plan.len[q]; ++j) {
-            const uint32_t l = plan.of(q)[j];
-            op.pages[q] += qi->list_first[l + 1] - qi->list_first[l];
-        }
+        for (uint32_t j = 0; j != plan.len[q]; ++j) op.pages[q] += qi->blocks_of(plan.of(q)[j]);
         if (op.pages[q] == 0) plan.len[q] = 0;  // (lists without a block)
         op.all += op.pages[q];
     }
-    const uint64_t limit = uint64_t(opt(DINT_OPT_QUERY_OR_PASS_PAGES));
-    op.first.assign(1, 0);
-    uint64_t in_pass = 0;
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (in_pass != 0 && in_pass + op.pages[q] > limit) {
-            op.first.push_back(q);
-            in_pass = 0;
-        }
-        in_pass += op.pages[q];
-    }
-    op.first.push_back(n_queries);
+    op.first = cut_passes(n_queries, {{op.pages.data(), uint64_t(opt(DINT_OPT_QUERY_OR_PASS_PAGES))}}, false);
     return DINT_OK;
+}
+
+// One pass: every block of the terms of its queries decoded, then ONE probe launch. A query of the pass as the pass
+// sees it: the id its records carry, its terms (longest list first) and, ranked, their multiplicities.
+struct or_pass_query {
+    uint32_t id, n;
+    const uint32_t *terms, *qf;
+};
+// The pass of `qs` on the stream: the inputs (or_pass_layout) staged — in an area
+// of at least min_stage bytes — and copied in, the pages' decode, and or_count_kernel, which adds to d_counts and the
+// sums behind them; or (rk) ranked_or_score_kernel over the union's representatives and ranked_topk, which selects the
+// best rk->k of the queries id0 .. id0 + n_ids - 1 into rk->keys. No wait.
+static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const ranked_args* rk, const std::vector<or_pass_query>& qs,
+                       size_t min_stage, unsigned long long* d_counts, size_t n_counts, uint32_t id0, size_t n_ids, hipStream_t s) {
+    uint64_t n_pages = 0, n_terms = 0;
+    for (const or_pass_query& q : qs) {
+        n_terms += q.n;
+        for (uint32_t j = 0; j != q.n; ++j) n_pages += qi->blocks_of(q.terms[j]);
+    }
+    const or_pass_layout L(n_pages, n_terms, rk != nullptr);
+    if (qi->stage(std::max<size_t>(L.words * 4, min_stage)) != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
+    uint32_t *page_block = qi->h(L.page_block), *page_term = qi->h(L.page_term), *term_order = qi->h(L.term_order);
+    std::vector<uint32_t> page_query(rk ? n_pages : 0);  // (ranked_topk's: the pass's queries, from 0)
+    uint32_t page = 0, rec = 0;
+    for (const or_pass_query& q : qs) {
+        const uint32_t from = rec;
+        if (rk) sort_records_by_term(term_order, from, q.n, q.terms);
+        for (uint32_t j = 0; j != q.n; ++j, ++rec) {
+            const uint32_t l = q.terms[j];
+            qi->h(L.term_first)[rec] = qi->list_first[l];
+            qi->h(L.term_blocks)[rec] = qi->blocks_of(l);
+            qi->h(L.term_page)[rec] = page;
+            qi->h(L.term_query)[rec] = q.id;
+            qi->h(L.term_from)[rec] = from;
+            if (rk) {
+                qi->h(L.term_n)[rec] = q.n;
+                qi->h<float>(L.term_weight)[rec] = bm25_query_term_weight(q.qf[j], qi->list_len[l], rk->num_docs);
+            }
+            for (uint32_t b = qi->list_first[l]; b != qi->list_first[l + 1]; ++b, ++page) {
+                page_block[page] = b;
+                page_term[page] = rec;
+                if (rk) page_query[page] = q.id - id0;
+            }
+        }
+    }
+    if (!qi->inputs.ensure(L.words) || !qi->sub.ensure(n_pages) || !qi->probe.ensure(n_pages * kPageSlots) ||
+        (freqs_dict && !qi->fprobe.ensure(n_pages * kPageSlots)))
+        return stream_failed(s, DINT_ERR_HIP);
+    HIP_TRY(hipMemcpyAsync(qi->inputs.p, qi->h_stage, L.words * 4, hipMemcpyHostToDevice, s));
+    const int st = gather_decode_pages(qi, qi->d(L.page_block), nullptr, n_pages, 0, freqs_dict, s);
+    if (st != DINT_OK) return stream_failed(s, st);
+    or_pass p{};
+    p.page_block = qi->d(L.page_block);
+    p.page_term = qi->d(L.page_term);
+    p.term_first = qi->d(L.term_first);
+    p.term_blocks = qi->d(L.term_blocks);
+    p.term_page = qi->d(L.term_page);
+    p.term_query = qi->d(L.term_query);
+    p.term_from = qi->d(L.term_from);
+    p.blocks = qi->d_blocks;
+    p.block_max = qi->d_block_max;
+    p.docs = qi->probe.p;
+    p.freqs = freqs_dict ? qi->fprobe.p : nullptr;
+    p.counts = d_counts;
+    p.freq_sums = d_counts + n_counts;
+    if (!rk) {
+        hipLaunchKernelGGL(or_count_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, p);
+        return hipGetLastError() != hipSuccess ? stream_failed(s, DINT_ERR_HIP) : DINT_OK;
+    }
+    // score the union's representatives, then select every query's best k
+    if (!qi->cand.ensure(n_pages * kPageSlots) || !qi->slot_score.ensure(n_pages * kPageSlots)) return stream_failed(s, DINT_ERR_HIP);
+    ranked_or_pass rp{};
+    rp.base = p;
+    rp.term_order = qi->d(L.term_order);
+    rp.term_n = qi->d(L.term_n);
+    rp.term_weight = qi->d<const float>(L.term_weight);
+    rp.norm_lens = rk->norm_lens;
+    rp.cand = qi->cand.p;
+    rp.score = qi->slot_score.p;
+    hipLaunchKernelGGL(ranked_or_score_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, rp);
+    if (hipGetLastError() != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
+    const int rst = ranked_topk(qi, *rk, page_query, n_ids, s);
+    return rst != DINT_OK ? stream_failed(s, rst) : DINT_OK;
 }
 
 static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
@@ -57,9 +127,6 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     const int planned = plan_or_passes(qi, terms, query_offsets, n_queries, rk != nullptr, freqs_dict != nullptr, counts, freq_sums, op);
     if (planned != DINT_OK) return planned;
     const query_plan& plan = op.plan;
-    const std::vector<uint64_t>& plan_pages = op.pages;
-    const std::vector<size_t>& pass_first = op.first;
-    auto list_blocks = [&](uint32_t l) { return uint64_t(qi->list_first[l + 1] - qi->list_first[l]); };
     if (op.all == 0) return DINT_OK;
 
     std::lock_guard<std::mutex> lock(qi->mutex);
@@ -68,101 +135,23 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     // the call's counters: counts[n_queries] then freq sums[n_queries], cleared once, added to by every pass
     if (!qi->freq_sums.ensure(2 * n_queries)) return DINT_ERR_HIP;
     unsigned long long* const d_counts = qi->freq_sums.p;
-    unsigned long long* const d_sums = d_counts + n_queries;
     HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * n_queries * sizeof(unsigned long long), s));
-    auto failed = [&](int st) {
-        (void)hipStreamSynchronize(s);
-        return st;
-    };
-    for (size_t k = 0; k + 1 < pass_first.size(); ++k) {
-        const size_t q0 = pass_first[k], q1 = pass_first[k + 1];
-        uint64_t n_pages = 0, n_terms = 0;
+    std::vector<or_pass_query> qs;
+    for (size_t k = 0; k + 1 < op.first.size(); ++k) {
+        const size_t q0 = op.first[k], q1 = op.first[k + 1];
+        uint64_t n_pages = 0;
+        qs.clear();
         for (size_t q = q0; q != q1; ++q) {
-            n_pages += plan_pages[q];
-            n_terms += plan.len[q];
+            n_pages += op.pages[q];
+            qs.push_back({uint32_t(q), plan.len[q], plan.of(q), rk ? plan.qf_of(q) : nullptr});
         }
         if (n_pages == 0) continue;
-        // inputs: page -> block, page -> term record, then per term record {first block, blocks, first page, query, from}
-        // (rk: and {the records of its query by term id, its query's terms, q_weight})
-        const size_t words = 2 * n_pages + (rk ? 8 : 5) * n_terms;
         if (k != 0) HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area)
-        if (qi->stage(std::max<size_t>(words * 4, 2 * n_queries * sizeof(unsigned long long))) != hipSuccess) return failed(DINT_ERR_HIP);
-        uint32_t* const h = static_cast<uint32_t*>(qi->h_stage);
-        uint32_t *page_block = h, *page_term = h + n_pages, *term_first = h + 2 * n_pages, *term_blocks = term_first + n_terms,
-                 *term_page = term_blocks + n_terms, *term_query = term_page + n_terms, *term_from = term_query + n_terms,
-                 *term_order = term_from + n_terms, *term_n = term_order + n_terms;
-        float* const term_weight = reinterpret_cast<float*>(term_n + n_terms);
-        uint32_t page = 0, rec = 0;
-        for (size_t q = q0; q != q1; ++q) {
-            const uint32_t from = rec;
-            if (rk) {  // the query's records by ascending term id: the order its scores are summed in
-                for (uint32_t j = 0; j != plan.len[q]; ++j) term_order[from + j] = from + j;
-                std::sort(term_order + from, term_order + from + plan.len[q],
-                          [&](uint32_t a, uint32_t b) { return plan.of(q)[a - from] < plan.of(q)[b - from]; });
-            }
-            for (uint32_t j = 0; j != plan.len[q]; ++j, ++rec) {
-                const uint32_t l = plan.of(q)[j];
-                term_first[rec] = qi->list_first[l];
-                term_blocks[rec] = uint32_t(list_blocks(l));
-                term_page[rec] = page;
-                term_query[rec] = uint32_t(q);
-                term_from[rec] = from;
-                if (rk) {
-                    term_n[rec] = plan.len[q];
-                    term_weight[rec] = bm25_query_term_weight(plan.qf_of(q)[j], qi->list_len[l], rk->num_docs);
-                }
-                for (uint32_t b = qi->list_first[l]; b != qi->list_first[l + 1]; ++b, ++page) {
-                    page_block[page] = b;
-                    page_term[page] = rec;
-                }
-            }
-        }
-        if (!qi->inputs.ensure(words) || !qi->sub.ensure(n_pages) || !qi->probe.ensure(n_pages * kPageSlots) ||
-            (freqs_dict && !qi->fprobe.ensure(n_pages * kPageSlots)))
-            return failed(DINT_ERR_HIP);
-        uint32_t* const d_in = qi->inputs.p;
-        HIP_TRY(hipMemcpyAsync(d_in, h, words * 4, hipMemcpyHostToDevice, s));
-        const uint32_t tb = 256;
-        hipLaunchKernelGGL(gather_pages_kernel, dim3(uint32_t((n_pages + tb - 1) / tb)), dim3(tb), 0, s, qi->d_blocks, d_in, n_pages,
-                           qi->sub.p, static_cast<const uint32_t*>(nullptr));
-        const int st = decode_pages(qi, n_pages, qi->probe.p, freqs_dict, freqs_dict ? qi->fprobe.p : nullptr, s);
-        if (st != DINT_OK) return failed(st);
-        or_pass p{};
-        p.page_block = d_in;
-        p.page_term = d_in + n_pages;
-        p.term_first = d_in + 2 * n_pages;
-        p.term_blocks = p.term_first + n_terms;
-        p.term_page = p.term_blocks + n_terms;
-        p.term_query = p.term_page + n_terms;
-        p.term_from = p.term_query + n_terms;
-        p.blocks = qi->d_blocks;
-        p.block_max = qi->d_block_max;
-        p.docs = qi->probe.p;
-        p.freqs = freqs_dict ? qi->fprobe.p : nullptr;
-        p.counts = d_counts;
-        p.freq_sums = d_sums;
-        if (rk) {  // score the union's representatives, then select every query's best k (one query: one pass)
-            if (!qi->cand.ensure(n_pages * kPageSlots) || !qi->slot_score.ensure(n_pages * kPageSlots)) return failed(DINT_ERR_HIP);
-            ranked_or_pass rp{};
-            rp.base = p;
-            rp.term_order = p.term_from + n_terms;
-            rp.term_n = rp.term_order + n_terms;
-            rp.term_weight = reinterpret_cast<const float*>(rp.term_n + n_terms);
-            rp.norm_lens = rk->norm_lens;
-            rp.cand = qi->cand.p;
-            rp.score = qi->slot_score.p;
-            hipLaunchKernelGGL(ranked_or_score_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, rp);
-            if (hipGetLastError() != hipSuccess) return failed(DINT_ERR_HIP);
-            std::vector<uint32_t> page_query(n_pages);  // (the pass's queries, from 0)
-            for (uint64_t pg = 0; pg != n_pages; ++pg) page_query[pg] = term_query[page_term[pg]] - uint32_t(q0);
-            ranked_args pass_rk = *rk;
-            pass_rk.keys = rk->keys + uint64_t(q0) * rk->k;
-            const int rst = ranked_topk(qi, pass_rk, page_query, q1 - q0, s);
-            if (rst != DINT_OK) return failed(rst);
-            continue;
-        }
-        hipLaunchKernelGGL(or_count_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, p);
-        if (hipGetLastError() != hipSuccess) return failed(DINT_ERR_HIP);
+        ranked_args pass_rk = rk ? *rk : ranked_args{};
+        if (rk) pass_rk.keys += uint64_t(q0) * rk->k;  // (the keys of the pass's queries at their own offset)
+        const int st = or_run_pass(qi, freqs_dict, rk ? &pass_rk : nullptr, qs, 2 * n_queries * sizeof(unsigned long long), d_counts,
+                                   n_queries, uint32_t(q0), q1 - q0, s);
+        if (st != DINT_OK) return st;
     }
     HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area: the results go there)
     if (rk) return DINT_OK;            // (ranked: the keys are already on the host)
@@ -175,7 +164,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
             counts[q] = h_res[q];
             if (freqs_dict) {
                 freq_sums[q] = h_res[n_queries + q];
-                if (freq_blocks) *freq_blocks += plan_pages[q];
+                if (freq_blocks) *freq_blocks += op.pages[q];
             }
         }
     return DINT_OK;

@@ -1,0 +1,114 @@
+// Part of dint_hip.hip (one translation unit; included from there, in order): what the query calls plan before they take the lock.
+// ---- query planning -----------------------------------------------------------------------------
+
+// Per query: its distinct terms (queries.hpp:28-31, 49-52, 92) by list length, ascending (AND: the rarest list first) or
+// descending (OR: the longest list probes nothing), equal lengths by term id, and (with_qf) each term's multiplicity
+// beside it (query_freqs, queries.hpp:135-148). One flat copy of the call's terms, every query's part planned in place
+// (a vector per query was an allocation per query: a third of a batch call's host time).
+struct query_plan {
+    const uint64_t* offsets = nullptr;
+    uint64_t first = 0;
+    std::vector<uint32_t> terms, qf;
+    std::vector<uint32_t> len;  // planned terms of query q; 0: none, or nothing to launch (one list, counted on the host)
+    const uint32_t* of(size_t q) const { return terms.data() + (offsets[q] - first); }
+    const uint32_t* qf_of(size_t q) const { return qf.data() + (offsets[q] - first); }
+};
+
+// Checks the offsets and every term before anything is written (DINT_ERR_ARG), then plans the queries: counts[q] and
+// freq_sums[q] (if given) <- 0, and without freqs a query of one list is answered here, counts[q] <- the list's length.
+static int plan_queries(const dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries,
+                        bool longest_first, bool with_qf, bool with_freqs, uint64_t* counts, uint64_t* freq_sums, query_plan& plan) {
+    if (query_offsets[0] != 0 && !terms) return DINT_ERR_ARG;
+    for (size_t q = 0; q != n_queries; ++q)
+        if (query_offsets[q + 1] < query_offsets[q] || (query_offsets[q + 1] > query_offsets[q] && !terms)) return DINT_ERR_ARG;
+    const uint64_t t_first = query_offsets[0], t_all = query_offsets[n_queries] - t_first;
+    for (uint64_t i = 0; i != t_all; ++i)
+        if (terms[t_first + i] >= qi->list_len.size()) return DINT_ERR_ARG;
+    plan.offsets = query_offsets;
+    plan.first = t_first;
+    plan.terms.assign(terms ? terms + t_first : nullptr, terms ? terms + t_first + t_all : nullptr);
+    plan.qf.assign(with_qf ? t_all : 0, 0u);
+    plan.len.assign(n_queries, 0u);
+    const uint32_t* const len = qi->list_len.data();
+    for (size_t q = 0; q != n_queries; ++q) {
+        uint32_t* const t = plan.terms.data() + (query_offsets[q] - t_first);
+        uint32_t* const qf = with_qf ? plan.qf.data() + (query_offsets[q] - t_first) : nullptr;
+        // (equal terms end up side by side in this order: one pass drops them and counts them)
+        std::sort(t, t + (query_offsets[q + 1] - query_offsets[q]), [&](uint32_t a, uint32_t b) {
+            return len[a] != len[b] ? (longest_first ? len[a] > len[b] : len[a] < len[b]) : a < b;
+        });
+        uint32_t n = 0;
+        for (uint64_t i = 0; i != query_offsets[q + 1] - query_offsets[q]; ++i) {
+            if (n != 0 && t[i] == t[n - 1]) {
+                if (qf) qf[n - 1] += 1;
+                continue;
+            }
+            if (qf) qf[n] = 1;
+            t[n++] = t[i];
+        }
+        counts[q] = 0;
+        if (freq_sums) freq_sums[q] = 0;
+        if (n == 1 && !with_freqs)  // one list: every posting is a result (and_query<false> would walk it and count)
+            counts[q] = len[t[0]];
+        else
+            plan.len[q] = n;
+    }
+    return DINT_OK;
+}
+
+// dint_ranked_and_queries (hip_api_ranked_query.inc), dint_ranked_or_queries: what the freqs pass scores with, and where
+// the selection goes
+struct ranked_args {
+    const float* norm_lens;    // device, the wand handle's
+    uint32_t k;
+    unsigned long long* keys;  // host, n_queries * k: the best keys of every query (ranked_topk)
+    uint64_t num_docs;         // the wand handle's
+};
+// bm25::query_term_weight (bm25.hpp), binary32 in its source order: qf = the term's multiplicity, df = its list's length
+static float bm25_query_term_weight(uint32_t qf, uint64_t df, uint64_t num_docs) {
+    const float f = float(qf);
+    const float fdf = float(df);
+    const float idf = std::log((float(num_docs) - fdf + 0.5f) / (fdf + 0.5f));
+    const float epsilon_score = 1.0E-6f;
+    return f * std::max(epsilon_score, idf) * (1.0f + kBm25K1);
+}
+static int ranked_topk(dint_query_index* qi, const ranked_args& rk, const std::vector<uint32_t>& page_query, size_t n_queries,
+                       hipStream_t s);
+
+// the *_queries_freqs entries: a freqs dictionary of the index's device and kind, and somewhere for the sums
+static bool freqs_args_ok(const dint_query_index* qi, const dint_dict* freqs_dict, const uint64_t* freq_sums) {
+    return freqs_dict && freq_sums && (!qi || (freqs_dict->device == qi->docs->device && freqs_dict->kind == qi->docs->kind));
+}
+
+// order[from .. from + n) <- the records from .. from + n - 1 of one query (record from + j: term t[j]) by ascending term
+// id: the order its scores are summed in
+static void sort_records_by_term(uint32_t* order, uint32_t from, uint32_t n, const uint32_t* t) {
+    for (uint32_t j = 0; j != n; ++j) order[from + j] = from + j;
+    std::sort(order + from, order + from + n, [&](uint32_t a, uint32_t b) { return t[a - from] < t[b - from]; });
+}
+
+// A call cut into passes of whole queries: pass k is the queries [first[k], first[k + 1]). Every size of a pass stays
+// within its limit — but a query larger than a limit is a pass alone, sized to it. skip_empty: a query whose sizes are
+// all zero never begins a pass.
+struct pass_size {
+    const uint64_t* of;  // per query
+    uint64_t limit;
+};
+static std::vector<size_t> cut_passes(size_t n_queries, std::initializer_list<pass_size> sizes, bool skip_empty) {
+    const pass_size* const sz = sizes.begin();
+    const size_t n = sizes.size();
+    std::vector<size_t> first(1, 0);
+    uint64_t in_pass[4] = {0, 0, 0, 0};  // (per size: at most four)
+    for (size_t q = 0; q != n_queries; ++q) {
+        bool empty = true, cut = false;
+        for (size_t i = 0; i != n; ++i) {
+            empty = empty && sz[i].of[q] == 0;
+            cut = cut || (in_pass[i] != 0 && in_pass[i] + sz[i].of[q] > sz[i].limit);
+        }
+        if (skip_empty && empty) continue;
+        if (cut) first.push_back(q);
+        for (size_t i = 0; i != n; ++i) in_pass[i] = (cut ? 0 : in_pass[i]) + sz[i].of[q];
+    }
+    first.push_back(n_queries);
+    return first;
+}

@@ -11,20 +11,11 @@ int dint_ranked_or_queries(dint_query_index* qi, const dint_dict* freqs_dict, co
                            uint32_t* docids, void* stream) {
     if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores)) return DINT_ERR_ARG;
     std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    ranked_args rk{};
-    rk.norm_lens = wd->d_norm_lens;
-    rk.k = k;
-    rk.keys = keys.data();
-    rk.num_docs = wd->num_docs;
+    const ranked_args rk = ranked_args_of(wd, k, keys.data());
     // (or_queries_impl checks the offsets and the terms before anything is launched)
     const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk);
     if (st != DINT_OK) return st;
-    for (size_t q = 0; q != n_queries; ++q) {
-        // every score is > 0: a query's keys are non-zero for its first min(k, |union|) and zero past them
-        uint64_t c = 0;
-        while (c != k && keys[q * k + c] != 0) ++c;
-        counts[q] = c;
-    }
+    counts_from_keys(keys, n_queries, k, counts);
     unpack_keys(keys, n_queries, k, counts, scores, docids);
     return DINT_OK;
 }

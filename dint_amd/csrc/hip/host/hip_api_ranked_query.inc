@@ -102,23 +102,22 @@ static int ranked_topk(dint_query_index* qi, const ranked_args& rk, const std::v
             for (uint64_t a = 0; a + half < runs[q]; a += 2 * half) tasks.push_back({uint32_t(q), uint32_t(a), uint32_t(a + half)});
         pass_first.push_back(tasks.size());
     }
-    // inputs: the tasks, then per query {first page, pages}, then the key bases (8-byte aligned)
-    const size_t task_words = tasks.size() * 3, base_at = (task_words + 2 * n_queries + 1) / 2 * 2;
-    const size_t words = base_at + 2 * n_queries;
-    std::vector<uint32_t> h(words, 0);
-    std::memcpy(h.data(), tasks.data(), task_words * 4);
-    std::memcpy(h.data() + task_words, q_page_first.data(), n_queries * 4);
-    std::memcpy(h.data() + task_words + n_queries, q_pages.data(), n_queries * 4);
-    std::memcpy(h.data() + base_at, key_base.data(), n_queries * 8);
-    if (!qi->topk_in.ensure(words) || !qi->topk_keys.ensure(std::max<uint64_t>(1, n_keys)) ||
+    // (the inputs, topk_layout, in pageable memory of this frame: hence the wait)
+    const topk_layout L(tasks.size(), n_queries);
+    std::vector<uint32_t> h(L.words, 0);
+    std::memcpy(staged(h.data(), L.tasks), tasks.data(), tasks.size() * sizeof(topk_task));
+    std::memcpy(staged(h.data(), L.page_first), q_page_first.data(), n_queries * 4);
+    std::memcpy(staged(h.data(), L.pages), q_pages.data(), n_queries * 4);
+    std::memcpy(staged(h.data(), L.key_base), key_base.data(), n_queries * 8);
+    if (!qi->topk_in.ensure(L.words) || !qi->topk_keys.ensure(std::max<uint64_t>(1, n_keys)) ||
         !qi->topk_out.ensure(uint64_t(n_queries) * rk.k))
         return DINT_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(qi->topk_in.p, h.data(), words * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));  // (h is pageable host memory of this frame)
-    const topk_task* const d_tasks = reinterpret_cast<const topk_task*>(qi->topk_in.p);
-    const uint32_t* const d_page_first = qi->topk_in.p + task_words;
-    const uint32_t* const d_pages = d_page_first + n_queries;
-    const unsigned long long* const d_base = reinterpret_cast<const unsigned long long*>(qi->topk_in.p + base_at);
+    HIP_TRY(hipMemcpyAsync(qi->topk_in.p, h.data(), L.words * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const topk_task* const d_tasks = staged<const topk_task>(qi->topk_in.p, L.tasks);
+    const uint32_t* const d_page_first = staged(qi->topk_in.p, L.page_first);
+    const uint32_t* const d_pages = staged(qi->topk_in.p, L.pages);
+    const unsigned long long* const d_base = staged<const unsigned long long>(qi->topk_in.p, L.key_base);
     const uint32_t tb = 256;
     for (size_t p = 0; p + 1 < pass_first.size(); ++p) {
         const size_t n_tasks = pass_first[p + 1] - pass_first[p];
@@ -148,6 +147,20 @@ static bool ranked_args_ok(const dint_query_index* qi, const dint_dict* freqs_di
     return n_queries < 0xFFFFFFFFull && uint64_t(n_queries) * k <= (uint64_t(1) << 32);
 }
 
+// what a ranked call scores with, from the wand handle; keys: where the selection goes
+static ranked_args ranked_args_of(const dint_wand_data* wd, uint32_t k, unsigned long long* keys) {
+    return ranked_args{wd->d_norm_lens, k, keys, wd->num_docs};
+}
+
+// the ranked OR calls' counts: every score is > 0, so a query's keys are non-zero for its first min(k, |union|) and zero past them
+static void counts_from_keys(const std::vector<unsigned long long>& keys, size_t n_queries, uint32_t k, uint64_t* counts) {
+    for (size_t q = 0; q != n_queries; ++q) {
+        uint64_t c = 0;
+        while (c != k && keys[q * k + c] != 0) ++c;
+        counts[q] = c;
+    }
+}
+
 // ranked_topk's keys (score bits, then the inverted docID; sorted descending) -> the first counts[q] scores and docIDs of
 // every query, 0.0f and 0xFFFFFFFF past them
 static void unpack_keys(const std::vector<unsigned long long>& keys, size_t n_queries, uint32_t k, const uint64_t* counts,
@@ -169,11 +182,7 @@ int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, c
     if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores)) return DINT_ERR_ARG;
     std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
     std::vector<uint64_t> freq_sums(n_queries, 0);
-    ranked_args rk{};
-    rk.norm_lens = wd->d_norm_lens;
-    rk.k = k;
-    rk.keys = keys.data();
-    rk.num_docs = wd->num_docs;
+    const ranked_args rk = ranked_args_of(wd, k, keys.data());
     // (and_queries_impl checks the offsets and the terms before anything is launched)
     const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk);
     if (st != DINT_OK) return st;

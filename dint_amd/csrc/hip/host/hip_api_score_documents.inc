@@ -34,44 +34,26 @@ int dint_score_documents(dint_query_index* qi, const dint_dict* freqs_dict, cons
     const int planned = plan_queries(qi, terms, query_offsets, n_queries, true, true, true, unused.data(), nullptr, plan);
     if (planned != DINT_OK) return planned;
     if (d_all == 0) return DINT_OK;
-    auto list_blocks = [&](uint32_t l) { return uint64_t(qi->list_first[l + 1] - qi->list_first[l]); };
-    auto docs_of = [&](size_t q) { return doc_offsets[q + 1] - doc_offsets[q]; };
-    // per query: its bound, its claim flags, where its freqs matrix begins; the passes
-    std::vector<uint64_t> bound(n_queries, 0), flags(n_queries, 0), freq_at(n_queries + 1, 0);
+    // per query: its documents, its bound, its claim flags, where its freqs matrix begins; the passes
+    std::vector<uint64_t> n_docs_of(n_queries, 0), bound(n_queries, 0), flags(n_queries, 0), freq_at(n_queries + 1, 0);
     for (size_t q = 0; q != n_queries; ++q) {
-        if (docs_of(q) != 0)
+        n_docs_of[q] = doc_offsets[q + 1] - doc_offsets[q];
+        if (n_docs_of[q] != 0)
             for (uint32_t j = 0; j != plan.len[q]; ++j) {
-                const uint64_t nb = list_blocks(plan.of(q)[j]);
-                bound[q] += std::min<uint64_t>(nb, docs_of(q));
+                const uint64_t nb = qi->blocks_of(plan.of(q)[j]);
+                bound[q] += std::min<uint64_t>(nb, n_docs_of[q]);
                 flags[q] += nb;
             }
-        freq_at[q + 1] = freq_at[q] + docs_of(q) * plan.len[q];
+        freq_at[q + 1] = freq_at[q] + n_docs_of[q] * plan.len[q];
     }
-    const uint64_t limit = uint64_t(opt(DINT_OPT_QUERY_OR_PASS_PAGES));
-    std::vector<size_t> pass_first(1, 0);
-    uint64_t in_pass = 0, in_flags = 0, in_docs = 0;
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (docs_of(q) == 0) continue;
-        if ((in_pass != 0 && in_pass + bound[q] > limit) || (in_flags != 0 && in_flags + flags[q] > kSdPassFlags) ||
-            (in_docs != 0 && in_docs + docs_of(q) > kSdPassDocs)) {
-            pass_first.push_back(q);
-            in_pass = in_flags = in_docs = 0;
-        }
-        in_pass += bound[q];
-        in_flags += flags[q];
-        in_docs += docs_of(q);
-    }
-    pass_first.push_back(n_queries);
+    const std::vector<size_t> pass_first = cut_passes(n_queries, {{bound.data(), uint64_t(opt(DINT_OPT_QUERY_OR_PASS_PAGES))},
+                                                                  {flags.data(), kSdPassFlags}, {n_docs_of.data(), kSdPassDocs}}, true);
     // (a pass indexes its flags and pages in 32 bits: a query's distinct terms have at most the index's blocks, < 2^32 - 1)
     const size_t n_passes = pass_first.size() - 1;
 
     std::lock_guard<std::mutex> lock(qi->mutex);
     HIP_TRY(hipSetDevice(qi->docs->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    auto failed = [&](int st) {
-        (void)hipStreamSynchronize(s);
-        return st;
-    };
     // the call's results: a score per document, the freqs matrices back to back, a touched count per pass
     const uint64_t n_freqs = freqs ? freq_at[n_queries] : 0;
     if (!qi->slot_score.ensure(d_all) || !qi->target.ensure(std::max<uint64_t>(1, n_freqs)) || !qi->ms_count.ensure(n_passes))
@@ -88,56 +70,46 @@ int dint_score_documents(dint_query_index* qi, const dint_dict* freqs_dict, cons
             n_rec += plan.len[q];
             B += bound[q];
             F += flags[q];
-            if (docs_of(q) != 0) most_terms = std::max(most_terms, plan.len[q]);
+            if (n_docs_of[q] != 0) most_terms = std::max(most_terms, plan.len[q]);
         }
-        // inputs: per record {first, blocks, flag, q_weight, order}, per query {from, n}, per document {query, docID}, then
-        // (8-byte aligned) per query where its freqs matrix begins, less the rows of the pass's documents before its own
-        const size_t w_rec = 5 * n_rec, w_q = 2 * nq, u64_at = (w_rec + w_q + 2 * size_t(n_docs) + 1) / 2 * 2;
-        const size_t words = u64_at + 2 * nq;
+        const score_documents_layout L(n_rec, nq, n_docs);
         if (k != 0) HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area)
-        if (qi->stage(words * 4) != hipSuccess) return failed(DINT_ERR_HIP);
-        uint32_t* const h = static_cast<uint32_t*>(qi->h_stage);
-        uint32_t *h_first = h, *h_blocks = h + n_rec, *h_flag = h_blocks + n_rec, *h_order = h_flag + 2 * n_rec;
-        float* const h_weight = reinterpret_cast<float*>(h_flag + n_rec);
-        uint32_t *h_qfrom = h + w_rec, *h_qn = h_qfrom + nq, *h_dq = h + w_rec + w_q, *h_did = h_dq + n_docs;
-        uint64_t* const h_freq_at = reinterpret_cast<uint64_t*>(h + u64_at);
+        if (qi->stage(L.words * 4) != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
+        uint32_t *h_blocks = qi->h(L.term_blocks), *h_order = qi->h(L.term_order), *h_dq = qi->h(L.doc_query);
         uint32_t rec = 0, flag = 0;
         uint64_t doc = 0;
         for (size_t q = q0; q != q1; ++q) {
             const uint32_t from = rec, n = plan.len[q];
             const uint32_t* t = plan.of(q);
-            h_qfrom[q - q0] = from;
-            h_qn[q - q0] = n;
-            h_freq_at[q - q0] = freq_at[q] - doc * n;  // (mod 2^64: the kernel adds the document's place in the pass times n)
+            qi->h(L.q_from)[q - q0] = from;
+            qi->h(L.q_n)[q - q0] = n;
+            qi->h<uint64_t>(L.q_freq_at)[q - q0] = freq_at[q] - doc * n;  // (mod 2^64: the kernel adds the document's place in the pass times n)
             for (uint32_t j = 0; j != n; ++j, ++rec) {
-                h_first[rec] = qi->list_first[t[j]];
-                h_blocks[rec] = uint32_t(list_blocks(t[j]));
-                h_flag[rec] = flag;
-                h_weight[rec] = bm25_query_term_weight(plan.qf_of(q)[j], qi->list_len[t[j]], wd->num_docs);
-                h_order[rec] = rec;
-                if (docs_of(q) != 0) flag += h_blocks[rec];
+                qi->h(L.term_first)[rec] = qi->list_first[t[j]];
+                h_blocks[rec] = qi->blocks_of(t[j]);
+                qi->h(L.term_flag)[rec] = flag;
+                qi->h<float>(L.term_weight)[rec] = bm25_query_term_weight(plan.qf_of(q)[j], qi->list_len[t[j]], wd->num_docs);
+                if (n_docs_of[q] != 0) flag += h_blocks[rec];
             }
-            // the query's records by ascending term id: the order its scores are summed in
-            std::sort(h_order + from, h_order + from + n, [&](uint32_t a, uint32_t b) { return t[a - from] < t[b - from]; });
-            for (uint64_t i = 0; i != docs_of(q); ++i, ++doc) h_dq[doc] = uint32_t(q - q0);
+            sort_records_by_term(h_order, from, n, t);
+            for (uint64_t i = 0; i != n_docs_of[q]; ++i, ++doc) h_dq[doc] = uint32_t(q - q0);
         }
-        std::memcpy(h_did, docids + doc_offsets[q0], n_docs * 4);
-        if (!qi->inputs.ensure(words) || !qi->ms_flag.ensure(std::max<uint64_t>(1, F)) || !qi->ms_rank.ensure(std::max<uint64_t>(1, F)) ||
+        std::memcpy(qi->h(L.doc_id), docids + doc_offsets[q0], n_docs * 4);
+        if (!qi->inputs.ensure(L.words) || !qi->ms_flag.ensure(std::max<uint64_t>(1, F)) || !qi->ms_rank.ensure(std::max<uint64_t>(1, F)) ||
             !qi->ms_touched.ensure(std::max<uint64_t>(1, B)))
-            return failed(DINT_ERR_HIP);
-        uint32_t* const d_in = qi->inputs.p;
-        HIP_TRY(hipMemcpyAsync(d_in, h, words * 4, hipMemcpyHostToDevice, s));
+            return stream_failed(s, DINT_ERR_HIP);
+        HIP_TRY(hipMemcpyAsync(qi->inputs.p, qi->h_stage, L.words * 4, hipMemcpyHostToDevice, s));
         score_documents_pass sp{};
-        sp.term_first = d_in;
-        sp.term_blocks = d_in + n_rec;
-        sp.term_flag = d_in + 2 * n_rec;
-        sp.term_weight = reinterpret_cast<const float*>(d_in + 3 * n_rec);
-        sp.term_order = d_in + 4 * n_rec;
-        sp.q_from = d_in + w_rec;
-        sp.q_n = sp.q_from + nq;
-        sp.doc_query = d_in + w_rec + w_q;
-        sp.doc_id = sp.doc_query + n_docs;
-        sp.q_freq_at = reinterpret_cast<const uint64_t*>(d_in + u64_at);
+        sp.term_first = qi->d(L.term_first);
+        sp.term_blocks = qi->d(L.term_blocks);
+        sp.term_flag = qi->d(L.term_flag);
+        sp.term_weight = qi->d<const float>(L.term_weight);
+        sp.term_order = qi->d(L.term_order);
+        sp.q_from = qi->d(L.q_from);
+        sp.q_n = qi->d(L.q_n);
+        sp.doc_query = qi->d(L.doc_query);
+        sp.doc_id = qi->d(L.doc_id);
+        sp.q_freq_at = qi->d<const uint64_t>(L.q_freq_at);
         sp.n_docs = uint32_t(n_docs);
         sp.blocks = qi->d_blocks;
         sp.block_max = qi->d_block_max;
@@ -150,18 +122,16 @@ int dint_score_documents(dint_query_index* qi, const dint_dict* freqs_dict, cons
         sp.freqs_out = freqs ? qi->target.p : nullptr;
         const uint32_t grid = uint32_t((n_docs + tb - 1) / tb);
         if (B != 0) {
-            if (!qi->sub.ensure(B) || !qi->probe.ensure(B * kPageSlots) || !qi->fprobe.ensure(B * kPageSlots)) return failed(DINT_ERR_HIP);
+            if (!qi->sub.ensure(B) || !qi->probe.ensure(B * kPageSlots) || !qi->fprobe.ensure(B * kPageSlots)) return stream_failed(s, DINT_ERR_HIP);
             HIP_TRY(hipMemsetAsync(qi->ms_flag.p, 0, F * 4, s));
             hipLaunchKernelGGL(sd_claim_kernel, dim3(grid, std::min<uint32_t>(most_terms, 1024)), dim3(tb), 0, s, sp);
-            hipLaunchKernelGGL(gather_pages_kernel, dim3(uint32_t((B + tb - 1) / tb)), dim3(tb), 0, s, qi->d_blocks, qi->ms_touched.p, B,
-                               qi->sub.p, static_cast<const uint32_t*>(sp.n_touched));
-            const int st = decode_pages(qi, B, qi->probe.p, freqs_dict, qi->fprobe.p, s);
-            if (st != DINT_OK) return failed(st);
+            const int st = gather_decode_pages(qi, qi->ms_touched.p, sp.n_touched, B, 0, freqs_dict, s);
+            if (st != DINT_OK) return stream_failed(s, st);
         }
         sp.docs = qi->probe.p;
         sp.freqs = qi->fprobe.p;
         hipLaunchKernelGGL(sd_score_kernel, dim3(grid), dim3(tb), 0, s, sp);
-        if (hipGetLastError() != hipSuccess) return failed(DINT_ERR_HIP);
+        if (hipGetLastError() != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     }
     std::vector<uint32_t> touched(n_passes, 0);
     HIP_TRY(hipMemcpyAsync(scores + d_first, qi->slot_score.p, d_all * sizeof(float), hipMemcpyDeviceToHost, s));

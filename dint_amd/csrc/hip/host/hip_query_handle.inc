@@ -1,4 +1,4 @@
-// Part of dint_hip.hip (one translation unit; included from there, in order): grow-only device workspaces; the query index handle.
+// Part of dint_hip.hip (one translation unit; included from there, in order): grow-only device workspaces; the query index handle; the launch of its decode kernels.
 namespace {
 template <class T>
 struct device_buffer {  // grow-only workspace, freed with its owner (on the current device: the owner sets it)
@@ -66,6 +66,12 @@ struct dint_query_index {
     device_buffer<uint32_t> ms_flag, ms_rank, ms_touched, ms_count;
     std::mutex mutex;
 
+    uint32_t blocks_of(uint32_t l) const { return list_first[l + 1] - list_first[l]; }
+    // a staged field (hip_stage_layout.inc) as the host fills it and as the kernels read it, from its one offset
+    template <class T = uint32_t>
+    T* h(size_t at) const { return staged<T>(h_stage, at); }
+    template <class T = uint32_t>
+    T* d(size_t at) const { return staged<T>(inputs.p, at); }
     // h_stage of at least `bytes` (grown by half again), d_stage the same memory as the kernels see it (null where it
     // cannot be mapped)
     hipError_t stage(size_t bytes) {
@@ -82,4 +88,27 @@ struct dint_query_index {
         return hipSuccess;
     }
 };
+
+namespace {
+// What every decode_*_query*_kernel launch starts from: the docs dictionary over the index. with_image false — lists of
+// fewer than 256 postings are one interpolative block each and need no dictionary: a query of such lists only (most of
+// a query log's) runs without the 88 KB LDS image — nothing reads it.
+decode_args query_decode_args(const dint_query_index* qi, bool with_image = true) {
+    decode_args a{};
+    a.dict = qi->docs->view;
+    a.enc = qi->d_index;
+    a.enc_bytes = qi->index_bytes;
+    if (!with_image) a.dict.hot_words = 0;
+    return a;
+}
+// ... and the launch: the LDS bytes of a's image, the single- or the multi-dictionary kernel
+template <class K, class... A>
+int query_decode_launch(const dint_query_index* qi, const decode_args& a, uint32_t grid, hipStream_t s, K single, K multi,
+                               const A&... args) {
+    const size_t lds_bytes = (size_t(a.dict.hot_words) + kClassTableWords + kWavesPerBlock * kScratchWords) * 4;
+    hipLaunchKernelGGL(qi->docs->kind == DINT_DICT_MULTI_PACKED ? multi : single, dim3(grid), dim3(kBlockThreads), lds_bytes, s, a, args...);
+    HIP_TRY(hipGetLastError());
+    return DINT_OK;
+}
+}  // namespace
 

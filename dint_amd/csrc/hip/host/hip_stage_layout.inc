@@ -1,0 +1,100 @@
+// Part of dint_hip.hip (one translation unit; included from there, in order): the staged input areas of the query calls, each laid out ONCE.
+// Plain C++, no HIP call and no allocation (tests/test_stage_layout.py compiles this file alone). A call stages what its
+// kernels read from the host in dint_query_index::h_stage and sends it to ::inputs in one copy: a layout takes the area's
+// fields in order and records each one's word offset; the host fills the field at h(at), the kernel's argument struct
+// gets d(at) (hip_query_handle.inc) — one offset, both addresses.
+struct stage_layout {
+    size_t words = 0;  // the total so far
+    // the next field: n words, at a multiple of `align` words (2: the field holds 8-byte values)
+    size_t take(size_t n, size_t align = 1) {
+        words = (words + align - 1) / align * align;
+        words += n;
+        return words - n;
+    }
+    // ... and a run of fields of n words each, in order
+    void take_each(std::initializer_list<size_t*> fields, size_t n) {
+        for (size_t* f : fields) *f = take(n);
+    }
+};
+// the field at word `at` of an area that begins at `base`
+template <class T = uint32_t>
+static inline T* staged(void* base, size_t at) {
+    return reinterpret_cast<T*>(static_cast<uint32_t*>(base) + at);
+}
+
+// The AND forms' tables: page -> block, page -> query, then per round and query the first block and the block count of
+// the round's list (n_tab = max(1, rounds * n_queries) each).
+struct and_tables_layout : stage_layout {
+    size_t page_block, page_query, term_first, term_blocks;
+    and_tables_layout(size_t n_pages, size_t n_tab) {
+        take_each({&page_block, &page_query}, n_pages);
+        take_each({&term_first, &term_blocks}, n_tab);
+    }
+};
+// The workgroup-per-query batch form: the tables; the result counters (u64 each; zeros, copied in with the tables); per
+// active query {query, first page, pages, steps}, then per active query {probe page, control word}.
+struct and_batch_layout : and_tables_layout {
+    size_t counts, qrec, qrec2;
+    and_batch_layout(size_t n_pages, size_t n_tab, size_t n_queries, size_t n_active) : and_tables_layout(n_pages, n_tab) {
+        counts = take(2 * n_queries, 4);
+        qrec = take(4 * n_active, 4);
+        qrec2 = take(2 * n_active);
+    }
+};
+// The general form: the tables and behind them — zeros, copied in with them: one copy instead of a copy and a clear —
+// every counter the call's launches count in (ctrl_words for the candidates and for every round) and the result counters
+// (u64 each); then the one-launch form's steps, 8-byte aligned (step_bytes = sizeof(fused_step)).
+struct and_general_layout : and_tables_layout {
+    size_t ctrl, counts, steps;
+    and_general_layout(size_t n_pages, size_t n_tab, size_t n_queries, size_t rounds, size_t ctrl_words, size_t step_bytes)
+        : and_tables_layout(n_pages, n_tab) {
+        ctrl = take((rounds + 1) * ctrl_words, 32);
+        counts = take(2 * n_queries);  // (ctrl_words is even: 8-byte aligned)
+        steps = take((rounds + 1) * ((step_bytes + 7) / 8 * 2), 2);
+    }
+};
+// An OR pass (and the pruned ranked call's seeds): page -> block, page -> term record, then per term record {first
+// block, blocks, first page, query, from} and, ranked, {the records of its query by term id, its query's terms, q_weight}.
+struct or_pass_layout : stage_layout {
+    size_t page_block, page_term, term_first, term_blocks, term_page, term_query, term_from, term_order = 0, term_n = 0, term_weight = 0;
+    or_pass_layout(size_t n_pages, size_t n_terms, bool ranked) {
+        take_each({&page_block, &page_term}, n_pages);
+        take_each({&term_first, &term_blocks, &term_page, &term_query, &term_from}, n_terms);
+        if (ranked) take_each({&term_order, &term_n, &term_weight}, n_terms);
+    }
+};
+// The pruned ranked call's main stage: per record {first, blocks, page, claimed, q_weight, order, E, query}, per query
+// {from, n, n_E, theta}, per candidate page {page, record}, the other E terms' blocks, then (8-byte aligned) per query
+// {rest, margin} (doubles).
+struct maxscore_layout : stage_layout {
+    size_t term_first, term_blocks, term_page, term_claimed, term_weight, term_order, term_e, rec_query;
+    size_t q_from, q_n, q_ne, q_theta, cpage_page, cpage_rec, rest_blocks, q_rest, q_margin;
+    maxscore_layout(size_t n_rec, size_t nq, size_t n_cpages, size_t n_rest) {
+        take_each({&term_first, &term_blocks, &term_page, &term_claimed, &term_weight, &term_order, &term_e, &rec_query}, n_rec);
+        take_each({&q_from, &q_n, &q_ne, &q_theta}, nq);
+        take_each({&cpage_page, &cpage_rec}, n_cpages);
+        rest_blocks = take(n_rest);
+        q_rest = take(2 * nq, 2);
+        q_margin = take(2 * nq);
+    }
+};
+// A pass of dint_score_documents: per record {first, blocks, flag, q_weight, order}, per query {from, n}, per document
+// {query, docID}, then (8-byte aligned, u64) per query where its freqs matrix begins.
+struct score_documents_layout : stage_layout {
+    size_t term_first, term_blocks, term_flag, term_weight, term_order, q_from, q_n, doc_query, doc_id, q_freq_at;
+    score_documents_layout(size_t n_rec, size_t nq, size_t n_docs) {
+        take_each({&term_first, &term_blocks, &term_flag, &term_weight, &term_order}, n_rec);
+        take_each({&q_from, &q_n}, nq);
+        take_each({&doc_query, &doc_id}, n_docs);
+        q_freq_at = take(2 * nq, 2);
+    }
+};
+// ranked_topk: the tasks (3 words each), per query {first page, pages}, then (8-byte aligned, u64) the key bases.
+struct topk_layout : stage_layout {
+    size_t tasks, page_first, pages, key_base;
+    topk_layout(size_t n_tasks, size_t nq) {
+        tasks = take(3 * n_tasks);
+        take_each({&page_first, &pages}, nq);
+        key_base = take(2 * nq, 2);
+    }
+};
