@@ -6,8 +6,7 @@
 //     count(q) = sum_k #{d in L_k : d not in L_j for all j < k}
 // and every docID of the union is counted exactly once, at the first list that holds it. Every block of every term is
 // decoded into pages (decode_pages), the query's pages term after term; then ONE launch, a workgroup per page, a thread
-// per slot, probes each posting against the lists before its own: the block-max search of next_geq
-// (dict_posting_list.hpp:126-147) over the earlier list's block maxima, then a binary search in that block's decoded page.
+// per slot, probes each posting against the lists before its own (find_posting: DESIGN.md 4d, "Shared device primitives").
 // The pages are only read: nothing is retired the way the AND probe retires its candidates.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,6 +35,12 @@ struct or_pass {
     unsigned long long* freq_sums;
 };
 
+// d in the list of term record j, every block of which lies decoded from page term_page[j] on? -> where
+__device__ __forceinline__ posting or_find(const or_pass& p, uint32_t j, uint32_t d) {
+    return find_posting(p.block_max, p.blocks, p.term_first[j], p.term_blocks[j], p.docs, d,
+                        [&](uint32_t pos) { return p.term_page[j] + pos; });
+}
+
 // A workgroup per page (256 slots = 4 waves), a thread per slot. A page is one term's block of one query, so a wave's
 // survivors all belong to one query: one atomic per wave. The slots past the block's n are padding and never count.
 __global__ __launch_bounds__(256) void or_count_kernel(or_pass p) {
@@ -51,13 +56,7 @@ __global__ __launch_bounds__(256) void or_count_kernel(or_pass p) {
         const uint32_t d = p.docs[at];
         if (p.freqs) f = p.freqs[at];
         for (uint32_t j = p.term_from[k]; j != k; ++j) {  // the lists before this one: does one of them hold d?
-            const uint32_t fb = p.term_first[j], nb = p.term_blocks[j];
-            const uint32_t pos = lower_bound_u32(p.block_max + fb, nb, d);
-            if (pos == nb) continue;  // past the list's last docID
-            const uint32_t m = p.blocks[fb + pos].n;
-            const uint32_t* probe = p.docs + uint64_t(p.term_page[j] + pos) * kPageSlots;
-            const uint32_t hit = lower_bound_u32(probe, m, d);
-            if (hit != m && probe[hit] == d) {
+            if (or_find(p, j, d).held()) {
                 alive = false;
                 break;
             }

@@ -16,11 +16,11 @@
 #include <cstdint>
 
 #include "dint_hip.h"
+#include "dint_query_lookup.hpp"
 
 namespace dint_dev {
 
 constexpr uint32_t kDeadCandidate = 0xFFFFFFFFu;  // not a docID: docIDs are < num_docs <= 2^32 - 1
-constexpr uint32_t kPageSlots = 256;              // one block per page
 
 // sub[i] = blocks[ids[i]] relocated to page i
 // (count set: page i >= *count is empty — n_pages is then what the host knows, an upper bound)
@@ -68,18 +68,6 @@ __global__ void prepare_pages_kernel(const dint_block_ref* blocks, uint64_t n_bl
     gaps_left[i] = 0;
 }
 
-// first index in [0, n) with a[i] >= key (n if none)
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* a, uint32_t n, uint32_t key) {
-    uint32_t lo = 0, len = n;
-    while (len) {
-        const uint32_t half = len >> 1;
-        const bool right = a[lo + half] < key;
-        lo = right ? lo + half + 1 : lo;
-        len = right ? len - half - 1 : half;
-    }
-    return lo;
-}
-
 // Claims: a round's searches name the blocks that must be decoded, each ONCE — whoever claims a block first appends it to the
 // touched list, and its place there (its page in the probe buffer) is what every candidate of the block looks up afterwards.
 // Two forms. Dense (hash_mask == 0): a flag and a rank per block of the INDEX (`needed`, `rank`: n_blocks words each) — the
@@ -87,15 +75,28 @@ __device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* a, uint32_t 
 // slot of an open-addressing table, `rank` the place — a table per WORKGROUP for the workgroup-per-query batch form, sized
 // for a query's rounds (at most 4096 touched blocks), not for the index. The keys are written and read at the L2 (atomics):
 // a workgroup walks query after query over the same table, and this CU's L1 may still hold a line of the query before.
+//
+// Neighbouring candidates are sorted, so they mostly fall into the same block: one claim per run of wave neighbours that
+// name the same idx (kDeadCandidate: nothing to claim). -> this lane leads its run. EVERY lane of the wave must reach it.
+__device__ __forceinline__ bool run_leader(uint32_t idx) {
+    const uint32_t prev = __shfl_up(idx, 1);
+    return idx != kDeadCandidate && ((threadIdx.x & 63u) == 0 || prev != idx);
+}
+// The dense claim of flag idx: the first to ask appends gb to the touched list and leaves its place there in rank[idx].
+// -> this thread was the first.
+__device__ __forceinline__ bool claim_dense(uint32_t* flag, uint32_t* rank, uint32_t* touched, uint32_t* n_touched, uint32_t idx,
+                                            uint32_t gb) {
+    if (atomicExch(&flag[idx], 1u) != 0u) return false;
+    const uint32_t k = atomicAdd(n_touched, 1u);
+    touched[k] = gb;
+    rank[idx] = k;
+    return true;
+}
 __device__ __forceinline__ uint32_t claim_slot(uint32_t gb, uint32_t hash_mask) { return ((gb * 2654435761u) >> 9) & hash_mask; }
 __device__ __forceinline__ void claim_block(uint32_t* needed, uint32_t* rank, uint32_t* touched, uint32_t* n_touched, uint32_t hash_mask,
                                             uint32_t gb) {
     if (hash_mask == 0) {
-        if (atomicExch(&needed[gb], 1u) == 0u) {
-            const uint32_t k = atomicAdd(n_touched, 1u);
-            touched[k] = gb;
-            rank[gb] = k;
-        }
+        claim_dense(needed, rank, touched, n_touched, gb, gb);
         return;
     }
     for (uint32_t h = claim_slot(gb, hash_mask);; h = (h + 1u) & hash_mask) {
@@ -121,8 +122,8 @@ __device__ __forceinline__ uint32_t claimed_rank(const uint32_t* needed, const u
 
 // A whole round behind its decode, in the decode's own launch (few candidates — a single query: a launch less is a
 // tenth of what the caller waits): the workgroup of decode_*_query_kernel that finishes last probes every candidate in
-// the pages just decoded (and_probe_release_kernel), and either searches the NEXT round's list for the survivors
-// (and_search_kernel) or, behind the last round, counts them and hands the results to the host. Two rounds' claim
+// the pages just decoded, and either searches the NEXT round's list for the survivors (what and_search_kernel does for
+// the first round) or, behind the last round, counts them and hands the results to the host. Two rounds' claim
 // flags / ranks / touched lists are live at once here — this round's are read and released while the next round's
 // are written; a list may be one query's term in this round and another's in the next — so rounds alternate
 // between two sets of them.
@@ -156,6 +157,49 @@ struct round_tail {
     uint32_t hash_mask;               // and_round_tail: 0, or the claim tables are hashed ones of this capacity - 1 (claim_block)
 };
 
+// One candidate slot's step of a round tail: the probe of this round's page, the block-max search of the next round's
+// list, and the candidate retired (cand[i] dead) or retargeted (target[i] = gb). hash_mask: the form of this round's
+// claims (a literal 0 folds the hashed form away). count_each: behind the last round a survivor adds itself to its
+// query's count on the spot (the one-workgroup tail; the batch kernel counts a page's survivors together).
+struct and_step {
+    uint32_t gb;  // the block to claim for the next round (kDeadCandidate: none)
+    bool alive;   // a candidate, and still one behind this round
+};
+__device__ __forceinline__ and_step and_candidate_step(const round_tail& t, uint64_t i, uint32_t hash_mask, bool count_each) {
+    // (what a candidate needs is asked for in as few dependent trips as its data allow: {candidate, its query, its target
+    // block} -> {the query's block counts in this round and the next} -> {the target's size and page} -> the probe -> the
+    // next round's block maxima. K-ary searches — 15 pivots a step, 2 trips for a block instead of 8 — were measured:
+    // 29.0 against 27.4 us a query, the one CU's load issue is what they cost)
+    uint32_t gb = kDeadCandidate;
+    const uint32_t c = t.cand[i];
+    const uint32_t q = t.page_query[i / kPageSlots];
+    const uint32_t b_raw = t.target[i];  // (only meaningful where this round has a term for q: masked below)
+    bool alive = false;
+    if (c != kDeadCandidate) {
+        const uint32_t tb = t.term_blocks[q];
+        uint32_t nb = 0, fb = 0;
+        if (t.next_blocks) nb = t.next_blocks[q], fb = t.next_first[q];
+        alive = true;
+        if (tb != 0) {
+            const uint32_t n = t.blocks[b_raw].n;
+            const uint32_t* page = t.probe + uint64_t(claimed_rank(t.needed, t.rank, hash_mask, b_raw)) * kPageSlots;
+            alive = find_in_page(page, n, c) != kAbsent;
+        }
+        if (alive && nb) {
+            const uint32_t pos = list_block_of(t.block_max, fb, nb, c);
+            if (pos == nb) {
+                alive = false;  // next_geq past the last block: m_universe, dict_posting_list.hpp:128-131
+            } else {
+                gb = fb + pos;
+                t.target[i] = gb;
+            }
+        }
+        if (!alive) t.cand[i] = kDeadCandidate;
+        else if (count_each && !t.next_blocks) atomicAdd(&t.counts[q], 1ull);
+    }
+    return {gb, alive};
+}
+
 // (every thread of one workgroup; n_slots is a multiple of 256, so wavefronts stay whole inside the loop)
 __device__ __forceinline__ void and_round_tail(const round_tail& t) {
     const uint32_t nt = *t.n_touched;
@@ -164,40 +208,8 @@ __device__ __forceinline__ void and_round_tail(const round_tail& t) {
     if (t.hash_mask == 0)
         for (uint32_t k = threadIdx.x; k < nt; k += blockDim.x) t.needed[t.touched[k]] = 0;
     for (uint64_t i = threadIdx.x; i < t.n_slots; i += blockDim.x) {
-        uint32_t gb = kDeadCandidate;
-        // (what a candidate needs is asked for in as few dependent trips as its data allow: {candidate, its query, its target
-        // block} -> {the query's block counts in this round and the next} -> {the target's size and page} -> the probe -> the
-        // next round's block maxima. K-ary searches — 15 pivots a step, 2 trips for a block instead of 8 — were measured:
-        // 29.0 against 27.4 us a query, the one CU's load issue is what they cost)
-        const uint32_t c = t.cand[i];
-        const uint32_t q = t.page_query[i / kPageSlots];
-        const uint32_t b_raw = t.target[i];  // (only meaningful where this round has a term for q: masked below)
-        if (c != kDeadCandidate) {
-            const uint32_t tb = t.term_blocks[q];
-            uint32_t nb = 0, fb = 0;
-            if (t.next_blocks) nb = t.next_blocks[q], fb = t.next_first[q];
-            bool alive = true;
-            if (tb != 0) {
-                const uint32_t n = t.blocks[b_raw].n;
-                const uint32_t* page = t.probe + uint64_t(claimed_rank(t.needed, t.rank, t.hash_mask, b_raw)) * kPageSlots;
-                const uint32_t pos = lower_bound_u32(page, n, c);
-                alive = pos != n && page[pos] == c;
-            }
-            if (alive && nb) {
-                const uint32_t pos = lower_bound_u32(t.block_max + fb, nb, c);
-                if (pos == nb) {
-                    alive = false;
-                } else {
-                    gb = fb + pos;
-                    t.target[i] = gb;
-                }
-            }
-            if (!alive) t.cand[i] = kDeadCandidate;
-            else if (!t.next_blocks) atomicAdd(&t.counts[q], 1ull);
-        }
-        const uint32_t prev = __shfl_up(gb, 1);
-        const bool lead = gb != kDeadCandidate && ((threadIdx.x & 63u) == 0 || prev != gb);
-        if (lead) claim_block(t.next_needed, t.next_rank, t.next_touched, t.next_n_touched, t.hash_mask, gb);
+        const uint32_t gb = and_candidate_step(t, i, t.hash_mask, true).gb;
+        if (run_leader(gb)) claim_block(t.next_needed, t.next_rank, t.next_touched, t.next_n_touched, t.hash_mask, gb);
     }
     if (t.hash_mask != 0 && nt != 0) {  // every probe has read its rank: this round's table is cleared for the round after next
         __syncthreads();
@@ -210,58 +222,24 @@ __device__ __forceinline__ void and_round_tail(const round_tail& t) {
 }
 
 // The same for a BATCH (a thread per candidate slot, a workgroup per page): the probe of round r, the release of its claims
-// and the block-max search of round r + 1 in ONE launch — until round 5 the batch path ran them as two (and_probe_release_kernel,
-// and_search_kernel): a launch per round less, of three. The two rounds' claim flags / ranks / touched lists alternate
+// and the block-max search of round r + 1 in ONE launch. The two rounds' claim flags / ranks / touched lists alternate
 // between two sets, as in and_round_tail. Behind the last round: the survivors counted per query and handed to the host by
-// the workgroup that finishes last (t.done: zero at launch).
+// the workgroup that finishes last (t.done: zero at launch; pinned memory, written from here: no copy back, one stream
+// operation less for the caller to wait for).
 __global__ void and_round_tail_kernel(round_tail t) {
     const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i < *t.n_touched) t.needed[t.touched[i]] = 0;
-    uint32_t gb = kDeadCandidate;
-    bool alive = false;
-    if (i < t.n_slots) {
-        const uint32_t c = t.cand[i];
-        if (c != kDeadCandidate) {
-            const uint32_t q = t.page_query[i / kPageSlots];
-            alive = true;
-            if (t.term_blocks[q] != 0) {
-                const uint32_t b = t.target[i];
-                const uint32_t n = t.blocks[b].n;
-                const uint32_t* page = t.probe + uint64_t(t.rank[b]) * kPageSlots;
-                const uint32_t pos = lower_bound_u32(page, n, c);
-                alive = pos != n && page[pos] == c;
-            }
-            if (alive && t.next_blocks) {
-                const uint32_t nb = t.next_blocks[q];
-                if (nb) {
-                    const uint32_t fb = t.next_first[q];
-                    const uint32_t pos = lower_bound_u32(t.block_max + fb, nb, c);
-                    if (pos == nb) {
-                        alive = false;  // next_geq past the last block: m_universe, dict_posting_list.hpp:128-131
-                    } else {
-                        gb = fb + pos;
-                        t.target[i] = gb;
-                    }
-                }
-            }
-            if (!alive) t.cand[i] = kDeadCandidate;
-        }
-    }
-    if (t.next_blocks) {  // (uniform) the next round's claims: one per run of candidates that fall into the same block
-        const uint32_t prev = __shfl_up(gb, 1);
-        const bool lead = gb != kDeadCandidate && ((threadIdx.x & 63u) == 0 || prev != gb);
-        if (lead && atomicExch(&t.next_needed[gb], 1u) == 0u) {
-            const uint32_t k = atomicAdd(t.next_n_touched, 1u);
-            t.next_touched[k] = gb;
-            t.next_rank[gb] = k;
-        }
+    and_step s{kDeadCandidate, false};
+    if (i < t.n_slots) s = and_candidate_step(t, i, 0, false);
+    if (t.next_blocks) {  // (uniform) the next round's claims
+        if (run_leader(s.gb)) claim_dense(t.next_needed, t.next_rank, t.next_touched, t.next_n_touched, s.gb, s.gb);
         return;
     }
-    const int n = __syncthreads_count(alive);
+    const int n = __syncthreads_count(s.alive);
     if (threadIdx.x == 0 && n) atomicAdd(&t.counts[t.page_query[i / kPageSlots]], (unsigned long long)n);
     if (!t.host_counts) return;  // (uniform)
     __shared__ uint32_t last;
-    if (gridDim.x != 1) {
+    if (gridDim.x != 1) {  // (one workgroup: nobody to wait for, and no fence — an agent-scope fence costs microseconds here)
         if (threadIdx.x == 0) {
             __threadfence();
             last = atomicAdd(t.done, 1u) == gridDim.x - 1 ? 1u : 0u;
@@ -290,7 +268,7 @@ __global__ void and_search_kernel(uint32_t* cand, uint64_t n_slots, const uint32
             const uint32_t nb = term_blocks[q];
             if (nb) {
                 const uint32_t fb = term_first[q];
-                const uint32_t pos = lower_bound_u32(block_max + fb, nb, c);
+                const uint32_t pos = list_block_of(block_max, fb, nb, c);
                 if (pos == nb) {
                     cand[i] = kDeadCandidate;  // next_geq past the last block: m_universe, :128-131
                 } else {
@@ -300,61 +278,7 @@ __global__ void and_search_kernel(uint32_t* cand, uint64_t n_slots, const uint32
             }
         }
     }
-    // neighbouring candidates are sorted, so they mostly fall into the same block: one claim per run
-    const uint32_t prev = __shfl_up(gb, 1);
-    const bool lead = gb != kDeadCandidate && ((threadIdx.x & 63u) == 0 || prev != gb);
-    if (lead && atomicExch(&needed[gb], 1u) == 0u) {
-        const uint32_t k = atomicAdd(n_touched, 1u);
-        touched[k] = gb;
-        rank[gb] = k;
-    }
-}
-
-// Round steps B and C in one launch: each live candidate looks itself up in its (now decoded) block, and — thread k, for the k-th touched block — the claim flag cleared for
-// the next round (the probe reads target / rank, not the flags). `counts` (the last round): the survivors of the
-// workgroup's page — one query's — are added to the query's result on the spot (and_count_kernel's job);
-// `host_counts`: ... and the results written to the host's (pinned) memory by the last workgroup to finish.
-__global__ void and_probe_release_kernel(uint32_t* cand, uint64_t n_slots, const uint32_t* page_query, const uint32_t* term_blocks,
-                                         const dint_block_ref* blocks, const uint32_t* target, const uint32_t* rank,
-                                         const uint32_t* probe, const uint32_t* touched, const uint32_t* n_touched, uint32_t* needed,
-                                         unsigned long long* counts, uint32_t* done, unsigned long long* host_counts, uint32_t n_queries) {
-    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i < *n_touched) needed[touched[i]] = 0;
-    bool alive = false;
-    if (i < n_slots) {
-        const uint32_t c = cand[i];
-        if (c != kDeadCandidate) {
-            alive = true;
-            if (term_blocks[page_query[i / kPageSlots]] != 0) {
-                const uint32_t gb = target[i];
-                const uint32_t n = blocks[gb].n;
-                const uint32_t* page = probe + uint64_t(rank[gb]) * kPageSlots;
-                const uint32_t pos = lower_bound_u32(page, n, c);
-                if (pos == n || page[pos] != c) {
-                    cand[i] = kDeadCandidate;
-                    alive = false;
-                }
-            }
-        }
-    }
-    if (!counts) return;  // (uniform)
-    const int n = __syncthreads_count(alive);
-    if (threadIdx.x == 0 && n) atomicAdd(&counts[page_query[i / kPageSlots]], (unsigned long long)n);
-    if (!host_counts) return;  // (uniform)
-    // ... and the workgroup that finishes last hands the results to the host (pinned memory, written from here: no
-    // copy back, one stream operation less for the caller to wait for)
-    __shared__ uint32_t last;
-    if (gridDim.x != 1) {  // (one workgroup: nobody to wait for, and no fence — an agent-scope fence costs microseconds here)
-        if (threadIdx.x == 0) {
-            __threadfence();
-            last = atomicAdd(done, 1u) == gridDim.x - 1 ? 1u : 0u;
-        }
-        __syncthreads();
-        if (!last) return;
-        __threadfence();
-    }
-    for (uint32_t q = threadIdx.x; q < n_queries; q += blockDim.x)
-        host_counts[q] = __hip_atomic_load(&counts[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (run_leader(gb)) claim_dense(needed, rank, touched, n_touched, gb, gb);
 }
 
 // and_query<true>, step A per term: the block each match (surviving candidate) falls into — for the rarest term
@@ -372,18 +296,12 @@ __global__ void and_freq_search_kernel(const uint32_t* cand, uint64_t n_slots, c
             } else {
                 const uint32_t q = page_query[i / kPageSlots];
                 const uint32_t nb = term_blocks[q];
-                if (nb) gb = term_first[q] + lower_bound_u32(block_max + term_first[q], nb, c);  // (a match: always found)
+                if (nb) gb = term_first[q] + list_block_of(block_max, term_first[q], nb, c);  // (a match: always found)
             }
             target[i] = gb;
         }
     }
-    const uint32_t prev = __shfl_up(gb, 1);
-    const bool lead = gb != kDeadCandidate && ((threadIdx.x & 63u) == 0 || prev != gb);
-    if (lead && atomicExch(&needed[gb], 1u) == 0u) {
-        const uint32_t k = atomicAdd(n_touched, 1u);
-        touched[k] = gb;
-        rank[gb] = k;
-    }
+    if (run_leader(gb)) claim_dense(needed, rank, touched, n_touched, gb, gb);
 }
 
 // ... step B: every match finds its docID in its block's decoded page and adds the freq at that position to its query's
@@ -400,8 +318,8 @@ __global__ void and_freq_gather_kernel(const uint32_t* cand, uint64_t n_slots, c
     const uint32_t gb = target[i];
     const uint32_t n = blocks[gb].n;
     const uint64_t page = uint64_t(rank[gb]) * kPageSlots;
-    const uint32_t pos = lower_bound_u32(probe + page, n, c);
-    if (pos < n && probe[page + pos] == c) atomicAdd(&freq_sums[q], (unsigned long long)fprobe[page + pos]);
+    const uint32_t pos = find_in_page(probe + page, n, c);
+    if (pos != kAbsent) atomicAdd(&freq_sums[q], (unsigned long long)fprobe[page + pos]);
 }
 
 __global__ void and_release_kernel(const uint32_t* touched, uint32_t n_touched, uint32_t* needed, const uint32_t* count = nullptr) {

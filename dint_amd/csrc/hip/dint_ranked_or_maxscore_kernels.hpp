@@ -9,9 +9,9 @@
 //      and dies if (P + sum_N m_t) * margin < theta; a live one claims, for every N term whose pages are not decoded,
 //      the block its docID falls in (block-max search). Claims are per (term record, block): a flag, a rank, a touched list.
 //   2. The host decodes the claimed blocks behind the other pages (docs and freqs).
-//   3. ms_score_kernel: every live representative walks ALL of the query's terms in ascending term id and adds
-//      q_weight * f / (f + kd) from 0.0f, binary32, uncontracted — ranked_or_score_kernel's operations in its order —
-//      probing decoded terms through their pages and N terms through their claimed blocks.
+//   3. ms_score_kernel: every live representative walks ALL of the query's terms in ascending term id and adds their
+//      addends from 0.0f (bm25_add) — ranked_or_score_kernel's operations in its order — probing decoded terms through
+//      their pages and N terms through their claimed blocks.
 // ranked_topk then selects over the candidate pages. Nothing is added atomically but the claim counters.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,15 +58,12 @@ struct maxscore_pass {
     float* score;
 };
 
-// d in the decoded page of record j? -> its position there, or ~0u
-__device__ __forceinline__ uint32_t ms_find_decoded(const maxscore_pass& p, uint32_t j, uint32_t d, uint64_t& pg) {
-    const uint32_t fb = p.term_first[j], nb = p.term_blocks[j];
-    const uint32_t pos = lower_bound_u32(p.block_max + fb, nb, d);
-    if (pos == nb) return ~0u;  // past the list's last docID
-    const uint32_t m = p.blocks[fb + pos].n;
-    pg = uint64_t(p.term_page[j] + pos) * kPageSlots;
-    const uint32_t hit = lower_bound_u32(p.docs + pg, m, d);
-    return hit != m && p.docs[pg + hit] == d ? hit : ~0u;
+// d in the list of record j? -> where. A decoded record's blocks lie from page term_page[j] on; a claimed one's block
+// is at its rank behind claim_page0 (asked by a candidate that claimed it).
+__device__ __forceinline__ posting ms_find(const maxscore_pass& p, uint32_t j, uint32_t d, bool claimed) {
+    return find_posting(p.block_max, p.blocks, p.term_first[j], p.term_blocks[j], p.docs, d, [&](uint32_t pos) {
+        return claimed ? p.claim_page0 + p.rank[p.term_page[j] + pos] : p.term_page[j] + pos;
+    });
 }
 
 // A workgroup per candidate page, a thread per slot. The loops over a query's records are uniform in the workgroup (a
@@ -82,7 +79,7 @@ __global__ __launch_bounds__(256) void ms_bound_kernel(maxscore_pass p) {
     bool alive = slot < n;
     const uint32_t d = alive ? p.docs[at] : kDeadCandidate;
     if (alive) {
-        const float kd = kBm25K1 * ((1.0f - kBm25B) + kBm25B * p.norm_lens[d]);
+        const float kd = bm25_kd(p.norm_lens[d]);
         const uint32_t from = p.q_from[q], ne = p.q_ne[q];
         bool before = true;  // (still in the E lists before this one)
         double P = 0.0;
@@ -93,18 +90,15 @@ __global__ __launch_bounds__(256) void ms_bound_kernel(maxscore_pass p) {
                 before = false;
                 f = float(p.freqs[at]);
             } else {
-                uint64_t pg = 0;
-                const uint32_t hit = ms_find_decoded(p, j, d, pg);
-                if (hit == ~0u) continue;
+                const posting hit = ms_find(p, j, d, false);
+                if (!hit.held()) continue;
                 if (before) {  // an earlier E list holds d: its posting there is the representative
                     alive = false;
                     break;
                 }
-                f = float(p.freqs[pg + hit]);
+                f = float(p.freqs[hit.slot()]);
             }
-            const float w = f / (f + kd);
-            const float a = p.term_weight[j] * w;
-            P = P + double(a);
+            P = P + double(bm25_addend(p.term_weight[j], f, kd));
         }
         if (alive && (P + p.q_rest[q]) * p.q_margin[q] < double(p.q_theta[q])) alive = false;  // strict: a tie with theta stays
     }
@@ -115,24 +109,17 @@ __global__ __launch_bounds__(256) void ms_bound_kernel(maxscore_pass p) {
         if (!p.term_claimed[j]) continue;
         uint32_t idx = kDeadCandidate;
         if (alive) {
-            const uint32_t fb = p.term_first[j], nb = p.term_blocks[j];
-            const uint32_t pos = lower_bound_u32(p.block_max + fb, nb, d);
+            const uint32_t nb = p.term_blocks[j];
+            const uint32_t pos = list_block_of(p.block_max, p.term_first[j], nb, d);
             if (pos != nb) idx = p.term_page[j] + pos;
         }
-        const uint32_t prev = __shfl_up(idx, 1);
-        const bool lead = idx != kDeadCandidate && ((threadIdx.x & 63u) == 0 || prev != idx);
-        if (lead && atomicExch(&p.flag[idx], 1u) == 0u) {
-            const uint32_t r = atomicAdd(p.n_touched, 1u);
-            p.touched[r] = p.term_first[j] + (idx - p.term_page[j]);
-            p.rank[idx] = r;
+        if (run_leader(idx) && claim_dense(p.flag, p.rank, p.touched, p.n_touched, idx, p.term_first[j] + (idx - p.term_page[j])))
             atomicAdd(&p.q_claims[q], 1u);
-        }
     }
 }
 
 // A workgroup per candidate page, a thread per live representative: its whole score, as ranked_or_score_kernel sums it.
 __global__ __launch_bounds__(256) void ms_score_kernel(maxscore_pass p) {
-#pragma clang fp contract(off)
     const uint32_t cp = blockIdx.x;
     const uint64_t c_at = uint64_t(cp) * kPageSlots + threadIdx.x;
     const uint32_t d = p.cand[c_at];
@@ -141,30 +128,19 @@ __global__ __launch_bounds__(256) void ms_score_kernel(maxscore_pass p) {
     const uint32_t q = p.rec_query[k];
     const uint64_t at = uint64_t(page) * kPageSlots + threadIdx.x;
     const uint32_t from = p.q_from[q], nr = p.q_n[q];
-    const float kd = kBm25K1 * ((1.0f - kBm25B) + kBm25B * p.norm_lens[d]);
+    const float kd = bm25_kd(p.norm_lens[d]);
     float sc = 0.0f;
     for (uint32_t i = 0; i != nr; ++i) {
         const uint32_t j = p.term_order[from + i];
         float f;
         if (j == k) {
             f = float(p.freqs[at]);
-        } else if (!p.term_claimed[j]) {
-            uint64_t pg = 0;
-            const uint32_t hit = ms_find_decoded(p, j, d, pg);
-            if (hit == ~0u) continue;
-            f = float(p.freqs[pg + hit]);
-        } else {  // (this candidate claimed the block: its rank is set)
-            const uint32_t fb = p.term_first[j], nb = p.term_blocks[j];
-            const uint32_t pos = lower_bound_u32(p.block_max + fb, nb, d);
-            if (pos == nb) continue;
-            const uint32_t m = p.blocks[fb + pos].n;
-            const uint64_t pg = uint64_t(p.claim_page0 + p.rank[p.term_page[j] + pos]) * kPageSlots;
-            const uint32_t hit = lower_bound_u32(p.docs + pg, m, d);
-            if (hit == m || p.docs[pg + hit] != d) continue;
-            f = float(p.freqs[pg + hit]);
+        } else {
+            const posting hit = ms_find(p, j, d, p.term_claimed[j] != 0);
+            if (!hit.held()) continue;
+            f = float(p.freqs[hit.slot()]);
         }
-        const float w = f / (f + kd);
-        sc = sc + p.term_weight[j] * w;
+        sc = bm25_add(sc, p.term_weight[j], f, kd);
     }
     p.score[c_at] = sc;
 }

@@ -6,10 +6,9 @@
 // list holds d (the first occurrence of or_count_kernel); the representative alone computes d's whole score, so a
 // document is scored by exactly one thread and nothing is added atomically. It walks the query's terms in ascending term
 // id — the order query_freqs (queries.hpp:135-148) hands ranked_or_query its cursors in, and so the order its sum runs
-// in — and adds q_weight_t * doc_term_weight(f_t, norm_len) for every term whose list holds d, from 0.0f, binary32,
-// uncontracted, as ranked_gather_kernel does. A term is its own list (its freq is the slot's own) or is probed once: the
-// block-max search, a binary search in the decoded page, the freq at the same position of the freqs page. A hit in a
-// list before its own (longer, or as long with a smaller term id) kills the slot: the walk decides that on its way.
+// in — and adds the BM25 addend (bm25_add) of every term whose list holds d, from 0.0f. A term is its own list (its freq is
+// the slot's own) or is probed once (or_find; DESIGN.md 4d, "Shared device primitives"). A hit in a list before its own
+// (longer, or as long with a smaller term id) kills the slot: the walk decides that on its way.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,7 +33,6 @@ struct ranked_or_pass {
 
 // A workgroup per page (256 slots), a thread per slot, as or_count_kernel. The slots past the block's n are padding: dead.
 __global__ __launch_bounds__(256) void ranked_or_score_kernel(ranked_or_pass p) {
-#pragma clang fp contract(off)
     const or_pass& o = p.base;
     const uint32_t page = blockIdx.x;
     const uint32_t k = o.page_term[page];
@@ -47,7 +45,7 @@ __global__ __launch_bounds__(256) void ranked_or_score_kernel(ranked_or_pass p) 
     }
     const uint32_t d = o.docs[at];
     const uint32_t from = o.term_from[k], n_terms = p.term_n[k];
-    const float kd = kBm25K1 * ((1.0f - kBm25B) + kBm25B * p.norm_lens[d]);
+    const float kd = bm25_kd(p.norm_lens[d]);
     float sc = 0.0f;
     for (uint32_t i = 0; i != n_terms; ++i) {
         const uint32_t j = p.term_order[from + i];
@@ -55,21 +53,15 @@ __global__ __launch_bounds__(256) void ranked_or_score_kernel(ranked_or_pass p) 
         if (j == k) {
             f = float(o.freqs[at]);
         } else {
-            const uint32_t fb = o.term_first[j], nb = o.term_blocks[j];
-            const uint32_t pos = lower_bound_u32(o.block_max + fb, nb, d);
-            if (pos == nb) continue;  // past the list's last docID
-            const uint32_t m = o.blocks[fb + pos].n;
-            const uint64_t pg = uint64_t(o.term_page[j] + pos) * kPageSlots;
-            const uint32_t hit = lower_bound_u32(o.docs + pg, m, d);
-            if (hit == m || o.docs[pg + hit] != d) continue;
+            const posting hit = or_find(o, j, d);
+            if (!hit.held()) continue;
             if (j < k) {  // an earlier list holds d: its posting there is the representative
                 p.cand[at] = kDeadCandidate;
                 return;
             }
-            f = float(o.freqs[pg + hit]);
+            f = float(o.freqs[hit.slot()]);
         }
-        const float w = f / (f + kd);
-        sc = sc + p.term_weight[j] * w;
+        sc = bm25_add(sc, p.term_weight[j], f, kd);
     }
     p.cand[at] = d;
     p.score[at] = sc;

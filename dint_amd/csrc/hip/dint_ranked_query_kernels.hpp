@@ -22,14 +22,30 @@ constexpr uint32_t kRankedMaxK = DINT_RANKED_MAX_K;
 constexpr float kBm25B = 0.5f;   // bm25::b  (bm25.hpp)
 constexpr float kBm25K1 = 1.2f;  // bm25::k1
 
+// BM25 as every scoring kernel computes it: q_weight * doc_term_weight(f, norm_len), doc_term_weight = f / (f + kd),
+// kd = k1 * ((1 - b) + b * norm_len), added term by term from 0.0f — in binary32, in the reference's order and
+// UNCONTRACTED (no fma): ranked OR, pruned ranked OR and the scores of given documents agree bit for bit because they
+// all add bm25_addend's value in the same order. The pragma is lexical, so each helper carries its own.
+__device__ __forceinline__ float bm25_kd(float norm_len) {
+#pragma clang fp contract(off)
+    return kBm25K1 * ((1.0f - kBm25B) + kBm25B * norm_len);
+}
+__device__ __forceinline__ float bm25_addend(float weight, float f, float kd) {
+#pragma clang fp contract(off)
+    const float w = f / (f + kd);
+    return weight * w;
+}
+__device__ __forceinline__ float bm25_add(float sc, float weight, float f, float kd) {
+#pragma clang fp contract(off)
+    return sc + bm25_addend(weight, f, kd);
+}
+
 // and_query<true>'s gather with a score instead of a freq sum: every live candidate of a query that has this term finds its
-// docID in its block's decoded page and adds q_weight[q] * w to its slot's score, w = f / (f + k1 * ((1 - b) + b * norm_len))
-// in binary32, in the reference's order and uncontracted. term_blocks null: the rarest term (every live candidate is a
-// match of its own page), where norm_len[docid] is read, once per candidate, into kden = k1 * ((1 - b) + b * norm_len).
+// docID in its block's decoded page and adds its term's addend to its slot's score (bm25_add). term_blocks null: the rarest
+// term (every live candidate is a match of its own page), where norm_len[docid] is read, once per candidate, into kden.
 __global__ void ranked_gather_kernel(const uint32_t* cand, uint64_t n_slots, const uint32_t* page_query, const uint32_t* term_blocks,
                                      const dint_block_ref* blocks, const uint32_t* target, const uint32_t* rank, const uint32_t* probe,
                                      const uint32_t* fprobe, const float* q_weight, const float* norm_lens, float* kden, float* score) {
-#pragma clang fp contract(off)
     const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n_slots) return;
     const uint32_t c = cand[i];
@@ -39,18 +55,16 @@ __global__ void ranked_gather_kernel(const uint32_t* cand, uint64_t n_slots, con
     const uint32_t gb = target[i];
     const uint32_t n = blocks[gb].n;
     const uint64_t page = uint64_t(rank[gb]) * kPageSlots;
-    const uint32_t pos = lower_bound_u32(probe + page, n, c);
-    if (pos >= n || probe[page + pos] != c) return;
+    const uint32_t pos = find_in_page(probe + page, n, c);
+    if (pos == kAbsent) return;
     float kd;
     if (!term_blocks) {
-        kd = kBm25K1 * ((1.0f - kBm25B) + kBm25B * norm_lens[c]);
+        kd = bm25_kd(norm_lens[c]);
         kden[i] = kd;
     } else {
         kd = kden[i];
     }
-    const float f = float(fprobe[page + pos]);
-    const float w = f / (f + kd);
-    score[i] = score[i] + q_weight[q] * w;
+    score[i] = bm25_add(score[i], q_weight[q], float(fprobe[page + pos]), kd);
 }
 
 // One task of the selection: query q, run a (and for a merge, run b: its best R keys are merged into run a).

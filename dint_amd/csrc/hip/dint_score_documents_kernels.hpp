@@ -7,8 +7,8 @@
 //   1. sd_claim_kernel: a thread per (document, term record) finds the block the docID falls in (the first block whose last
 //      docID is >= it: block-max search) and claims it, once per (term record, block): a flag, a rank, a touched list.
 //   2. The host decodes the touched blocks' docs and freqs parts, launches sized by its own bound.
-//   3. sd_score_kernel: a thread per document walks the query's terms in ascending term id and adds q_weight * f / (f + kd)
-//      from 0.0f, binary32, uncontracted — ranked_or_score_kernel's operations in its order.
+//   3. sd_score_kernel: a thread per document walks the query's terms in ascending term id and adds their addends from
+//      0.0f (bm25_add) — ranked_or_score_kernel's operations in its order.
 // Nothing is added atomically but the touched counter.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -61,25 +61,18 @@ __global__ __launch_bounds__(256) void sd_claim_kernel(score_documents_pass p) {
         if (r < nr) {
             const uint32_t j = from + r;
             const uint32_t fb = p.term_first[j], nb = p.term_blocks[j];
-            const uint32_t pos = lower_bound_u32(p.block_max + fb, nb, d);
+            const uint32_t pos = list_block_of(p.block_max, fb, nb, d);
             if (pos != nb) {  // (a document past the list's last docID claims nothing)
                 idx = p.term_flag[j] + pos;
                 gb = fb + pos;
             }
         }
-        const uint32_t prev = __shfl_up(idx, 1);
-        const bool lead = idx != kDeadCandidate && ((threadIdx.x & 63u) == 0 || prev != idx);
-        if (lead && atomicExch(&p.flag[idx], 1u) == 0u) {
-            const uint32_t at = atomicAdd(p.n_touched, 1u);
-            p.touched[at] = gb;
-            p.rank[idx] = at;
-        }
+        if (run_leader(idx)) claim_dense(p.flag, p.rank, p.touched, p.n_touched, idx, gb);
     }
 }
 
 // A thread per document: its whole score, as ranked_or_score_kernel sums it, and its row of freqs.
 __global__ __launch_bounds__(256) void sd_score_kernel(score_documents_pass p) {
-#pragma clang fp contract(off)
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= p.n_docs) return;
     const uint32_t q = p.doc_query[i], d = p.doc_id[i];
@@ -90,26 +83,17 @@ __global__ __launch_bounds__(256) void sd_score_kernel(score_documents_pass p) {
     float sc = 0.0f;
     for (uint32_t r = 0; r != nr; ++r) {
         const uint32_t j = p.term_order[from + r];
-        const uint32_t fb = p.term_first[j], nb = p.term_blocks[j];
-        const uint32_t pos = lower_bound_u32(p.block_max + fb, nb, d);
-        uint32_t fr = 0;
-        bool held = false;
-        if (pos != nb) {  // (this document claimed the block: its rank is set)
-            const uint32_t m = p.blocks[fb + pos].n;
-            const uint64_t pg = uint64_t(p.rank[p.term_flag[j] + pos]) * kPageSlots;
-            const uint32_t hit = lower_bound_u32(p.docs + pg, m, d);
-            held = hit != m && p.docs[pg + hit] == d;
-            if (held) fr = p.freqs[pg + hit];
-        }
+        // (this document claimed the block its docID falls in: its rank is set)
+        const posting hit = find_posting(p.block_max, p.blocks, p.term_first[j], p.term_blocks[j], p.docs, d,
+                                         [&](uint32_t pos) { return p.rank[p.term_flag[j] + pos]; });
+        const uint32_t fr = hit.held() ? p.freqs[hit.slot()] : 0u;
         if (row) row[r] = fr;
-        if (!held) continue;
+        if (!hit.held()) continue;
         if (!have_kd) {
-            kd = kBm25K1 * ((1.0f - kBm25B) + kBm25B * p.norm_lens[d]);
+            kd = bm25_kd(p.norm_lens[d]);
             have_kd = true;
         }
-        const float f = float(fr);
-        const float w = f / (f + kd);
-        sc = sc + p.term_weight[j] * w;
+        sc = bm25_add(sc, p.term_weight[j], float(fr), kd);
     }
     p.score_out[i] = sc;
 }
