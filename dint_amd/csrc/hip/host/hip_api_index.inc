@@ -125,177 +125,197 @@ int block_table_prepare(dint_block_table& t, const dint_block_ref* d_blocks, siz
     return DINT_OK;
 }
 
-// docs parts -> docIDs, freqs parts -> freqs: launches only, nothing waited for
-int block_table_decode(const dint_dict* docs_dict, const dint_dict* freqs_dict, const uint8_t* d_index, size_t index_bytes,
-                       const dint_block_table& t, uint32_t* d_docids, uint32_t* d_freqs, size_t out_capacity, hipStream_t s) {
+// One decode call of a block table, as its two forms see it: the docs and the freqs launch (the same request over the
+// blocks, each with its own units, spans, output, schedule and half of the call's counters) and what the call decided.
+struct block_decode {
+    dint_block_table& t;
+    decode_request docs, freqs;  // (freqs.out null: docs only)
+    tails_args sb{};             // the short blocks' tickets where the docs launch brings them along (tails_phase), else empty
+    bool inline_tails = false;
+    bool covers = false;         // this call decodes EVERY block
+    bool keep = false;           // what the call learns is kept for the next ones
+    bool concurrent = false;     // ... and the table's side streams may be used
+    explicit block_decode(dint_block_table& table) : t(table) {}
+};
+
+// The table's two side streams and three events: all five or none (a table with half of them would trip over the missing
+// ones on its next decode).
+int ensure_side_streams(dint_block_table& t) {
+    if (t.side) return DINT_OK;
+    hipStream_t s1 = nullptr, s2 = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    int prio_low = 0, prio_high = 0;  // (the short blocks' few, long-lived waves first: the DINT launches fill in around them)
+    const bool ok = hip_ok(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking), "hipStreamCreateWithFlags") &&
+                    hip_ok(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high), "hipDeviceGetStreamPriorityRange") &&
+                    hip_ok(hipStreamCreateWithPriority(&s2, hipStreamNonBlocking, prio_high), "hipStreamCreateWithPriority") &&
+                    hip_ok(hipEventCreateWithFlags(&e0, hipEventDisableTiming), "hipEventCreateWithFlags") &&
+                    hip_ok(hipEventCreateWithFlags(&e1, hipEventDisableTiming), "hipEventCreateWithFlags") &&
+                    hip_ok(hipEventCreateWithFlags(&e2, hipEventDisableTiming), "hipEventCreateWithFlags");
+    if (!ok) {
+        if (s1) (void)hipStreamDestroy(s1);
+        if (s2) (void)hipStreamDestroy(s2);
+        for (hipEvent_t e : {e0, e1, e2})
+            if (e) (void)hipEventDestroy(e);
+        return DINT_ERR_HIP;
+    }
+    t.side = s1, t.side2 = s2, t.fork = e0, t.join = e1, t.join2 = e2;
+    return DINT_OK;
+}
+
+// The short blocks — both parts of a block in one lane — through the interpolative decoder, a launch of their own
+// (one wave per kTailLanes short blocks; their outputs are their own)
+void launch_short_blocks(const dint_block_table& t, hipStream_t s, const block_decode& c) {
+    const uint32_t tgrid = uint32_t((t.n_tails + kTailLanes - 1) / kTailLanes);
+    hipLaunchKernelGGL(interpolative_tails_kernel, dim3(tgrid), dim3(64), kTailLdsBytes, s, c.docs.enc, uint64_t(c.docs.enc_bytes), t.d_blocks,
+                       static_cast<const uint64_t*>(nullptr), t.d_tails, t.d_tails + t.n_blocks, c.docs.out, uint64_t(c.docs.out_capacity),
+                       static_cast<uint64_t*>(nullptr), 0u, 1u, c.freqs.out, static_cast<uint8_t*>(nullptr), uint64_t(0));
+}
+
+// ONE launch for the docs parts, the short blocks and the freqs parts (decode_*_index_pair_kernel): both kept schedules
+// are known to be bundles and nothing else (or nearly: the stragglers' small launches follow).
+int block_table_decode_pair(block_decode& c) {
+    dint_block_table& t = c.t;
+    hipStream_t s = c.docs.stream;
+    deferred_launch pd, pf;
+    c.docs.defer = &pd;
+    c.freqs.defer = &pf;
+    int st = launch_decode(c.docs);
+    if (st != DINT_OK) return st;
+    st = launch_decode(c.freqs);
+    if (st != DINT_OK) {
+        if (pd.prepared) (void)finish_deferred(pd);
+        return st;
+    }
+    tails_args sb = c.sb;
+    if (pd.prepared && pf.prepared && pd.bundles_only && pf.bundles_only && pd.grid == pf.grid) {
+        const size_t lds = std::max(pd.lds_bytes, pf.lds_bytes);
+        sb.zero_next = t.d_counter_sets[t.cur_set ^ 1];  // (the next decode's counters: see tails_args)
+        sb.zero_words = uint32_t(t.zero_bytes / 4);
+        hipLaunchKernelGGL(pd.dict->kind == DINT_DICT_MULTI_PACKED ? decode_multi_index_pair_kernel : decode_single_index_pair_kernel,
+                           dim3(pd.grid), dim3(kBlockThreads), lds, s, pd.a, pf.a, sb);
+    } else {  // (a schedule was rebuilt under this call: a launch each)
+        if (pd.prepared) launch_prepared(pd);
+        if (pf.prepared) launch_prepared(pf);
+    }
+    if (pd.prepared) launch_stragglers(pd);
+    if (pf.prepared) launch_stragglers(pf);
+    if (pd.prepared) st = finish_deferred(pd);
+    if (st == DINT_OK && pf.prepared) st = finish_deferred(pf);
+    if (st != DINT_OK) return st;
+    HIP_TRY(hipGetLastError());
+    if (sb.zero_next != nullptr) {  // (the launch that clears the other set is on the stream)
+        t.set_clean[t.cur_set ^ 1] = true;
+        t.cur_set ^= 1;
+    }
+    if (c.covers) t.decodes += 1;
+    return DINT_OK;
+}
+
+// A launch each: docs parts of the full blocks through the DINT kernel (docIDs formed in the expansion); then, where they
+// end, their freqs parts; the short blocks inside the docs launch or through a launch of their own. From the second decode
+// of a table on (the side streams are the table's) the freqs launch runs beside the docs launch once its units are known,
+// and the short blocks' decoder beside both.
+int block_table_decode_each(block_decode& c) {
+    dint_block_table& t = c.t;
+    hipStream_t s = c.docs.stream;
     const size_t n_blocks = t.n_blocks;
     const uint32_t tb = 256, grid = uint32_t((n_blocks + tb - 1) / tb);
-    const uint32_t tgrid = uint32_t((t.n_tails + kTailLanes - 1) / kTailLanes);  // one wave per kTailLanes short blocks
-    // ONE fill: the two launches' counters. (The "left as gaps" flags need none: a flag is the decoding wave's own — cleared,
-    // perhaps set, looked at and cleared again by the wave that decodes the block, which turns the rare block it had to
-    // leave as gaps into docIDs on the spot: gaps_to_docids_here. Until round 4 the flags were cleared per call and a
-    // fix-up launch went through them behind the decode: two fills and a launch of 9 us behind a 20 us gap.)
-    dint_block_table& mt = const_cast<dint_block_table&>(t);
-    uint32_t* const d_counters = t.d_counter_sets[t.cur_set];
-    if (!t.set_clean[t.cur_set]) HIP_TRY(hipMemsetAsync(d_counters, 0, t.zero_bytes, s));
-    mt.set_clean[t.cur_set] = false;  // (in use from here on)
-    // docs parts of the full blocks through the DINT kernel (docIDs formed in the expansion); then, where they end,
-    // their freqs parts; the short blocks — both parts of a block in one lane — through the interpolative decoder
-    // What a decode learns for the next ones (exact spans, the freqs parts' units, the schedules) is kept only when
-    // this call decodes EVERY block: with an out_capacity below some block's end the kernels skip that block and leave
-    // its end offset unwritten — nothing may be derived from it.
-    const bool covers = out_capacity >= t.max_out_end;
-    const bool keep = t.owns_blocks && covers && t.decodes >= 1;  // (a one-shot table never reaches its second decode)
-    const bool concurrent_ok = opt(DINT_OPT_INDEX_CONCURRENT) != 0;
-    // From the second decode of a table on (the side streams are the table's): the freqs launch beside the docs launch once
-    // its units are known, and the short blocks' decoder beside both.
-    // (the short blocks inside the docs launch: tails_phase)
-    const bool inline_tails = t.n_tail_tickets != 0 && opt(DINT_OPT_INDEX_INLINE_TAILS) != 0;
-    auto bundles = [&](const sched_cache& c) { return c.valid && c.items_known && c.n_items <= index_straggler_limit(t.n_blocks); };
-    const bool pair = d_freqs && keep && concurrent_ok && t.freqs_units_ready && t.spans_exact && (tgrid == 0 || inline_tails) &&
-                      opt(DINT_OPT_INDEX_PAIR) != 0 && bundles(mt.docs_sched) && bundles(mt.freqs_sched) &&
-                      docs_dict->kind == freqs_dict->kind;
-    const bool side_freqs = d_freqs && t.freqs_units_ready && keep && concurrent_ok && !pair;
-    tails_args sb{};
-    if (inline_tails) {
-        sb.blocks = t.d_blocks;
-        sb.ids = t.d_tail_ids;
-        sb.tickets = t.d_tail_tickets;
-        sb.n_tickets = t.n_tail_tickets;
-        sb.docids = d_docids;
-        sb.freqs = d_freqs;
-        sb.out_capacity = out_capacity;
-    }
-    const bool side_tails = tgrid != 0 && keep && concurrent_ok && !inline_tails;
+    const bool with_freqs = c.freqs.out != nullptr;
+    const bool tails_apart = t.n_tails != 0 && !c.inline_tails;
+    const bool side_freqs = with_freqs && t.freqs_units_ready && c.concurrent;
+    const bool side_tails = tails_apart && c.concurrent;
     if (side_freqs || side_tails) {
-        if (!mt.side) {  // (all five or none: a table with half of them would trip over the missing ones on its next decode)
-            hipStream_t s1 = nullptr, s2 = nullptr;
-            hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-            int prio_low = 0, prio_high = 0;  // (the short blocks' few, long-lived waves first: the DINT launches fill in around them)
-            const bool ok = hip_ok(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking), "hipStreamCreateWithFlags") &&
-                            hip_ok(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high), "hipDeviceGetStreamPriorityRange") &&
-                            hip_ok(hipStreamCreateWithPriority(&s2, hipStreamNonBlocking, prio_high), "hipStreamCreateWithPriority") &&
-                            hip_ok(hipEventCreateWithFlags(&e0, hipEventDisableTiming), "hipEventCreateWithFlags") &&
-                            hip_ok(hipEventCreateWithFlags(&e1, hipEventDisableTiming), "hipEventCreateWithFlags") &&
-                            hip_ok(hipEventCreateWithFlags(&e2, hipEventDisableTiming), "hipEventCreateWithFlags");
-            if (!ok) {
-                if (s1) (void)hipStreamDestroy(s1);
-                if (s2) (void)hipStreamDestroy(s2);
-                for (hipEvent_t e : {e0, e1, e2})
-                    if (e) (void)hipEventDestroy(e);
-                return DINT_ERR_HIP;
-            }
-            mt.side = s1, mt.side2 = s2, mt.fork = e0, mt.join = e1, mt.join2 = e2;
-        }
-        HIP_TRY(hipEventRecord(mt.fork, s));  // (what the caller put on its stream before this call — the index — is there)
+        const int st = ensure_side_streams(t);
+        if (st != DINT_OK) return st;
+        HIP_TRY(hipEventRecord(t.fork, s));  // (what the caller put on its stream before this call — the index — is there)
     }
-    hipStream_t fs = s;  // the freqs launch's stream
     if (side_freqs) {
-        fs = mt.side;
-        HIP_TRY(hipStreamWaitEvent(fs, mt.fork, 0));
+        c.freqs.stream = t.side;  // (its counters were cleared on the caller's stream, before the fork)
+        HIP_TRY(hipStreamWaitEvent(t.side, t.fork, 0));
     }
+    hipStream_t fs = c.freqs.stream;
     if (side_tails) {
-        // (the short blocks' outputs are their own)
-        HIP_TRY(hipStreamWaitEvent(mt.side2, mt.fork, 0));
-        hipLaunchKernelGGL(interpolative_tails_kernel, dim3(tgrid), dim3(64), kTailLdsBytes, mt.side2, d_index, uint64_t(index_bytes), t.d_blocks,
-                           static_cast<const uint64_t*>(nullptr), t.d_tails, t.d_tails + n_blocks, d_docids, uint64_t(out_capacity),
-                           static_cast<uint64_t*>(nullptr), 0u, 1u, d_freqs, static_cast<uint8_t*>(nullptr), uint64_t(0));
-        HIP_TRY(hipEventRecord(mt.join2, mt.side2));
+        HIP_TRY(hipStreamWaitEvent(t.side2, t.fork, 0));
+        launch_short_blocks(t, t.side2, c);
+        HIP_TRY(hipEventRecord(t.join2, t.side2));
     }
-    // ONE launch for the docs parts, the short blocks and the freqs parts (decode_*_index_pair_kernel) once both kept schedules
-    // are known to be bundles and nothing else (or nearly: the stragglers' small launches follow).
-    if (pair) {
-        deferred_launch pd, pf;
-        int st2 = launch_decode(docs_dict, d_index, index_bytes, t.d_units, n_blocks, d_docids, out_capacity, t.d_ends, s, 1, t.d_spans, 0,
-                                t.d_bases, t.d_gaps_left, &mt.docs_sched, 2, nullptr, nullptr, &pd, d_counters);
-        if (st2 != DINT_OK) return st2;
-        st2 = launch_decode(freqs_dict, d_index, index_bytes, t.d_funits, n_blocks, d_freqs, out_capacity, nullptr, s, 1, t.d_fspans, 1,
-                            nullptr, nullptr, &mt.freqs_sched, 2, nullptr, nullptr, &pf, d_counters + size_t(kQueueLines) * kQueueStride);
-        if (st2 != DINT_OK) {
-            if (pd.prepared) (void)finish_deferred(docs_dict, pd, s);
-            return st2;
-        }
-        if (pd.prepared && pf.prepared && pd.bundles_only && pf.bundles_only && pd.grid == pf.grid) {
-            const size_t lds = std::max(pd.lds_bytes, pf.lds_bytes);
-            sb.zero_next = t.d_counter_sets[t.cur_set ^ 1];  // (the next decode's counters: see tails_args)
-            sb.zero_words = uint32_t(t.zero_bytes / 4);
-            if (docs_dict->kind == DINT_DICT_MULTI_PACKED)
-                hipLaunchKernelGGL(decode_multi_index_pair_kernel, dim3(pd.grid), dim3(kBlockThreads), lds, s, pd.a, pf.a, sb);
-            else
-                hipLaunchKernelGGL(decode_single_index_pair_kernel, dim3(pd.grid), dim3(kBlockThreads), lds, s, pd.a, pf.a, sb);
-        } else {  // (a schedule was rebuilt under this call: a launch each, as before)
-            if (pd.prepared) launch_prepared(docs_dict, pd, s, inline_tails ? &sb : nullptr);
-            if (pf.prepared) launch_prepared(freqs_dict, pf, s, nullptr);
-        }
-        if (pd.prepared) launch_stragglers(docs_dict, pd, s);
-        if (pf.prepared) launch_stragglers(freqs_dict, pf, s);
-        if (pd.prepared) st2 = finish_deferred(docs_dict, pd, s);
-        if (st2 == DINT_OK && pf.prepared) st2 = finish_deferred(freqs_dict, pf, s);
-        if (st2 != DINT_OK) return st2;
-        HIP_TRY(hipGetLastError());
-        if (sb.zero_next != nullptr) {  // (the launch that clears the other set is on the stream)
-            mt.set_clean[t.cur_set ^ 1] = true;
-            mt.cur_set ^= 1;
-        }
-        if (covers) mt.decodes += 1;
-        return DINT_OK;
-    }
-    int st = launch_decode(docs_dict, d_index, index_bytes, t.d_units, n_blocks, d_docids, out_capacity, t.d_ends, s, 1, t.d_spans, 0,
-                           t.d_bases, t.d_gaps_left, keep ? &mt.docs_sched : nullptr, 2, nullptr, inline_tails ? &sb : nullptr, nullptr, d_counters);
     auto fail = [&](int code) {  // (nothing of this call may still be running on the table's streams when the caller hears of it)
-        if (side_freqs) (void)hipStreamSynchronize(mt.side);
-        if (side_tails) (void)hipStreamSynchronize(mt.side2);
+        if (side_freqs) (void)hipStreamSynchronize(t.side);
+        if (side_tails) (void)hipStreamSynchronize(t.side2);
         return code;
     };
+    int st = launch_decode(c.docs);
     if (st != DINT_OK) return fail(st);
-    if (!t.spans_exact && covers) {  // (stream-ordered: the next decode on this table finds the exact spans)
+    if (!t.spans_exact && c.covers) {  // (stream-ordered: the next decode on this table finds the exact spans)
         hipLaunchKernelGGL(exact_spans_kernel, dim3(grid), dim3(tb), 0, s, t.d_units, t.d_ends, uint64_t(n_blocks), t.d_spans);
-        mt.spans_exact = true;
+        t.spans_exact = true;
     }
-    if (d_freqs) {
+    if (with_freqs) {
         if (!t.freqs_units_ready) {
             // (a skipped block's end offset is zero: its freqs unit then starts at the buffer's first byte and is
             // skipped in turn — same out_off, same capacity)
             hipLaunchKernelGGL(blocks_to_units_kernel, dim3(grid), dim3(tb), 0, s, t.d_blocks, t.d_ends, uint64_t(n_blocks),
-                               uint64_t(index_bytes), t.d_funits, t.d_fspans, static_cast<uint32_t*>(nullptr));
-            mt.freqs_units_ready = t.owns_blocks && covers;
+                               uint64_t(c.docs.enc_bytes), t.d_funits, t.d_fspans, static_cast<uint32_t*>(nullptr));
+            t.freqs_units_ready = t.owns_blocks && c.covers;
         }
-        // (freq = decoded value + 1, dict_posting_list.hpp:164-169: added where the values are stored)
-        st = launch_decode(freqs_dict, d_index, index_bytes, t.d_funits, n_blocks, d_freqs, out_capacity, nullptr, fs, 1, t.d_fspans, 1,
-                           nullptr, nullptr, keep ? &mt.freqs_sched : nullptr, 2, nullptr, nullptr, nullptr,
-                           d_counters + size_t(kQueueLines) * kQueueStride);  // (cleared on the caller's stream, before the fork)
+        st = launch_decode(c.freqs);
         if (st != DINT_OK) return fail(st);
-        if (fs != s) HIP_TRY(hipEventRecord(mt.join, fs));
+        if (fs != s) HIP_TRY(hipEventRecord(t.join, fs));
     }
-    // (the short blocks by a launch of their own, where they are not inside the docs launch or beside it)
     if (side_tails) {
-        HIP_TRY(hipStreamWaitEvent(s, mt.join2, 0));
-    } else if (tgrid && !inline_tails)
-        hipLaunchKernelGGL(interpolative_tails_kernel, dim3(tgrid), dim3(64), kTailLdsBytes, s, d_index, uint64_t(index_bytes), t.d_blocks,
-                           static_cast<const uint64_t*>(nullptr), t.d_tails, t.d_tails + n_blocks, d_docids, uint64_t(out_capacity),
-                           static_cast<uint64_t*>(nullptr), 0u, 1u, d_freqs, static_cast<uint8_t*>(nullptr), uint64_t(0));
+        HIP_TRY(hipStreamWaitEvent(s, t.join2, 0));
+    } else if (tails_apart)
+        launch_short_blocks(t, s, c);
     HIP_TRY(hipGetLastError());
-    if (fs != s) HIP_TRY(hipStreamWaitEvent(s, mt.join, 0));  // (everything behind this call on the caller's stream sees the freqs)
-    // Once per kept schedule (the decode that built it): how many work items its unit queue got. None — every full block
-    // fits a tile — and the later decodes run the kernels compiled without the queue.
-    if (keep) {
-        auto learn = [&](sched_cache& c, hipStream_t st) -> int {
-            if (!c.valid || c.items_known) return DINT_OK;
-            sched_layout L(n_blocks);
-            L.place(c.d_mem);
-            uint32_t n_items = 0;
-            HIP_TRY(hipMemcpyAsync(&n_items, L.d_n_items, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            c.n_items = n_items;
-            c.items_known = true;
-            return DINT_OK;
-        };
-        int ls = learn(mt.docs_sched, s);
-        if (ls == DINT_OK && d_freqs) ls = learn(mt.freqs_sched, fs);
-        if (ls != DINT_OK) return fail(ls);
+    if (fs != s) HIP_TRY(hipStreamWaitEvent(s, t.join, 0));  // (everything behind this call on the caller's stream sees the freqs)
+    // Once per kept schedule (the decode that built it): how many work items its unit queue got.
+    if (c.keep) {
+        st = read_queue_items(t.docs_sched, n_blocks, s);
+        if (st == DINT_OK && with_freqs) st = read_queue_items(t.freqs_sched, n_blocks, fs);
+        if (st != DINT_OK) return fail(st);
     }
-    if (covers) mt.decodes += 1;
+    if (c.covers) t.decodes += 1;
     return DINT_OK;
+}
+
+// docs parts -> docIDs, freqs parts -> freqs: launches only, nothing waited for
+int block_table_decode(const dint_dict* docs_dict, const dint_dict* freqs_dict, const uint8_t* d_index, size_t index_bytes,
+                       dint_block_table& t, uint32_t* d_docids, uint32_t* d_freqs, size_t out_capacity, hipStream_t s) {
+    // ONE fill: the two launches' counters. (The "left as gaps" flags need none: a flag is the decoding wave's own — cleared,
+    // perhaps set, looked at and cleared again by the wave that decodes the block, which turns the rare block it had to
+    // leave as gaps into docIDs on the spot: gaps_to_docids_here. Until round 4 the flags were cleared per call and a
+    // fix-up launch went through them behind the decode: two fills and a launch of 9 us behind a 20 us gap.)
+    uint32_t* const d_counters = t.d_counter_sets[t.cur_set];
+    if (!t.set_clean[t.cur_set]) HIP_TRY(hipMemsetAsync(d_counters, 0, t.zero_bytes, s));
+    t.set_clean[t.cur_set] = false;  // (in use from here on)
+    block_decode c(t);
+    // What a decode learns for the next ones (exact spans, the freqs parts' units, the schedules) is kept only when
+    // this call decodes EVERY block: with an out_capacity below some block's end the kernels skip that block and leave
+    // its end offset unwritten — nothing may be derived from it.
+    c.covers = out_capacity >= t.max_out_end;
+    c.keep = t.owns_blocks && c.covers && t.decodes >= 1;  // (a one-shot table never reaches its second decode)
+    const bool concurrent_ok = opt(DINT_OPT_INDEX_CONCURRENT) != 0;
+    c.concurrent = c.keep && concurrent_ok;
+    c.inline_tails = t.n_tail_tickets != 0 && opt(DINT_OPT_INDEX_INLINE_TAILS) != 0;
+    if (c.inline_tails) {
+        c.sb.blocks = t.d_blocks, c.sb.ids = t.d_tail_ids, c.sb.tickets = t.d_tail_tickets, c.sb.n_tickets = t.n_tail_tickets;
+        c.sb.docids = d_docids, c.sb.freqs = d_freqs, c.sb.out_capacity = out_capacity;
+    }
+    decode_request blocks;  // what the two launches share
+    blocks.enc = d_index, blocks.enc_bytes = index_bytes, blocks.n_units = t.n_blocks, blocks.out_capacity = out_capacity;
+    blocks.stream = s, blocks.only_full = 1;
+    c.docs = c.freqs = blocks;
+    c.docs.dict = docs_dict, c.docs.units = t.d_units, c.docs.spans = t.d_spans, c.docs.out = d_docids;
+    c.docs.cache = c.keep ? &t.docs_sched : nullptr, c.docs.own_counters = d_counters;
+    c.docs.end_off = t.d_ends, c.docs.unit_base = t.d_bases, c.docs.gaps_left = t.d_gaps_left;
+    c.docs.short_blocks = c.inline_tails ? &c.sb : nullptr;
+    c.freqs.dict = freqs_dict, c.freqs.units = t.d_funits, c.freqs.spans = t.d_fspans, c.freqs.out = d_freqs;
+    c.freqs.cache = c.keep ? &t.freqs_sched : nullptr, c.freqs.own_counters = d_counters + size_t(kQueueLines) * kQueueStride;
+    c.freqs.plus_one = 1;  // (freq = decoded value + 1, dict_posting_list.hpp:164-169: added where the values are stored)
+    const bool pair = d_freqs && c.concurrent && t.freqs_units_ready && t.spans_exact && (t.n_tails == 0 || c.inline_tails) &&
+                      opt(DINT_OPT_INDEX_PAIR) != 0 && schedule_is_bundles(t.docs_sched, t.n_blocks) &&
+                      schedule_is_bundles(t.freqs_sched, t.n_blocks) && docs_dict->kind == freqs_dict->kind;
+    return pair ? block_table_decode_pair(c) : block_table_decode_each(c);
 }
 }  // namespace
 
@@ -422,9 +442,8 @@ int dint_block_table_learn(dint_block_table* table, const dint_dict* docs_dict, 
 int dint_block_table_ready(const dint_block_table* t, int with_freqs) {
     if (!t) return 0;
     if (t->n_blocks == 0) return 1;
-    auto bundles = [&](const sched_cache& c) { return c.valid && c.items_known && c.n_items <= index_straggler_limit(t->n_blocks); };
-    if (!t->owns_blocks || t->decodes < 1 || !t->spans_exact || !bundles(t->docs_sched)) return 0;
-    return !with_freqs || (t->freqs_units_ready && bundles(t->freqs_sched)) ? 1 : 0;
+    if (!t->owns_blocks || t->decodes < 1 || !t->spans_exact || !schedule_is_bundles(t->docs_sched, t->n_blocks)) return 0;
+    return !with_freqs || (t->freqs_units_ready && schedule_is_bundles(t->freqs_sched, t->n_blocks)) ? 1 : 0;
 }
 
 int dint_block_table_info_get(const dint_block_table* t, dint_block_table_info* info) {

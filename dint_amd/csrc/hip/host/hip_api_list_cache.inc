@@ -92,7 +92,10 @@ int dint_list_cache_create(const dint_dict* docs_c, const dint_dict* freqs_dict,
                        uint64_t(padded), d_units, d_spans, static_cast<uint32_t*>(nullptr));
     // docs parts as the Coder returns them (gaps), where they end; then the freqs parts from there
     dd->host_sched.valid = false;
-    st = launch_decode(docs_c, d_index, padded, d_units, n_blocks, d_gaps, total, d_dends, s, 1, d_spans, 0, nullptr, nullptr, &dd->host_sched);
+    decode_request docs;
+    docs.dict = docs_c, docs.enc = d_index, docs.enc_bytes = padded, docs.n_units = n_blocks, docs.out_capacity = total, docs.stream = s;
+    docs.only_full = 1, docs.units = d_units, docs.spans = d_spans, docs.out = d_gaps, docs.end_off = d_dends, docs.cache = &dd->host_sched;
+    st = launch_decode(docs);
     if (st != DINT_OK) return fail(st);
     hipLaunchKernelGGL(interpolative_tails_kernel, dim3(tgrid), dim3(64), kTailLdsBytes, s, d_index, uint64_t(padded), d_blocks,
                        static_cast<const uint64_t*>(nullptr), d_tails, d_tails + n_blocks, d_gaps, uint64_t(total), d_dends, 0u);
@@ -100,8 +103,10 @@ int dint_list_cache_create(const dint_dict* docs_c, const dint_dict* freqs_dict,
         hipLaunchKernelGGL(blocks_to_units_kernel, dim3(grid), dim3(tb), 0, s, d_blocks, d_dends, uint64_t(n_blocks), uint64_t(padded), d_funits,
                            d_fspans, static_cast<uint32_t*>(nullptr));
         fdd->host_sched.valid = false;  // (the freqs dictionary's own schedule memory)
-        st = launch_decode(freqs_dict, d_index, padded, d_funits, n_blocks, d_freqs, total, d_fends, s, 1, d_fspans, 0, nullptr, nullptr,
-                           &fdd->host_sched);
+        decode_request freqs = docs;
+        freqs.dict = freqs_dict;
+        freqs.units = d_funits, freqs.spans = d_fspans, freqs.out = d_freqs, freqs.end_off = d_fends, freqs.cache = &fdd->host_sched;
+        st = launch_decode(freqs);
         if (st != DINT_OK) return fail(st);
         hipLaunchKernelGGL(interpolative_tails_kernel, dim3(tgrid), dim3(64), kTailLdsBytes, s, d_index, uint64_t(padded), d_blocks, d_dends, d_tails,
                            d_tails + n_blocks, d_freqs, uint64_t(total), d_fends, 0u);

@@ -62,6 +62,16 @@ int dint_query_index_create(const dint_dict* docs_dict, const uint8_t* d_index, 
     return DINT_OK;
 }
 
+// The docs launch of `n_pages` prepared pages (units, spans, bases, left-as-gaps flags in the handle's workspaces), 256
+// slots per page
+static decode_request pages_request(dint_query_index* qi, size_t n_pages, uint32_t* d_docs, hipStream_t s) {
+    decode_request r;
+    r.dict = qi->docs, r.enc = qi->d_index, r.enc_bytes = qi->index_bytes, r.units = qi->units.p, r.n_units = n_pages;
+    r.out = d_docs, r.out_capacity = size_t(n_pages) * kPageSlots, r.stream = s;
+    r.only_full = 1, r.spans = qi->spans.p, r.unit_base = qi->bases.p, r.gaps_left = qi->gaps_left.p;
+    return r;
+}
+
 // The pages of `sub` decoded, 256 slots per page, no sync: docs parts -> docIDs in d_docs (formed in the decode
 // kernels' expansion, like dint_decode_block_table) and, with a freqs dictionary, freqs parts -> d_freqs.
 static int decode_pages(dint_query_index* qi, size_t n_pages, uint32_t* d_docs, const dint_dict* freqs_dict, uint32_t* d_freqs,
@@ -78,13 +88,16 @@ static int decode_pages(dint_query_index* qi, size_t n_pages, uint32_t* d_docs, 
                        uint64_t(n_pages), uint64_t(qi->index_bytes), qi->units.p, qi->spans.p, qi->bases.p);
     hipLaunchKernelGGL(collect_tails_kernel, dim3(grid), dim3(tb), 0, s, qi->sub.p, uint64_t(n_pages), qi->tails.p,
                        qi->tails.p + n_pages);
-    int st = launch_decode(qi->docs, qi->d_index, qi->index_bytes, qi->units.p, n_pages, d_docs, cap, qi->ends.p, s, 1, qi->spans.p, 0,
-                           qi->bases.p, qi->gaps_left.p);
+    decode_request docs = pages_request(qi, n_pages, d_docs, s);
+    docs.end_off = qi->ends.p;
+    int st = launch_decode(docs);
     if (st != DINT_OK) return st;
     if (freqs_dict) {  // freqs parts of the full blocks: from where their docs parts ended
         hipLaunchKernelGGL(blocks_to_units_kernel, dim3(grid), dim3(tb), 0, s, qi->sub.p, qi->ends.p, uint64_t(n_pages),
                            uint64_t(qi->index_bytes), qi->units.p, qi->spans.p, static_cast<uint32_t*>(nullptr));
-        st = launch_decode(freqs_dict, qi->d_index, qi->index_bytes, qi->units.p, n_pages, d_freqs, cap, nullptr, s, 1, qi->spans.p, 1);
+        decode_request freqs = pages_request(qi, n_pages, d_freqs, s);
+        freqs.dict = freqs_dict, freqs.plus_one = 1, freqs.unit_base = nullptr, freqs.gaps_left = nullptr;
+        st = launch_decode(freqs);
         if (st != DINT_OK) return st;
     }
     // (the grid is sized for "every page is a short block"; the waves past the list's end leave at once)
@@ -145,12 +158,8 @@ static int decode_pages_lean(dint_query_index* qi, const uint32_t* d_ids, const 
     a.out = d_docs;
     a.out_capacity = uint64_t(bound) * kPageSlots;
     a.gaps_left = qi->gaps_left.p;
-    const uint64_t blocks_needed = (uint64_t(bound) + kWavesPerBlock - 1) / kWavesPerBlock;
-    const uint32_t grid = uint32_t(std::min<uint64_t>(blocks_needed, std::max<uint32_t>(1, qi->docs->compute_units) * kBlocksPerCU));
-    a.queue = ctrl + kCtrlQueueAt;
-    a.chunk_queue = a.queue + kQueueShards * kQueueStride;
-    a.clock = reinterpret_cast<uint64_t*>(a.chunk_queue + kClockWordAt);
-    a.n_shards = std::min<uint32_t>(kQueueShards, grid);
+    const uint32_t grid = decode_grid(qi->docs, bound);
+    bind_counters(a, ctrl + kCtrlQueueAt, grid);
     query_pages qp{};
     if (search) qp = *search;  // (the first round's search, for the candidate pages)
     qp.blocks = qi->d_blocks;
@@ -184,8 +193,9 @@ static int decode_pages_counted(dint_query_index* qi, const uint32_t* d_ids, con
     hipLaunchKernelGGL(prepare_pages_kernel, dim3(uint32_t((bound + tb - 1) / tb)), dim3(tb), 0, s, qi->d_blocks, uint64_t(qi->n_blocks),
                        uint64_t(qi->index_bytes), d_ids, d_count, uint64_t(bound), qi->sub.p, qi->units.p, qi->spans.p, qi->bases.p,
                        qi->gaps_left.p, qi->tails.p, d_n_tails);
-    int st = launch_decode(qi->docs, qi->d_index, qi->index_bytes, qi->units.p, bound, d_docs, cap, nullptr, s, 1, qi->spans.p, 0,
-                           qi->bases.p, qi->gaps_left.p, nullptr, 2048, ctrl + kCtrlQueueAt);
+    decode_request docs = pages_request(qi, bound, d_docs, s);
+    docs.schedule_from = 2048, docs.zeroed_queue = ctrl + kCtrlQueueAt;
+    int st = launch_decode(docs);
     if (st != DINT_OK) return st;
     // (the grid is sized for "every page is a short block": the waves with nothing to do leave at once)
     hipLaunchKernelGGL(fix_pages_kernel, dim3(uint32_t((bound + kTailLanes - 1) / kTailLanes)), dim3(64), kTailLdsBytes, s, qi->d_index,

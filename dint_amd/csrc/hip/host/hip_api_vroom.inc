@@ -1,63 +1,86 @@
-// Part of dint_hip.hip (one translation unit; included from there, in order): extern "C": the vroom decode — bundle schedule, launch_decode, dint_decode_units, prepared unit tables (single_dint::decode / multi_opt_dint::decode, vroom_env/dint_codecs.hpp:37-107, 521-619).
-// workspace of a schedule: [unit records 16 B x n][chunk bases 16 B x chunks][items u32 x n][block counts/offsets u32 x blocks]
-// [n_items u32][sched u8 x n][item counts u8 x n]
-struct sched_layout {
-    size_t n_units, n_blocks, n_chunks, need;
+// Part of dint_hip.hip (one translation unit; included from there, in order): extern "C": the vroom decode — bundle schedule, launch_decode and its stages, dint_decode_units, prepared unit tables (single_dint::decode / multi_opt_dint::decode, vroom_env/dint_codecs.hpp:37-107, 521-619).
+constexpr size_t kCounterBytes = size_t(kQueueLines) * kQueueStride * 4;  // a launch's counter lines
+// The two schedule workspaces (sched_layout, split_layout: hip_stage_layout.inc) sized by the kernels' constants and placed
+// in their memory.
+struct placed_schedule : sched_layout {
     u32x4* d_urec = nullptr;
     uint64_t* d_cbase = nullptr;
     uint32_t *d_items = nullptr, *d_block = nullptr, *d_n_items = nullptr;
     uint8_t *d_sch = nullptr, *d_item_cnt = nullptr;
-    explicit sched_layout(size_t n) : n_units(n), n_blocks((n + 255) / 256), n_chunks((n + kChunkUnits - 1) / kChunkUnits) {
-        need = 16 * n_units + 16 * n_chunks + 4 * n_units + 4 * n_blocks + 4 + 2 * n_units;
-    }
+    explicit placed_schedule(size_t n) : sched_layout(n, kChunkUnits) {}
     void place(void* mem) {
-        d_urec = reinterpret_cast<u32x4*>(mem);
-        d_cbase = reinterpret_cast<uint64_t*>(d_urec + n_units);
-        d_items = reinterpret_cast<uint32_t*>(d_cbase + 2 * n_chunks);
-        d_block = d_items + n_units;
-        d_n_items = d_block + n_blocks;
-        d_sch = reinterpret_cast<uint8_t*>(d_n_items + 1);
-        d_item_cnt = d_sch + n_units;
+        d_urec = at_byte<u32x4>(mem, urec);
+        d_cbase = at_byte<uint64_t>(mem, cbase);
+        d_items = at_byte<uint32_t>(mem, items);
+        d_block = at_byte<uint32_t>(mem, block);
+        d_n_items = at_byte<uint32_t>(mem, n_items);
+        d_sch = at_byte<uint8_t>(mem, sch);
+        d_item_cnt = at_byte<uint8_t>(mem, item_cnt);
     }
 };
-
-// workspace of a kept schedule's cut units (sched_cache::d_split)
-struct split_layout {
-    size_t n_items, n_sub, n_chunks, need;
+struct placed_split : split_layout {
     u32x4* d_urec = nullptr;
-    uint64_t *d_cbase = nullptr, *d_end = nullptr;
+    uint64_t *d_cbase = nullptr, *d_end = nullptr, *d_clock = nullptr;
     uint32_t *d_left = nullptr, *d_n_left = nullptr, *d_counters = nullptr;
-    explicit split_layout(size_t items) : n_items(items), n_sub(2 * items), n_chunks((2 * items + kChunkUnits - 1) / kChunkUnits) {
-        need = 16 * n_sub + 16 * n_chunks + 8 * n_sub + 4 * n_items + 256 + size_t(kQueueLines) * kQueueStride * 4;
-    }
+    explicit placed_split(size_t items) : split_layout(items, kChunkUnits, kCounterBytes) {}
     void place(void* mem) {
-        d_urec = reinterpret_cast<u32x4*>(mem);
-        d_cbase = reinterpret_cast<uint64_t*>(d_urec + n_sub);
-        d_end = d_cbase + 2 * n_chunks;
-        d_left = reinterpret_cast<uint32_t*>(d_end + n_sub);
-        d_n_left = d_left + n_items;  // (+ the sub launch's clock word behind it: 256 bytes in all)
-        d_counters = d_n_left + 64;
+        d_urec = at_byte<u32x4>(mem, urec);
+        d_cbase = at_byte<uint64_t>(mem, cbase);
+        d_end = at_byte<uint64_t>(mem, end);
+        d_left = at_byte<uint32_t>(mem, left);
+        d_n_left = at_byte<uint32_t>(mem, n_left);
+        d_clock = at_byte<uint64_t>(mem, clock);
+        d_counters = at_byte<uint32_t>(mem, counters);
     }
 };
 
-static void run_schedule_kernels(const dint_dict* dd, const uint8_t* d_enc, size_t enc_bytes, const dint_unit* d_units, size_t n_units,
-                                 size_t out_capacity, uint32_t only_full, const uint32_t* d_spans, const sched_layout& L, hipStream_t s) {
-    hipLaunchKernelGGL(bundle_schedule_kernel, dim3(uint32_t(L.n_blocks)), dim3(256), 0, s, d_units, d_spans, uint64_t(n_units), d_enc,
-                       uint64_t(enc_bytes), uint64_t(out_capacity), only_full, uint32_t(dd->kind == DINT_DICT_MULTI_PACKED),
-                       uint32_t(dd->kind == DINT_DICT_MULTI_PACKED || only_full != 0), L.d_sch,
-                       L.d_block, L.d_urec, L.d_cbase);
-    if (dd->kind == DINT_DICT_MULTI_PACKED || only_full != 0)  // (the chunked schedules: first fit)
-        hipLaunchKernelGGL(bundle_pack_kernel, dim3(uint32_t((L.n_chunks + 63) / 64)), dim3(64), 0, s, L.d_urec, uint64_t(n_units));
+struct deferred_launch;
+// What a decode launch is asked for. Everything optional is null or 0.
+struct decode_request {
+    const dint_dict* dict = nullptr;
+    const uint8_t* enc = nullptr;
+    size_t enc_bytes = 0;
+    const dint_unit* units = nullptr;
+    size_t n_units = 0;
+    uint32_t* out = nullptr;
+    size_t out_capacity = 0;
+    uint64_t* end_off = nullptr;
+    hipStream_t stream = nullptr;
+    // an in-index launch (any of these set: the kernels compiled for blocks, docIDs, freqs + 1; the vroom kernels carry none of it)
+    uint32_t only_full = 0;
+    const uint32_t* spans = nullptr;
+    uint32_t plus_one = 0;
+    const uint32_t* unit_base = nullptr;
+    uint8_t* gaps_left = nullptr;
+    const tails_args* short_blocks = nullptr;  // (a docs launch may bring its table's short blocks along: tails_phase)
+    // the workspace
+    sched_cache* cache = nullptr;  // a kept schedule (rebuilt under the call where it does not match); null: one of the dictionary's
+    // a caller that decodes a handful of units at a time — a query's pages — does without the three schedule launches: with
+    // fewer units than waves nothing is gained by sharing tiles
+    size_t schedule_from = 2;
+    uint32_t* zeroed_queue = nullptr;  // the caller's zeroed counters: an unscheduled launch is then the lean form
+    // kQueueLines lines the caller has zeroed on this stream — a block table clears both launches' counters with ONE fill;
+    // the slot still carries the launch's events
+    uint32_t* own_counters = nullptr;
+    deferred_launch* defer = nullptr;  // prepared, not launched: the caller launches, then finish_deferred
+};
+
+static void run_schedule_kernels(const decode_request& r, const placed_schedule& L, hipStream_t s) {
+    const bool chunked = r.dict->kind == DINT_DICT_MULTI_PACKED || r.only_full != 0;
+    hipLaunchKernelGGL(bundle_schedule_kernel, dim3(uint32_t(L.n_blocks)), dim3(256), 0, s, r.units, r.spans, uint64_t(r.n_units), r.enc,
+                       uint64_t(r.enc_bytes), uint64_t(r.out_capacity), r.only_full, uint32_t(r.dict->kind == DINT_DICT_MULTI_PACKED),
+                       uint32_t(chunked), L.d_sch, L.d_block, L.d_urec, L.d_cbase);
+    if (chunked)  // (the chunked schedules: first fit)
+        hipLaunchKernelGGL(bundle_pack_kernel, dim3(uint32_t((L.n_chunks + 63) / 64)), dim3(64), 0, s, L.d_urec, uint64_t(r.n_units));
     hipLaunchKernelGGL(bundle_offsets_kernel, dim3(1), dim3(1024), 0, s, L.d_block, uint32_t(L.n_blocks), L.d_n_items);
-    hipLaunchKernelGGL(bundle_items_kernel, dim3(uint32_t(L.n_blocks)), dim3(256), 0, s, L.d_sch, uint64_t(n_units), L.d_block, L.d_items,
+    hipLaunchKernelGGL(bundle_items_kernel, dim3(uint32_t(L.n_blocks)), dim3(256), 0, s, L.d_sch, uint64_t(r.n_units), L.d_block, L.d_items,
                        L.d_item_cnt);
 }
 
-// (Re)build a kept schedule on stream `s` and remember what it was built from.
-static int build_schedule(const dint_dict* dd, const uint8_t* d_enc, size_t enc_bytes, const dint_unit* d_units, size_t n_units,
-                          size_t out_capacity, uint32_t only_full, const uint32_t* d_spans, sched_cache* cache, hipStream_t s) {
-    HIP_TRY(hipSetDevice(dd->device));
-    sched_layout L(n_units);
+// (Re)build the schedule of `r` in `cache` on stream `s` and remember what it was built from.
+static int build_schedule(const decode_request& r, sched_cache* cache, hipStream_t s) {
+    HIP_TRY(hipSetDevice(r.dict->device));
+    placed_schedule L(r.n_units);
     cache->valid = false;
     if (cache->mem_bytes < L.need) {
         if (cache->d_mem) HIP_TRY(hipFree(cache->d_mem));  // (hipFree waits for the launches that read it)
@@ -67,54 +90,124 @@ static int build_schedule(const dint_dict* dd, const uint8_t* d_enc, size_t enc_
         cache->mem_bytes = L.need;
     }
     L.place(cache->d_mem);
-    run_schedule_kernels(dd, d_enc, enc_bytes, d_units, n_units, out_capacity, only_full, d_spans, L, s);
+    run_schedule_kernels(r, L, s);
     HIP_TRY(hipGetLastError());
     cache->valid = true;
     cache->items_known = false;
     cache->split_ready = false;
-    cache->dict = dd, cache->d_enc = d_enc, cache->enc_bytes = enc_bytes, cache->d_units = d_units, cache->n_units = n_units;
-    cache->d_spans = d_spans, cache->out_capacity = out_capacity, cache->only_full = only_full;
+    cache->dict = r.dict, cache->d_enc = r.enc, cache->enc_bytes = r.enc_bytes, cache->d_units = r.units, cache->n_units = r.n_units;
+    cache->d_spans = r.spans, cache->out_capacity = r.out_capacity, cache->only_full = r.only_full;
     return DINT_OK;
 }
 
-// A launch prepared — queue slot taken and zeroed, schedule validated, start event recorded — but left to the caller
-// to put on the stream (block_table_decode: the docs and the freqs launch of an index as ONE kernel), then finish_deferred.
+// How many work items the unit queue of a kept schedule got, read back once (waits for `s`, the stream it was built on).
+// None: the kernels compiled without the queue serve it.
+static int read_queue_items(sched_cache& c, size_t n_units, hipStream_t s) {
+    if (!c.valid || c.items_known) return DINT_OK;
+    placed_schedule L(n_units);
+    L.place(c.d_mem);
+    uint32_t n_items = 0;
+    HIP_TRY(hipMemcpyAsync(&n_items, L.d_n_items, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    c.n_items = n_items;
+    c.items_known = true;
+    return DINT_OK;
+}
+
+// The one description of a decode launch: what launch_decode prepares — arguments, grid, queue slot, the plan — and
+// launch_prepared, launch_stragglers and finish_deferred consume. A DEFERRED launch is handed to the caller prepared (slot
+// taken and zeroed, schedule validated, start event recorded) to be put on the stream by it: block_table_decode's docs
+// and freqs launch of an index as ONE kernel.
 struct deferred_launch {
+    const dint_dict* dict = nullptr;
+    hipStream_t stream = nullptr;
     decode_args a{};
-    uint32_t grid = 0, slot = 0, stragglers = 0;
+    tails_args short_blocks{};
+    uint32_t grid = 0, slot = 0;
+    uint32_t stragglers = 0;    // a kept schedule that left a few units to the queue: that many, decoded by a second, small launch
     size_t lds_bytes = 0;
-    bool bundles_only = false, index_launch = false, prepared = false, deferred = false;
+    bool bundles_only = false;  // a kept schedule known to have left the unit queue empty (or to the stragglers' launch)
+    bool index_launch = false, prepared = false, deferred = false;
 };
-static void launch_stragglers(const dint_dict* dd, const deferred_launch& d, hipStream_t s) {
+
+static uint32_t decode_grid(const dint_dict* dd, size_t n_units) {
+    const uint64_t blocks_needed = (uint64_t(n_units) + kWavesPerBlock - 1) / kWavesPerBlock;
+    return uint32_t(std::min<uint64_t>(blocks_needed, std::max<uint32_t>(1, dd->compute_units) * kBlocksPerCU));
+}
+static size_t decode_lds_bytes(const dint_dict* dd) {
+    return (size_t(dd->view.hot_words) + kClassTableWords + kWavesPerBlock * kScratchWords) * 4;
+}
+// The counters of a launch of `grid` workgroups in a (zeroed) counter area: unit-queue shards | the clock's line, the bundle
+// path's chunk counters behind it.
+static void bind_counters(decode_args& a, uint32_t* counters, uint32_t grid) {
+    a.queue = counters;
+    a.chunk_queue = a.queue + kQueueShards * kQueueStride;
+    a.clock = reinterpret_cast<uint64_t*>(a.chunk_queue + kClockWordAt);
+    a.n_shards = std::min<uint32_t>(kQueueShards, grid);
+}
+
+static void launch_prepared(const deferred_launch& d) {
+    const bool multi = d.dict->kind == DINT_DICT_MULTI_PACKED;
+    const dim3 grid(d.grid), block(kBlockThreads);
+    if (d.index_launch && d.bundles_only)
+        hipLaunchKernelGGL(multi ? decode_multi_index_bundles_kernel : decode_single_index_bundles_kernel, grid, block, d.lds_bytes, d.stream, d.a, d.short_blocks);
+    else if (d.index_launch)
+        hipLaunchKernelGGL(multi ? decode_multi_index_kernel : decode_single_index_kernel, grid, block, d.lds_bytes, d.stream, d.a, d.short_blocks);
+    else if (multi && d.bundles_only)
+        hipLaunchKernelGGL(decode_multi_bundles_kernel, grid, block, d.lds_bytes, d.stream, d.a);
+    else
+        hipLaunchKernelGGL(multi ? decode_multi_kernel : decode_single_kernel, grid, block, d.lds_bytes, d.stream, d.a);
+}
+// The few units a bundles-only launch left: a small launch of the general kernel behind it, which skips the chunks.
+static void launch_stragglers(const deferred_launch& d) {
     if (!d.stragglers) return;
     decode_args b = d.a;
     b.urec = nullptr;  // (says: the unit queue only — the chunks are the first launch's)
     const uint32_t grid2 = std::min<uint32_t>(d.grid, (d.stragglers + kWavesPerBlock - 1) / kWavesPerBlock);
     b.n_shards = std::min<uint32_t>(kQueueShards, grid2);
     if (d.index_launch)
-        hipLaunchKernelGGL(dd->kind == DINT_DICT_MULTI_PACKED ? decode_multi_index_kernel : decode_single_index_kernel, dim3(grid2), dim3(kBlockThreads),
-                           d.lds_bytes, s, b, tails_args{});
+        hipLaunchKernelGGL(d.dict->kind == DINT_DICT_MULTI_PACKED ? decode_multi_index_kernel : decode_single_index_kernel, dim3(grid2),
+                           dim3(kBlockThreads), d.lds_bytes, d.stream, b, tails_args{});
     else  // (a block-granular multi-dictionary unit table: the chunked schedules of the vroom kernels are its)
-        hipLaunchKernelGGL(decode_multi_kernel, dim3(grid2), dim3(kBlockThreads), d.lds_bytes, s, b);
+        hipLaunchKernelGGL(decode_multi_kernel, dim3(grid2), dim3(kBlockThreads), d.lds_bytes, d.stream, b);
 }
-static void launch_prepared(const dint_dict* dd, const deferred_launch& d, hipStream_t s, const tails_args* short_blocks) {
-    const bool multi = dd->kind == DINT_DICT_MULTI_PACKED;
-    tails_args sb{};  // (an in-index docs launch may bring its table's short blocks along: tails_phase)
-    if (short_blocks) sb = *short_blocks;
-    if (d.index_launch && d.bundles_only)
-        hipLaunchKernelGGL(multi ? decode_multi_index_bundles_kernel : decode_single_index_bundles_kernel, dim3(d.grid), dim3(kBlockThreads), d.lds_bytes, s, d.a, sb);
-    else if (d.index_launch)
-        hipLaunchKernelGGL(multi ? decode_multi_index_kernel : decode_single_index_kernel, dim3(d.grid), dim3(kBlockThreads), d.lds_bytes, s, d.a, sb);
-    else if (multi && d.bundles_only)
-        hipLaunchKernelGGL(decode_multi_bundles_kernel, dim3(d.grid), dim3(kBlockThreads), d.lds_bytes, s, d.a);
-    else
-        hipLaunchKernelGGL(multi ? decode_multi_kernel : decode_single_kernel, dim3(d.grid), dim3(kBlockThreads), d.lds_bytes, s, d.a);
+// The cut units of a prepared multi-dictionary table, instead of its stragglers: a second launch of the bundles kernel over
+// their own small schedule, the end offsets of the second halves put where the units' are, and the general kernel for
+// what could not be cut.
+static int launch_cut_units(const deferred_launch& d, const sched_cache& cache) {
+    placed_schedule L(d.a.n_units);
+    L.place(cache.d_mem);
+    placed_split SL(cache.n_items);
+    SL.place(cache.d_split);
+    HIP_TRY(hipMemsetAsync(SL.d_counters, 0, kCounterBytes, d.stream));
+    decode_args b = d.a;
+    b.urec = SL.d_urec;
+    b.cbase = SL.d_cbase;
+    b.n_units = SL.n_sub;
+    b.end_off = d.a.end_off ? SL.d_end : nullptr;
+    const uint32_t grid2 = uint32_t(std::min<size_t>(d.grid, std::max<size_t>(1, (SL.n_chunks + 3) / 4)));
+    bind_counters(b, SL.d_counters, grid2);
+    b.clock = SL.d_clock;  // (the slot's clock word stays the main launch's)
+    hipLaunchKernelGGL(decode_multi_bundles_kernel, dim3(grid2), dim3(kBlockThreads), d.lds_bytes, d.stream, b);
+    if (d.a.end_off)
+        hipLaunchKernelGGL(split_ends_kernel, dim3(uint32_t((cache.n_items + 255) / 256)), dim3(256), 0, d.stream, L.d_items, cache.n_items,
+                           SL.d_urec, SL.d_end, d.a.end_off);
+    if (cache.n_left) {
+        decode_args c = d.a;
+        c.urec = nullptr;  // (the unit queue only)
+        c.items = SL.d_left;
+        c.n_items = SL.d_n_left;
+        const uint32_t grid3 = std::min<uint32_t>(d.grid, (cache.n_left + kWavesPerBlock - 1) / kWavesPerBlock);
+        c.n_shards = std::min<uint32_t>(kQueueShards, grid3);
+        hipLaunchKernelGGL(decode_multi_kernel, dim3(grid3), dim3(kBlockThreads), d.lds_bytes, d.stream, c);
+    }
+    return DINT_OK;
 }
-static int finish_deferred(const dint_dict* dd, const deferred_launch& d, hipStream_t s) {
-    dint_dict* mut = const_cast<dint_dict*>(dd);
+static int finish_deferred(const deferred_launch& d) {
+    dint_dict* mut = const_cast<dint_dict*>(d.dict);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(mut->slot_stop[d.slot], s));
-    HIP_TRY(hipEventRecord(mut->slot_done[d.slot], s));
+    HIP_TRY(hipEventRecord(mut->slot_stop[d.slot], d.stream));
+    HIP_TRY(hipEventRecord(mut->slot_done[d.slot], d.stream));
     // (a deferred launch — block_table_decode's pair — comes here after launch_decode has returned and released the lock)
     std::unique_lock<std::mutex> lock(mut->launch_mutex, std::defer_lock);
     if (d.deferred) lock.lock();
@@ -123,208 +216,147 @@ static int finish_deferred(const dint_dict* dd, const deferred_launch& d, hipStr
     return DINT_OK;
 }
 
-static int launch_decode(const dint_dict* dd, const uint8_t* d_enc, size_t enc_bytes, const dint_unit* d_units,
-                         size_t n_units, uint32_t* d_out, size_t out_capacity, uint64_t* d_end_off, void* stream,
-                         uint32_t only_full, const uint32_t* d_spans = nullptr, uint32_t plus_one = 0,
-                         const uint32_t* d_unit_base = nullptr, uint8_t* d_gaps_left = nullptr, sched_cache* cache = nullptr,
-                         size_t schedule_from = 2, uint32_t* d_zeroed_queue = nullptr, const tails_args* short_blocks = nullptr,
-                         deferred_launch* defer = nullptr, uint32_t* d_own_counters = nullptr) {
-    if (!dd) return DINT_ERR_ARG;
-    if (n_units == 0) return DINT_OK;
-    if (!d_enc || !d_units || !d_out || enc_bytes < 8) return DINT_ERR_ARG;  // slots are fetched 8 bytes at a time
-    HIP_TRY(hipSetDevice(dd->device));
-    decode_args a{};
-    a.dict = dd->view;
-    a.enc = d_enc;
-    a.enc_bytes = enc_bytes;
-    a.units = d_units;
-    a.n_units = n_units;
-    a.out = d_out;
-    a.out_capacity = out_capacity;
-    a.end_off = d_end_off;
-    a.only_full = only_full;
-    a.plus_one = plus_one;
-    a.unit_base = d_unit_base;
-    a.gaps_left = d_gaps_left;
-    a.chunk_split_log2 = uint32_t(opt(DINT_OPT_CHUNK_SPLIT));  // (-1: by the launch's size)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint64_t blocks_needed = (uint64_t(n_units) + kWavesPerBlock - 1) / kWavesPerBlock;
-    const uint32_t grid = uint32_t(std::min<uint64_t>(blocks_needed, std::max<uint32_t>(1, dd->compute_units) * kBlocksPerCU));
-    const size_t lds_bytes = (size_t(dd->view.hot_words) + kClassTableWords + kWavesPerBlock * kScratchWords) * 4;
-    dint_dict* mut = const_cast<dint_dict*>(dd);
-    // (an in-index launch — blocks, docIDs, freqs + 1 — runs the kernels compiled for that; the vroom kernels carry none of it)
-    const bool index_launch = only_full != 0 || plus_one != 0 || d_unit_base != nullptr || d_gaps_left != nullptr;
-    bool bundles_only = false;  // (set below: a kept schedule that is known to have left the unit queue empty)
-    uint32_t stragglers = 0;    // (set below: ... or nearly empty, in-index launches: that many units, decoded by a second, small launch)
-    const bool multi_kind = dd->kind == DINT_DICT_MULTI_PACKED;
-    auto launch_kernel = [&]() {
-        deferred_launch now;
-        now.a = a;
-        now.grid = grid;
-        now.lds_bytes = lds_bytes;
-        now.bundles_only = bundles_only;
-        now.index_launch = index_launch;
-        launch_prepared(dd, now, s, short_blocks);
-    };
-    if (d_zeroed_queue && (n_units < schedule_from || (opt(DINT_OPT_BUNDLES) == 0))) {
-        // the lean launch: the caller brings the (zeroed) queue counters, nothing is timed, nothing scheduled — one
-        // API call (a query's pages: the host-side cost of a launch sequence is what a single query waits for)
-        a.queue = d_zeroed_queue;
-        a.chunk_queue = a.queue + kQueueShards * kQueueStride;
-        a.clock = reinterpret_cast<uint64_t*>(a.chunk_queue + kClockWordAt);  // (the caller's counters: nobody reads this launch's clock)
-        a.n_shards = std::min<uint32_t>(kQueueShards, grid);
-        a.sched = nullptr;
-        a.items = nullptr;
-        a.n_items = nullptr;
-        a.item_cnt = nullptr;
-        a.urec = nullptr;
-        a.cbase = nullptr;
-        a.spans = d_spans;
-        launch_kernel();
-        HIP_TRY(hipGetLastError());
-        return DINT_OK;
-    }
-    std::lock_guard<std::mutex> lock(mut->launch_mutex);
-    const uint32_t slot = mut->next_slot.fetch_add(1) % dint_dict::kQueueSlots;
-    mut->launches += 1;
-    if (mut->slot_used[slot]) HIP_TRY(hipEventSynchronize(mut->slot_done[slot]));  // normally long complete
-    // (d_own_counters: kQueueLines lines the caller has zeroed on this stream — a block table clears its flags and both
-    // launches' counters with ONE fill; the slot still carries the launch's events)
-    a.queue = d_own_counters ? d_own_counters : mut->d_queues + size_t(slot) * kQueueLines * kQueueStride;
-    a.chunk_queue = a.queue + kQueueShards * kQueueStride;  // (the clock's line; the bundle path's counters behind it)
+// ---- the stages of launch_decode, in order ---------------------------------------------------------------------------------
+static deferred_launch describe_launch(const decode_request& r) {
+    deferred_launch d;
+    d.dict = r.dict, d.stream = r.stream;
+    d.a.dict = r.dict->view;
+    d.a.enc = r.enc, d.a.enc_bytes = r.enc_bytes, d.a.units = r.units, d.a.n_units = r.n_units;
+    d.a.out = r.out, d.a.out_capacity = r.out_capacity, d.a.end_off = r.end_off;
+    d.a.only_full = r.only_full, d.a.spans = r.spans, d.a.plus_one = r.plus_one, d.a.unit_base = r.unit_base, d.a.gaps_left = r.gaps_left;
+    d.a.chunk_split_log2 = uint32_t(opt(DINT_OPT_CHUNK_SPLIT));  // (-1: by the launch's size)
+    if (r.short_blocks) d.short_blocks = *r.short_blocks;
+    d.grid = decode_grid(r.dict, r.n_units);
+    d.lds_bytes = decode_lds_bytes(r.dict);
+    d.index_launch = r.only_full != 0 || r.plus_one != 0 || r.unit_base != nullptr || r.gaps_left != nullptr;
+    return d;
+}
+
+// The lean form: the caller brings the (zeroed) queue counters, nothing is timed, nothing scheduled, no slot taken — one
+// API call (a query's pages: the host-side cost of a launch sequence is what a single query waits for). Nobody reads this
+// launch's clock.
+static int launch_decode_lean(const decode_request& r, deferred_launch& d) {
+    bind_counters(d.a, r.zeroed_queue, d.grid);
+    launch_prepared(d);
+    HIP_TRY(hipGetLastError());
+    return DINT_OK;
+}
+
+// The next queue slot of the dictionary (under launch_mutex): a reused slot's last launch waited for — normally long
+// complete —, its counters bound and, unless the caller brought zeroed ones, cleared on the stream.
+static int take_slot(dint_dict* dd, const decode_request& r, deferred_launch& d) {
+    d.slot = dd->next_slot.fetch_add(1) % dint_dict::kQueueSlots;
+    dd->launches += 1;
+    if (dd->slot_used[d.slot]) HIP_TRY(hipEventSynchronize(dd->slot_done[d.slot]));
+    uint32_t* const slot_counters = dd->d_queues + size_t(d.slot) * kQueueLines * kQueueStride;
+    bind_counters(d.a, slot_counters, d.grid);
     // where this launch's first wave leaves its cycle count: always the slot's own line of the dictionary's counters (a block
     // table's launches bring their own ticket counters, but a table may be destroyed before somebody asks for the clock)
-    a.clock = reinterpret_cast<uint64_t*>(mut->d_queues + size_t(slot) * kQueueLines * kQueueStride + kQueueShards * kQueueStride + kClockWordAt);
-    mut->slot_clock[slot] = reinterpret_cast<const uint32_t*>(a.clock);
-    a.n_shards = std::min<uint32_t>(kQueueShards, grid);
-    if (!d_own_counters) HIP_TRY(hipMemsetAsync(a.queue, 0, size_t(kQueueLines) * kQueueStride * 4, s));
-    // tiny consecutive units are decoded several to a tile: schedule them (single-dictionary streams)
-    a.sched = nullptr;
-    a.items = nullptr;
-    a.n_items = nullptr;
-    a.item_cnt = nullptr;
-    a.urec = nullptr;
-    a.cbase = nullptr;
-    a.spans = d_spans;
-    bool start_recorded = false;
-    // (schedule_from: a caller that decodes a handful of units at a time — a query's pages — does without the three
-    // schedule launches: with fewer units than waves nothing is gained by sharing tiles)
-    if (n_units >= schedule_from && n_units < 0xFFFFFFFFull &&
-        !(opt(DINT_OPT_BUNDLES) == 0)) {
-        sched_layout L(n_units);
-        if (cache) {
-            if (!cache->matches(dd, d_enc, enc_bytes, d_units, n_units, d_spans, out_capacity, only_full)) {
-                // not built yet, or built for other buffers / a larger capacity: (re)built on this stream, and timed with
-                // the launch — the event pair spans what the call put on the stream
-                HIP_TRY(hipEventRecord(mut->slot_start[slot], s));
-                start_recorded = true;
-                const int st = build_schedule(dd, d_enc, enc_bytes, d_units, n_units, out_capacity, only_full, d_spans, cache, s);
-                if (st != DINT_OK) return st;
-            }
-            L.place(cache->d_mem);
-            // (chunked schedules only: the vroom single-dictionary kernel's bundles ARE items of the unit queue)
-            bundles_only = (multi_kind || only_full != 0) && cache->items_known && cache->n_items == 0;
-            // An in-index schedule that left a FEW units to the queue (a full block of more than 504 bytes — 256 postings,
-            // nearly all of them exceptions — fits no tile): the bundles through the kernel compiled without the queue all
-            // the same, and the few through a small launch of the general kernel behind it, which skips the chunks.
-            // (round 6: kMaxStragglers is a 10^8-posting index's limit — 4096 of 4 * 10^5 blocks; an index of 10^9 postings leaves
-            // 7.5 k, one of 5 * 10^9 38 k (multi-dictionary: 91 k / 460 k) and kept the general kernel for everything. From 2^21 blocks
-            // on the limit is a share of the table, as for the vroom tables: profiles/r06_inindex_scale.json)
-            const size_t straggler_limit = index_straggler_limit(n_units);
-            stragglers = index_launch && only_full != 0 && cache->items_known && cache->n_items != 0 && cache->n_items <= straggler_limit ? cache->n_items : 0;
-            // ... and a block-granular multi-dictionary unit table (2 * 10^7 units of 256 integers): the few in a thousand that fit
-            // no tile kept the WHOLE launch on the general kernel (its bundle loop spills; profiles/r05_kernel_stats_multi.csv
-            // names it) — up to 1/32 of the units now follow the bundles-only kernel the same way
-            if (!index_launch && multi_kind && cache->items_known && cache->n_items != 0 && cache->n_items <= std::max<size_t>(kMaxStragglers, n_units / 32))
-                stragglers = cache->n_items;
-            if (stragglers) bundles_only = true;
-        } else {
-            const uint32_t ss = uint32_t(mut->launches % dint_dict::kSchedSlots);
-            const int prev = mut->sched_user[ss];
-            if (prev >= 0 && prev != int(slot) && mut->slot_used[prev]) HIP_TRY(hipEventSynchronize(mut->slot_done[prev]));
-            mut->sched_user[ss] = int(slot);
-            if (mut->sched_cap[ss] < L.need) {
-                if (mut->d_sched[ss]) HIP_TRY(hipFree(mut->d_sched[ss]));
-                mut->d_sched[ss] = nullptr;
-                mut->sched_cap[ss] = 0;
-                const size_t want = L.need + L.need / 4 + 4096;
-                HIP_TRY(counted_malloc(&mut->d_sched[ss], want));
-                mut->sched_cap[ss] = want;
-            }
-            L.place(mut->d_sched[ss]);
-            HIP_TRY(hipEventRecord(mut->slot_start[slot], s));
+    uint64_t* const slot_clock = d.a.clock;
+    if (r.own_counters) bind_counters(d.a, r.own_counters, d.grid);
+    d.a.clock = slot_clock;
+    dd->slot_clock[d.slot] = reinterpret_cast<const uint32_t*>(slot_clock);
+    if (!r.own_counters) HIP_TRY(hipMemsetAsync(d.a.queue, 0, kCounterBytes, r.stream));
+    return DINT_OK;
+}
+
+// The schedule of the launch, placed: the kept one — not built yet, or built for other buffers / a larger capacity:
+// (re)built on this stream, and timed with the launch (the event pair spans what the call put on the stream) — or one of
+// the dictionary's kSchedSlots workspaces, taken in turn, and the schedule kernels run into it.
+static int choose_schedule(dint_dict* dd, const decode_request& r, uint32_t slot, placed_schedule& L, bool& start_recorded) {
+    if (r.cache) {
+        if (!r.cache->matches(dd, r.enc, r.enc_bytes, r.units, r.n_units, r.spans, r.out_capacity, r.only_full)) {
+            HIP_TRY(hipEventRecord(dd->slot_start[slot], r.stream));
             start_recorded = true;
-            run_schedule_kernels(dd, d_enc, enc_bytes, d_units, n_units, out_capacity, only_full, d_spans, L, s);
+            const int st = build_schedule(r, r.cache, r.stream);
+            if (st != DINT_OK) return st;
         }
-        uint8_t* const d_sch = L.d_sch;
-        uint32_t* const d_items = L.d_items;
-        uint32_t* const d_n_items = L.d_n_items;
-        uint8_t* const d_item_cnt = L.d_item_cnt;
-        u32x4* const d_urec = L.d_urec;
-        uint64_t* const d_cbase = L.d_cbase;
-        a.sched = d_sch;
-        a.items = d_items;
-        a.n_items = d_n_items;
-        a.item_cnt = d_item_cnt;
-        a.urec = d_urec;
-        a.cbase = d_cbase;
-    }
-    if (!start_recorded) HIP_TRY(hipEventRecord(mut->slot_start[slot], s));
-    deferred_launch d;
-    d.a = a;
-    d.grid = grid;
-    d.slot = slot;
-    d.stragglers = stragglers;
-    d.lds_bytes = lds_bytes;
-    d.bundles_only = bundles_only;
-    d.index_launch = index_launch;
-    d.prepared = true;
-    if (defer) {  // (the caller launches: finish_deferred behind it)
-        d.deferred = true;
-        *defer = d;
+        L.place(r.cache->d_mem);
         return DINT_OK;
     }
-    launch_kernel();
-    if (stragglers && cache && cache->split_ready && !index_launch) {
-        // the cut units: a second launch of the bundles kernel over their own small schedule, the end offsets of the second
-        // halves put where the units' are, and the general kernel for what could not be cut
-        sched_layout L(n_units);
-        L.place(cache->d_mem);
-        split_layout SL(cache->n_items);
-        SL.place(cache->d_split);
-        HIP_TRY(hipMemsetAsync(SL.d_counters, 0, size_t(kQueueLines) * kQueueStride * 4, s));
-        decode_args b = d.a;
-        b.urec = SL.d_urec;
-        b.cbase = SL.d_cbase;
-        b.n_units = SL.n_sub;
-        b.end_off = d.a.end_off ? SL.d_end : nullptr;
-        b.queue = SL.d_counters;
-        b.chunk_queue = b.queue + kQueueShards * kQueueStride;
-        b.clock = reinterpret_cast<uint64_t*>(SL.d_n_left + 2);  // (the slot's clock word stays the main launch's)
-        const uint32_t grid2 = uint32_t(std::min<size_t>(d.grid, std::max<size_t>(1, (SL.n_chunks + 3) / 4)));
-        b.n_shards = std::min<uint32_t>(kQueueShards, grid2);
-        hipLaunchKernelGGL(decode_multi_bundles_kernel, dim3(grid2), dim3(kBlockThreads), d.lds_bytes, s, b);
-        if (d.a.end_off)
-            hipLaunchKernelGGL(split_ends_kernel, dim3(uint32_t((cache->n_items + 255) / 256)), dim3(256), 0, s, L.d_items, cache->n_items,
-                               SL.d_urec, SL.d_end, d.a.end_off);
-        if (cache->n_left) {
-            decode_args c2 = d.a;
-            c2.urec = nullptr;  // (the unit queue only)
-            c2.items = SL.d_left;
-            c2.n_items = SL.d_n_left;
-            const uint32_t grid3 = std::min<uint32_t>(d.grid, (cache->n_left + kWavesPerBlock - 1) / kWavesPerBlock);
-            c2.n_shards = std::min<uint32_t>(kQueueShards, grid3);
-            hipLaunchKernelGGL(decode_multi_kernel, dim3(grid3), dim3(kBlockThreads), d.lds_bytes, s, c2);
-        }
-    } else {
-        launch_stragglers(dd, d, s);
+    const uint32_t ss = uint32_t(dd->launches % dint_dict::kSchedSlots);
+    const int prev = dd->sched_user[ss];
+    if (prev >= 0 && prev != int(slot) && dd->slot_used[prev]) HIP_TRY(hipEventSynchronize(dd->slot_done[prev]));
+    dd->sched_user[ss] = int(slot);
+    if (dd->sched_cap[ss] < L.need) {
+        if (dd->d_sched[ss]) HIP_TRY(hipFree(dd->d_sched[ss]));
+        dd->d_sched[ss] = nullptr;
+        dd->sched_cap[ss] = 0;
+        const size_t want = L.need + L.need / 4 + 4096;
+        HIP_TRY(counted_malloc(&dd->d_sched[ss], want));
+        dd->sched_cap[ss] = want;
     }
-    return finish_deferred(dd, d, s);
+    L.place(dd->d_sched[ss]);
+    HIP_TRY(hipEventRecord(dd->slot_start[slot], r.stream));
+    start_recorded = true;
+    run_schedule_kernels(r, L, r.stream);
+    return DINT_OK;
+}
+
+// What a kept schedule whose queue items have been read back lets the launch do. None left to the queue (chunked
+// schedules only: the vroom single-dictionary kernel's bundles ARE items of the unit queue): the kernel compiled without it.
+// A FEW left — an in-index schedule: a full block of more than 504 bytes (256 postings, nearly all of them exceptions) fits
+// no tile; a block-granular multi-dictionary unit table the same — the bundles through that kernel all the same, and the
+// few through a small launch of the general kernel behind it (the stragglers), or as the table's cut units.
+// (round 6: kMaxStragglers is a 10^8-posting index's limit — 4096 of 4 * 10^5 blocks; an index of 10^9 postings leaves
+// 7.5 k, one of 5 * 10^9 38 k (multi-dictionary: 91 k / 460 k) and kept the general kernel for everything. From 2^21 blocks
+// on the limit is a share of the table, as for the vroom tables: profiles/r06_inindex_scale.json)
+static void plan_launch(const decode_request& r, deferred_launch& d) {
+    const sched_cache& c = *r.cache;
+    if (!c.items_known) return;
+    const bool multi = r.dict->kind == DINT_DICT_MULTI_PACKED;
+    size_t limit = 0;
+    if (r.only_full != 0) limit = index_straggler_limit(r.n_units);
+    else if (multi && !d.index_launch) limit = vroom_straggler_limit(r.n_units);
+    if (c.n_items != 0 && c.n_items <= limit) d.stragglers = c.n_items;
+    d.bundles_only = ((multi || r.only_full != 0) && c.n_items == 0) || d.stragglers != 0;
+}
+
+static int launch_decode(const decode_request& r) {
+    if (!r.dict) return DINT_ERR_ARG;
+    if (r.n_units == 0) return DINT_OK;
+    if (!r.enc || !r.units || !r.out || r.enc_bytes < 8) return DINT_ERR_ARG;  // slots are fetched 8 bytes at a time
+    HIP_TRY(hipSetDevice(r.dict->device));
+    deferred_launch d = describe_launch(r);
+    // tiny consecutive units are decoded several to a tile: schedule them
+    const bool scheduled = r.n_units >= r.schedule_from && opt(DINT_OPT_BUNDLES) != 0;
+    if (r.zeroed_queue && !scheduled) return launch_decode_lean(r, d);
+    dint_dict* dd = const_cast<dint_dict*>(r.dict);
+    std::lock_guard<std::mutex> lock(dd->launch_mutex);
+    int st = take_slot(dd, r, d);
+    if (st != DINT_OK) return st;
+    bool start_recorded = false;
+    if (scheduled && r.n_units < 0xFFFFFFFFull) {
+        placed_schedule L(r.n_units);
+        st = choose_schedule(dd, r, d.slot, L, start_recorded);
+        if (st != DINT_OK) return st;
+        if (r.cache) plan_launch(r, d);
+        d.a.sched = L.d_sch, d.a.items = L.d_items, d.a.n_items = L.d_n_items, d.a.item_cnt = L.d_item_cnt;
+        d.a.urec = L.d_urec, d.a.cbase = L.d_cbase;
+    }
+    if (!start_recorded) HIP_TRY(hipEventRecord(dd->slot_start[d.slot], r.stream));
+    d.prepared = true;
+    if (r.defer) {
+        d.deferred = true;
+        *r.defer = d;
+        return DINT_OK;
+    }
+    launch_prepared(d);
+    if (d.stragglers && r.cache->split_ready && !d.index_launch) {
+        st = launch_cut_units(d, *r.cache);
+        if (st != DINT_OK) return st;
+    } else {
+        launch_stragglers(d);
+    }
+    return finish_deferred(d);
 }
 
 int dint_decode_units(const dint_dict* dd, const uint8_t* d_enc, size_t enc_bytes, const dint_unit* d_units,
                       size_t n_units, uint32_t* d_out, size_t out_capacity, uint64_t* d_end_off, void* stream) {
-    return launch_decode(dd, d_enc, enc_bytes, d_units, n_units, d_out, out_capacity, d_end_off, stream, 0);
+    decode_request r;
+    r.dict = dd, r.enc = d_enc, r.enc_bytes = enc_bytes, r.units = d_units, r.n_units = n_units;
+    r.out = d_out, r.out_capacity = out_capacity, r.end_off = d_end_off, r.stream = static_cast<hipStream_t>(stream);
+    return launch_decode(r);
 }
 
 struct dint_unit_table {
@@ -341,6 +373,13 @@ struct dint_unit_table {
     uint32_t* d_first = nullptr;     // owned: first[i] = the first block of the caller's unit i, n_user_units + 1 entries
     uint64_t* d_end_sub = nullptr;   // owned, made by the first decode that asks for end offsets: where every block ends
     size_t n_user_units = 0;
+    // what a decode of the table asks of launch_decode, less the output (the kept schedule is built for the table's own capacity)
+    decode_request request() {
+        decode_request r;
+        r.dict = dict, r.enc = d_enc, r.enc_bytes = enc_bytes, r.units = d_units, r.n_units = n_units;
+        r.out_capacity = out_capacity, r.cache = &sched;
+        return r;
+    }
 };
 
 namespace {
@@ -399,6 +438,31 @@ int refine_table(dint_unit_table* t, hipStream_t s) {
     t->n_units = n_blocks;
     return DINT_OK;
 }
+
+// (round 6) A multi-dictionary table's units that fit no tile, where they are few: cut in two records each and scheduled on
+// their own (launch_cut_units decodes them). Waits for the stream.
+int prepare_cut_units(dint_unit_table* t, hipStream_t s) {
+    sched_cache& c = t->sched;
+    if (t->dict->kind != DINT_DICT_MULTI_PACKED || c.n_items == 0 || c.n_items > vroom_straggler_limit(t->n_units) ||
+        opt(DINT_OPT_SPLIT_UNITS) == 0)
+        return DINT_OK;
+    placed_schedule L(t->n_units);
+    L.place(c.d_mem);
+    placed_split SL(c.n_items);
+    HIP_TRY(counted_malloc(&c.d_split, SL.need));
+    SL.place(c.d_split);
+    HIP_TRY(hipMemsetAsync(SL.d_n_left, 0, 256, s));
+    hipLaunchKernelGGL(split_units_kernel, dim3((c.n_items + 255) / 256), dim3(256), 0, s, L.d_items, c.n_items, t->d_units, t->d_enc,
+                       uint64_t(t->enc_bytes), uint64_t(t->out_capacity), t->dict->view, SL.d_urec, SL.d_cbase, SL.d_left, SL.d_n_left);
+    hipLaunchKernelGGL(bundle_pack_kernel, dim3(uint32_t((SL.n_chunks + 63) / 64)), dim3(64), 0, s, SL.d_urec, uint64_t(SL.n_sub));
+    HIP_TRY(hipGetLastError());
+    uint32_t n_left = 0;
+    HIP_TRY(hipMemcpyAsync(&n_left, SL.d_n_left, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    c.n_left = n_left;
+    c.split_ready = true;
+    return DINT_OK;
+}
 }  // namespace
 
 int dint_unit_table_create(const dint_dict* dd, const uint8_t* d_enc, size_t enc_bytes, const dint_unit* d_units, size_t n_units,
@@ -420,44 +484,13 @@ int dint_unit_table_create(const dint_dict* dd, const uint8_t* d_enc, size_t enc
             dint_unit_table_destroy(t);
             return st;
         }
-        d_units = t->d_units;  // (the table's own, if it was refined)
-        n_units = t->n_units;
+        n_units = t->n_units;  // (the table's own units, if it was refined)
     }
     if (n_units >= 2 && n_units < 0xFFFFFFFFull && !(opt(DINT_OPT_BUNDLES) == 0)) {
-        int st = build_schedule(dd, d_enc, enc_bytes, d_units, n_units, out_capacity, 0, nullptr, &t->sched, static_cast<hipStream_t>(stream));
-        if (st == DINT_OK) {  // how many work items the unit queue got (none: the bundles-only kernel serves the table)
-            sched_layout L(n_units);
-            L.place(t->sched.d_mem);
-            uint32_t n_items = 0;
-            if (!hip_ok(hipMemcpyAsync(&n_items, L.d_n_items, 4, hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)), "hipMemcpyAsync") ||
-                !hip_ok(hipStreamSynchronize(static_cast<hipStream_t>(stream)), "hipStreamSynchronize"))
-                st = DINT_ERR_HIP;
-            t->sched.n_items = n_items;
-            t->sched.items_known = st == DINT_OK;
-            // (round 6) a multi-dictionary table's units that fit no tile: cut in two records each, scheduled on their own
-            if (st == DINT_OK && dd->kind == DINT_DICT_MULTI_PACKED && n_items != 0 && n_items <= std::max<size_t>(kMaxStragglers, n_units / 32) &&
-                opt(DINT_OPT_SPLIT_UNITS) != 0) {
-                hipStream_t s = static_cast<hipStream_t>(stream);
-                split_layout SL(n_items);
-                if (!hip_ok(counted_malloc(&t->sched.d_split, SL.need), "counted_malloc(split)")) st = DINT_ERR_HIP;
-                if (st == DINT_OK) {
-                    SL.place(t->sched.d_split);
-                    uint32_t n_left = 0;
-                    if (!hip_ok(hipMemsetAsync(SL.d_n_left, 0, 256, s), "hipMemsetAsync")) st = DINT_ERR_HIP;
-                    if (st == DINT_OK) {
-                        hipLaunchKernelGGL(split_units_kernel, dim3((n_items + 255) / 256), dim3(256), 0, s, L.d_items, n_items, d_units, d_enc,
-                                           uint64_t(enc_bytes), uint64_t(out_capacity), dd->view, SL.d_urec, SL.d_cbase, SL.d_left, SL.d_n_left);
-                        hipLaunchKernelGGL(bundle_pack_kernel, dim3(uint32_t((SL.n_chunks + 63) / 64)), dim3(64), 0, s, SL.d_urec, uint64_t(SL.n_sub));
-                        if (!hip_ok(hipGetLastError(), "split_units_kernel") ||
-                            !hip_ok(hipMemcpyAsync(&n_left, SL.d_n_left, 4, hipMemcpyDeviceToHost, s), "hipMemcpyAsync") ||
-                            !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize"))
-                            st = DINT_ERR_HIP;
-                    }
-                    t->sched.n_left = n_left;
-                    t->sched.split_ready = st == DINT_OK;
-                }
-            }
-        }
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        int st = build_schedule(t->request(), &t->sched, s);
+        if (st == DINT_OK) st = read_queue_items(t->sched, n_units, s);
+        if (st == DINT_OK) st = prepare_cut_units(t, s);
         if (st != DINT_OK) {
             dint_unit_table_destroy(t);
             return st;
@@ -488,8 +521,9 @@ int dint_decode_unit_table(const dint_dict* dd, dint_unit_table* t, uint32_t* d_
         if (!t->d_end_sub) HIP_TRY(counted_malloc(&t->d_end_sub, t->n_units * sizeof(uint64_t)));
         end_arg = t->d_end_sub;
     }
-    const int st = launch_decode(dd, t->d_enc, t->enc_bytes, t->d_units, t->n_units, d_out, out_capacity, end_arg, stream, 0, nullptr, 0, nullptr,
-                                 nullptr, &t->sched);
+    decode_request r = t->request();
+    r.out = d_out, r.out_capacity = out_capacity, r.end_off = end_arg, r.stream = static_cast<hipStream_t>(stream);
+    const int st = launch_decode(r);
     if (st == DINT_OK && t->d_first && d_end_off) {
         hipLaunchKernelGGL(refined_ends_kernel, dim3(uint32_t((t->n_user_units + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                            t->d_first, uint64_t(t->n_user_units), t->d_end_sub, d_end_off);

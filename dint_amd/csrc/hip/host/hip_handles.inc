@@ -14,8 +14,12 @@ constexpr size_t kIndexStragglerShareFrom = size_t(1) << 21;
 inline size_t index_straggler_limit(size_t n_units) {
     return n_units >= kIndexStragglerShareFrom ? std::max<size_t>(kMaxStragglers, n_units / kIndexStragglerShare) : kMaxStragglers;
 }
+// ... and a block-granular multi-dictionary unit table (2 * 10^7 units of 256 integers): the few in a thousand that fit no tile
+// kept the WHOLE launch on the general kernel (its bundle loop spills; profiles/r05_kernel_stats_multi.csv names it) — up to
+// 1/32 of the units follow the bundles-only kernel the same way
+inline size_t vroom_straggler_limit(size_t n_units) { return std::max<size_t>(kMaxStragglers, n_units / 32); }
 struct sched_cache {
-    void* d_mem = nullptr;  // (the layout launch_decode gives a slot's schedule workspace)
+    void* d_mem = nullptr;  // (laid out by sched_layout, hip_stage_layout.inc: the one description, a slot's workspace too)
     size_t mem_bytes = 0;
     bool valid = false;
     // What the schedule was built from. bundle_schedule_kernel bakes this launch's bounds checks (stream bytes, output
@@ -30,8 +34,8 @@ struct sched_cache {
     bool items_known = false;  // n_items has been read back (a prepared unit table does, once)
     uint32_t n_items = 0;      // work items of the unit queue: 0 = every unit is a bundle member
     // round 6 (a prepared multi-dictionary vroom table): the units that fit no tile cut in two records each (split_units_kernel)
-    // and scheduled on their own — [records 16 B x 2 n_items][chunk bases][end offsets 8 B x 2 n_items][left items][n_left, pad]
-    // [a launch's counter lines] — decoded by a second launch of the bundles kernel; `n_left`: those that could not be cut
+    // and scheduled on their own (split_layout, hip_stage_layout.inc) — decoded by a second launch of the bundles kernel;
+    // `n_left`: those that could not be cut
     void* d_split = nullptr;
     bool split_ready = false;
     uint32_t n_left = 0;
@@ -41,6 +45,11 @@ struct sched_cache {
                cap >= out_capacity && only_full == full;
     }
 };
+// An in-index schedule that has been read back and left at most the stragglers' share to the unit queue: its launches run
+// the kernels compiled without the queue (the one-launch decode of a block table asks this of both of its schedules).
+inline bool schedule_is_bundles(const sched_cache& c, size_t n_units) {
+    return c.valid && c.items_known && c.n_items <= index_straggler_limit(n_units);
+}
 
 struct dint_dict {
     int kind = 0;

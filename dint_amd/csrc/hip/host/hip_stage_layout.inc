@@ -1,4 +1,4 @@
-// Part of dint_hip.hip (one translation unit; included from there, in order): the staged input areas of the query calls, each laid out ONCE.
+// Part of dint_hip.hip (one translation unit; included from there, in order): the staged input areas of the query calls and the decode launch's two schedule workspaces, each laid out ONCE.
 // Plain C++, no HIP call and no allocation (tests/test_stage_layout.py compiles this file alone). A call stages what its
 // kernels read from the host in dint_query_index::h_stage and sends it to ::inputs in one copy: a layout takes the area's
 // fields in order and records each one's word offset; the host fills the field at h(at), the kernel's argument struct
@@ -96,5 +96,46 @@ struct topk_layout : stage_layout {
         tasks = take(3 * n_tasks);
         take_each({&page_first, &pages}, nq);
         key_base = take(2 * nq, 2);
+    }
+};
+
+// ---- the two schedule workspaces of a decode launch (hip_api_vroom.inc), as byte offsets into one allocation -----------------
+// (what the kernels size them by comes in as arguments — chunk_units: kChunkUnits, kernels/bundles.inc; counter_bytes: a
+// launch's kQueueLines counter lines of kQueueStride words, dint_kernels.hpp — so that this file still compiles alone)
+template <class T>
+static inline T* at_byte(void* base, size_t off) {
+    return reinterpret_cast<T*>(static_cast<uint8_t*>(base) + off);
+}
+// A bundle schedule of n units (sched_cache::d_mem, dint_dict::d_sched): per unit a 16-byte record, per chunk of chunk_units
+// units a 16-byte base, per unit its work item (u32), per 256 units their count / offset (u32), the number of work items
+// (u32), then per unit the schedule byte and the item count byte.
+struct sched_layout {
+    size_t n_units, n_blocks, n_chunks;
+    size_t urec = 0, cbase, items, block, n_items, sch, item_cnt, need;
+    sched_layout(size_t n, size_t chunk_units) : n_units(n), n_blocks((n + 255) / 256), n_chunks((n + chunk_units - 1) / chunk_units) {
+        cbase = urec + 16 * n_units;
+        items = cbase + 16 * n_chunks;
+        block = items + 4 * n_units;
+        n_items = block + 4 * n_blocks;
+        sch = n_items + 4;
+        item_cnt = sch + n_units;
+        need = item_cnt + n_units;
+    }
+};
+// The cut units of a kept schedule (sched_cache::d_split) that left `items` units to the queue: two 16-byte records each,
+// their chunks' bases, two end offsets each (u64), the units that could not be cut (u32), a 256-byte line — their number,
+// and 8 bytes on the clock word of the cut units' launch — then a launch's counter lines.
+struct split_layout {
+    size_t n_items, n_sub, n_chunks;
+    size_t urec = 0, cbase, end, left, n_left, clock, counters, need;
+    split_layout(size_t items, size_t chunk_units, size_t counter_bytes)
+        : n_items(items), n_sub(2 * items), n_chunks((2 * items + chunk_units - 1) / chunk_units) {
+        cbase = urec + 16 * n_sub;
+        end = cbase + 16 * n_chunks;
+        left = end + 8 * n_sub;
+        n_left = left + 4 * n_items;
+        clock = n_left + 8;
+        counters = n_left + 256;
+        need = counters + counter_bytes;
     }
 };

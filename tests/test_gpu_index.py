@@ -142,6 +142,37 @@ def test_a_taught_table_decodes_in_one_launch_from_its_first_decode(device, smal
 
 
 @pytest.mark.parametrize("kind", [host.SINGLE_PACKED, host.MULTI_PACKED])
+def test_a_taught_table_follows_its_index_to_another_address(device, small_corpus, kind):
+    """A taught table's kept schedules belong to the index buffer they were built over. Handed a second device copy of
+    the same bytes, the one-launch (pair) call finds both schedules stale, rebuilds them under the call and falls back to
+    a launch each — deferred launches that are not bundles-only; the next decode reads the new schedules' queue items
+    back, and a decode on the first copy rebuilds again. Every decode bit-exact, every one counted as complete."""
+    import torch
+
+    ix = get_index(small_corpus, kind)
+    blocks, total = device.index_posting_lists(ix.bytes, ix.offsets)
+    dd, fd = device.Dictionary(kind, ix.docs_dict), device.Dictionary(kind, ix.freqs_dict)
+    dev = torch.device("cuda", 0)
+    padded = np.concatenate([ix.bytes, np.zeros(16, np.uint8)])
+    copy_a, copy_b = torch.from_numpy(padded).to(dev), torch.from_numpy(padded).to(dev)
+    assert copy_a.data_ptr() != copy_b.data_ptr()
+    table = device.BlockTable(dd, blocks, padded.size)
+    table.learn(dd, fd, copy_a, padded.size)
+    assert table.ready(True)
+    done = table.info()["complete_decodes"]
+    for index_dev in (copy_a, copy_b, copy_b, copy_a):
+        docids_dev = torch.full((total,), -1, dtype=torch.int32, device=dev)
+        freqs_dev = torch.full((total,), -1, dtype=torch.int32, device=dev)
+        table.decode(dd, fd, index_dev, padded.size, docids_dev, freqs_dev)
+        torch.cuda.synchronize()
+        assert np.array_equal(docids_dev.cpu().numpy().view(np.uint32), ix.docids)
+        assert np.array_equal(freqs_dev.cpu().numpy().view(np.uint32), ix.freqs)
+        done += 1
+        assert table.info()["complete_decodes"] == done
+    table.close()
+
+
+@pytest.mark.parametrize("kind", [host.SINGLE_PACKED, host.MULTI_PACKED])
 def test_block_table_side_streams_are_joined_to_the_callers_stream(device, small_corpus, kind):
     """From its second decode on a table runs the freqs launch and the short blocks' decoder on streams of its own. What
     the caller puts on ITS stream around a call must still be ordered with them: the poison written before a call is there
