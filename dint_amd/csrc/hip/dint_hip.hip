@@ -32,6 +32,7 @@
 #include "dint_ranked_or_query_kernels.hpp"
 #include "dint_ranked_or_maxscore_kernels.hpp"
 #include "dint_score_documents_kernels.hpp"
+#include "dint_wand_kernels.hpp"
 #include "dint_stats_kernels.hpp"
 
 #include "host/hip_common.inc"
@@ -51,6 +52,7 @@
 #include "host/hip_api_ranked_or_query.inc"
 #include "host/hip_api_ranked_or_maxscore.inc"
 #include "host/hip_api_score_documents.inc"
+#include "host/hip_api_wand.inc"
 #include "host/hip_api_stats.inc"
 #include "host/hip_api_host_calls.inc"
 #include "host/hip_api_list_cache.inc"

@@ -6,7 +6,8 @@
 // one-term records, then ranked_topk) and the host's split of its terms into the essential ones E and the rest N:
 //   1. ms_bound_kernel: a thread per posting of E's decoded pages. A posting is its document's representative iff no E
 //      list before its own (longest first) holds it. The representative sums its E addends in double (P, in E's order)
-//      and dies if (P + sum_N m_t) * margin < theta; a live one claims, for every N term whose pages are not decoded,
+//      and dies if (P + sum_N m_t) * margin < theta — with block maxima, also if the candidate's own sum over N does it:
+//      per N term, q_weight * the maximum of the block its docID falls in (ms_block_rest) — a live one claims, for every N term whose pages are not decoded,
 //      the block its docID falls in (block-max search). Claims are per (term record, block): a flag, a rank, a touched list.
 //   2. The host decodes the claimed blocks behind the other pages (docs and freqs).
 //   3. ms_score_kernel: every live representative walks ALL of the query's terms in ascending term id and adds their
@@ -30,7 +31,7 @@ struct maxscore_pass {
     const uint32_t* term_first;    // record -> first block of its list in the index
     const uint32_t* term_blocks;   // ... its list's block count
     const uint32_t* term_page;     // ... decoded: its first page in docs; claimed (N): its first claim flag
-    const uint32_t* term_claimed;  // ... 1: an N term probed through its claimed blocks
+    const uint32_t* term_claimed;  // ... 0: an E term; 1: an N term probed through its claimed blocks; 2: a seed in N (its pages are decoded)
     const float* term_weight;      // ... q_weight of its term in its query
     const uint32_t* term_order;    // [q_from[q] + i] = the record of query q's i-th smallest term id
     const uint32_t* term_e;        // [q_from[q] + i], i < q_ne[q]: query q's E records, longest first
@@ -54,6 +55,7 @@ struct maxscore_pass {
     uint32_t* n_touched;
     uint32_t* q_claims;            // pass query -> the blocks it claimed
     const float* norm_lens;
+    const float* block_max_weight; // nullable; per index block: the largest doc_term_weight of its postings (block maxima)
     uint32_t* cand;                // per candidate slot: the representative's docID, kDeadCandidate otherwise
     float* score;
 };
@@ -64,6 +66,25 @@ __device__ __forceinline__ posting ms_find(const maxscore_pass& p, uint32_t j, u
     return find_posting(p.block_max, p.blocks, p.term_first[j], p.term_blocks[j], p.docs, d, [&](uint32_t pos) {
         return claimed ? p.claim_page0 + p.rank[p.term_page[j] + pos] : p.term_page[j] + pos;
     });
+}
+
+// Block maxima: what the N terms can still add to document d of query q. From 0.0, over the N terms in ascending term id,
+// (double) fl32(q_weight_t * block_max_weight[b_t(d)]), b_t(d) the block of t that d falls in (the claims' lookup); a
+// term whose list ends before d adds nothing. fl32(q_w * maximum) >= every addend of that block (rounding is monotone).
+__device__ __forceinline__ double ms_block_rest(const maxscore_pass& p, uint32_t q, uint32_t d) {
+#pragma clang fp contract(off)
+    const uint32_t from = p.q_from[q], nr = p.q_n[q];
+    double rest = 0.0;
+    for (uint32_t i = 0; i != nr; ++i) {
+        const uint32_t j = p.term_order[from + i];
+        if (!p.term_claimed[j]) continue;
+        const uint32_t nb = p.term_blocks[j];
+        const uint32_t pos = list_block_of(p.block_max, p.term_first[j], nb, d);
+        if (pos == nb) continue;
+        const float m = p.term_weight[j] * p.block_max_weight[p.term_first[j] + pos];
+        rest = rest + double(m);
+    }
+    return rest;
 }
 
 // A workgroup per candidate page, a thread per slot. The loops over a query's records are uniform in the workgroup (a
@@ -100,13 +121,20 @@ __global__ __launch_bounds__(256) void ms_bound_kernel(maxscore_pass p) {
             }
             P = P + double(bm25_addend(p.term_weight[j], f, kd));
         }
-        if (alive && (P + p.q_rest[q]) * p.q_margin[q] < double(p.q_theta[q])) alive = false;  // strict: a tie with theta stays
+        if (alive) {
+            double rest = p.q_rest[q];
+            if (p.block_max_weight) {  // (the smaller of the two bounds: block maxima above their term's maximum cost nothing)
+                const double by_block = ms_block_rest(p, q, d);
+                rest = by_block < rest ? by_block : rest;
+            }
+            if ((P + rest) * p.q_margin[q] < double(p.q_theta[q])) alive = false;  // strict: a tie with theta stays
+        }
     }
     p.cand[c_at] = alive ? d : kDeadCandidate;
     // claims: per N term whose pages are not decoded, the block of every live candidate (neighbours in a wave share one)
     const uint32_t from = p.q_from[q], nr = p.q_n[q];
     for (uint32_t j = from; j != from + nr; ++j) {
-        if (!p.term_claimed[j]) continue;
+        if (p.term_claimed[j] != 1) continue;
         uint32_t idx = kDeadCandidate;
         if (alive) {
             const uint32_t nb = p.term_blocks[j];
@@ -136,7 +164,7 @@ __global__ __launch_bounds__(256) void ms_score_kernel(maxscore_pass p) {
         if (j == k) {
             f = float(p.freqs[at]);
         } else {
-            const posting hit = ms_find(p, j, d, p.term_claimed[j] != 0);
+            const posting hit = ms_find(p, j, d, p.term_claimed[j] == 1);
             if (!hit.held()) continue;
             f = float(p.freqs[hit.slot()]);
         }

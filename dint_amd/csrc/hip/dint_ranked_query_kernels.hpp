@@ -30,9 +30,13 @@ __device__ __forceinline__ float bm25_kd(float norm_len) {
 #pragma clang fp contract(off)
     return kBm25K1 * ((1.0f - kBm25B) + kBm25B * norm_len);
 }
+__device__ __forceinline__ float bm25_doc_term_weight(float f, float kd) {  // (what the wand data's maxima are taken over)
+#pragma clang fp contract(off)
+    return f / (f + kd);
+}
 __device__ __forceinline__ float bm25_addend(float weight, float f, float kd) {
 #pragma clang fp contract(off)
-    const float w = f / (f + kd);
+    const float w = bm25_doc_term_weight(f, kd);
     return weight * w;
 }
 __device__ __forceinline__ float bm25_add(float sc, float weight, float f, float kd) {

@@ -8,7 +8,8 @@
 //   split   on the host: N = the longest proper prefix of the terms by (m_t = q_weight_t * max_term_weight_t ascending, term
 //           id) with (sum_N m_t) * margin < theta, E = the rest; margin = 1 + (|T| + 1) * 2^-23 (the reordering of the binary32
 //           sum, DESIGN.md 4d-maxscore)
-//   E       the other E terms' pages decoded behind the seeds'; ms_bound_kernel over E's pages (the seed's own reused)
+//   E       the other E terms' pages decoded behind the seeds'; ms_bound_kernel over E's pages (the seed's own reused); a wand
+//           handle with block maxima (dint_wand_data_set_block_max_weights) bounds N per candidate, by the blocks it falls in
 //   claims  the claimed blocks decoded behind those; ms_score_kernel; ranked_topk
 // Pages of a pass: seeds + E + claimed <= every block of every term, the pass bound of ranked_or.
 
@@ -109,6 +110,7 @@ static void maxscore_split(maxscore_pass_state& m) {
             if (j == m.seed[i]) {
                 m.t_page[r] = m.seed_page[i];
                 m.read[q] += nb;
+                if (!m.is_e[r]) m.claimed[r] = 2;  // (a seed in N: decoded, but bounded like any N term under block maxima)
             } else if (m.is_e[r]) {
                 m.t_page[r] = m.S + m.R;
                 for (uint32_t b = 0; b != nb; ++b) m.rest_blocks.push_back(qi->list_first[t[j]] + b);
@@ -204,6 +206,7 @@ static int maxscore_main(maxscore_pass_state& m) {
     mp.n_touched = qi->ms_count.p;
     mp.q_claims = qi->ms_count.p + 1;
     mp.norm_lens = m.wd->d_norm_lens;
+    mp.block_max_weight = m.wd->has_block_max ? m.wd->d_block_max_weight : nullptr;
     mp.cand = qi->cand.p;
     mp.score = qi->slot_score.p;
     hipLaunchKernelGGL(ms_bound_kernel, dim3(C), dim3(kPageSlots), 0, m.s, mp);
@@ -227,6 +230,7 @@ int dint_ranked_or_maxscore_queries(dint_query_index* qi, const dint_dict* freqs
                                     float* scores, uint32_t* docids, uint64_t* blocks_read, void* stream) {
     if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores)) return DINT_ERR_ARG;
     if (!wd->has_max_weights || wd->max_term_weight.size() < qi->list_len.size()) return DINT_ERR_ARG;
+    if (wd->has_block_max && wd->n_block_max != qi->n_blocks) return DINT_ERR_ARG;
     if (blocks_read) *blocks_read = 0;
     if (n_queries == 0) return DINT_OK;
     or_passes op;

@@ -13,14 +13,17 @@ struct dint_wand_data {
     // dint_wand_data_create_with_max_weights: max_term_weight[n_lists], on the host (only the pruned ranked call reads it)
     bool has_max_weights = false;
     std::vector<float> max_term_weight;
+    // dint_wand_data_set_block_max_weights (hip_api_wand.inc): a maximum per block of a query index, on the device
+    bool has_block_max = false;
+    size_t n_block_max = 0;
+    float* d_block_max_weight = nullptr;
 };
 
 void dint_wand_data_destroy(dint_wand_data* wd) {
     if (!wd) return;
-    if (wd->d_norm_lens) {
-        (void)hipSetDevice(wd->device);
-        (void)hipFree(wd->d_norm_lens);
-    }
+    (void)hipSetDevice(wd->device);
+    if (wd->d_norm_lens) (void)hipFree(wd->d_norm_lens);
+    if (wd->d_block_max_weight) (void)hipFree(wd->d_block_max_weight);
     delete wd;
 }
 

@@ -36,7 +36,8 @@ ABI_SYMBOLS = (
     "dint_block_table_create", "dint_block_table_destroy", "dint_block_table_learn", "dint_block_table_ready", "dint_block_table_info_get", "dint_decode_block_table",
     "dint_query_index_create", "dint_query_index_destroy", "dint_and_queries", "dint_and_queries_freqs", "dint_or_queries", "dint_or_queries_freqs",
     "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_or_queries",
-    "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
+    "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
+    "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
 
 #: dint_block_ref (include/dint_hip.h)
@@ -132,6 +133,8 @@ def _load():
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_index_max_weights.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.dint_wand_data_set_block_max_weights.argtypes = [vp, vp, sz]
     lib.dint_count_ngrams.argtypes = [C.c_int, C.c_int, vp, u64, vp, u64, C.c_uint32, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_float)]
     lib.dint_select_ngrams.argtypes = [C.c_int, vp, u64, u64, vp, sz, C.c_uint32, C.POINTER(sz)]
     lib.dint_debug_wave_scan.argtypes = [vp, vp]
@@ -643,6 +646,17 @@ class QueryIndex:
             mats = [freqs[at[q]:at[q + 1]].reshape(int(doc_offs[q + 1] - doc_offs[q]), n_terms[q]) for q in range(n)]
         return out, mats, blocks.value
 
+    def max_weights(self, freqs_dict: "Dictionary", wand: "WandData", with_blocks: bool = False):
+        """The wand data's BM25 maxima from the index, on the device (dint_index_max_weights): every
+        block decoded once -> max_term_weight f32[n_lists], bit for bit host.wand_data's second array (`wand` carrying that
+        call's norm_lens); with_blocks: (max_term_weight, block_max_weight f32[n_blocks]), one maximum per block of
+        self.blocks, for WandData.set_block_max_weights."""
+        mtw = np.zeros(self.n_lists, dtype=np.float32)
+        bmw = np.zeros(len(self.blocks), dtype=np.float32) if with_blocks else None
+        _check(_lib.dint_index_max_weights(self._h, freqs_dict._h, wand._h, mtw.ctypes.data if mtw.size else None,
+                                           bmw.ctypes.data if with_blocks else None, self._stream()), "dint_index_max_weights")
+        return (mtw, bmw) if with_blocks else mtw
+
 
 class WandData:
     """The wand data's document lengths on the device (dint_wand_data_create): norm_lens f32[num_docs], as
@@ -664,6 +678,15 @@ class WandData:
             mw = np.ascontiguousarray(max_term_weight, dtype=np.float32)
             _check(_lib.dint_wand_data_create_with_max_weights(device, nl.ctypes.data, nl.size, mw.ctypes.data, mw.size,
                                                                C.byref(self._h)), "dint_wand_data_create_with_max_weights")
+
+    def set_block_max_weights(self, block_max_weight) -> None:
+        """Block maxima (QueryIndex.max_weights(..., with_blocks=True)'s second array) for ranked_or_maxscore_queries: with
+        them the call bounds a candidate by the maxima of the blocks it falls in (dint_wand_data_set_block_max_weights).
+        Raises DintError (DINT_ERR_ARG) for a NaN or negative value and leaves the handle as it was; a second call replaces
+        the first's maxima. Not to be called while another thread runs a query with this handle."""
+        bm = np.ascontiguousarray(block_max_weight, dtype=np.float32)
+        _check(_lib.dint_wand_data_set_block_max_weights(self._h, bm.ctypes.data if bm.size else None, bm.size),
+               "dint_wand_data_set_block_max_weights")
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None

@@ -490,6 +490,45 @@ int dint_ranked_or_maxscore_queries(dint_query_index* qi, const dint_dict* freqs
                                     const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts,
                                     float* scores, uint32_t* docids, uint64_t* blocks_read, void* stream);
 
+/* ---- the wand data's BM25 maxima from the index, on the device; block maxima for the pruned call --------------
+ * Replaces: the max_term_weight half of wand_data's constructor (include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp),
+ * which walks the uncompressed collection posting by posting, by one decode of the INDEX: a caller that has only what this
+ * library serves from (the index and the document sizes, for norm_lens) can build the maxima.
+ * block_max_weight[b] (HOST, nullable: not wanted; one per block of the block table the query index was created from, in
+ * that table's order) = the largest f / (f + k1 * ((1 - b) + b * norm_lens[d])) over the postings (d, f) of block b, every
+ * operation a binary32 one, uncontracted: the expression of the scoring kernels without the query weight, and of
+ * dinth_wand_data. max_term_weight[t] (HOST, n_lists of the query index) = the largest block_max_weight over list t's
+ * blocks, 0.0f for a list without a block. Every maximum starts at 0.0f and takes a value only if it is larger, as the
+ * host's std::max(max, score) does: a NaN (a norm_len of 0 under a freq that wrapped to 0), a negative value or -0.0f never
+ * enters it. A maximum of binary32 values does not depend on the order they are taken in, so max_term_weight equals
+ * dinth_wand_data's array bit for bit (include/dint_host.h; wd's norm_lens being that call's).
+ * Every block's docs and freqs parts are decoded once, in passes of consecutive blocks of at most
+ * DINT_OPT_QUERY_OR_PASS_PAGES pages (a list may span passes), into the query index's workspaces, under the handle's lock
+ * like the query calls; the results come back in one copy and the call returns after synchronising `stream`.
+ * DINT_ERR_ARG, before anything is launched: a null handle, a null max_term_weight with n_lists != 0, a freqs_dict of another
+ * kind or device than the docs dictionary, a wand handle on another device or one whose num_docs does not exceed the index's
+ * largest docID. An index of zero blocks returns DINT_OK and writes zeros. */
+int dint_index_max_weights(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, float* max_term_weight,
+                           float* block_max_weight, void* stream);
+
+/* Gives a wand handle block maxima (HOST, n_blocks floats: dint_index_max_weights' block_max_weight for the query index the
+ * handle will be used with): a device copy on the handle's device, owned by the handle; calling it again replaces the copy.
+ * A NaN or negative value is DINT_ERR_ARG, checked before the device is touched, and the handle is left as it was; -0.0f,
+ * +inf and FLT_MAX are accepted (the rule of dint_wand_data_create_with_max_weights). NOT thread-safe against calls running
+ * on the same handle: set the maxima before the handle is shared.
+ * With block maxima dint_ranked_or_maxscore_queries bounds the non-essential terms per candidate: the sum of their term
+ * maxima gives way to the candidate's own sum — from 0.0 in double over those terms in ascending term id, (double) of the
+ * binary32 product q_weight_t * block_max_weight[the first block of t whose last docID is >= the candidate], nothing for a
+ * term whose list ends before the candidate — wherever that sum is the smaller of the two (it is, for block maxima no
+ * larger than their list's max_term_weight); the comparison, its margin, the seed, theta, the split by TERM maxima, the
+ * claims, the scores and the selection are unchanged. A handle whose n_blocks differs from the query index's block
+ * count is DINT_ERR_ARG there, before anything is launched; a handle without block maxima behaves as it always did.
+ * SAFETY ASSUMPTION, beside the one on max_term_weight: block_max_weight[b] >= the doc_term_weight of every posting of
+ * block b. Then the call still returns dint_ranked_or_queries' answer bit for bit, and *blocks_read can only fall: any
+ * larger block maxima give the same answer, and +inf reads exactly the blocks the handle read without block maxima. Smaller block maxima do what smaller term maxima do: documents may
+ * be missing, never wrong (every returned pair is a document of the union with its exact score, in order). */
+int dint_wand_data_set_block_max_weights(dint_wand_data* wd, const float* block_max_weight, size_t n_blocks);
+
 /* ---- BM25 scores and term frequencies of caller-given documents over the same query index -----------
  * Replaces: the cursor primitive under every query, document_enumerator::next_geq(d) then freq()
  * (include/dint/dict_posting_list.hpp:126-169), with ranked_or_query's sums (include/ds2i/queries.hpp:387-457), for a batch

@@ -2,13 +2,16 @@
 //
 //   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
-//   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore, several separated by ':'
+//   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax, several
+//               separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
 //               BM25 top 10 of the union) is not in the reference driver's list, and is answered as ranked_and is, with
 //               the wand file, and refused the same way without one; ranked_or_maxscore is ranked_or with MaxScore's pruning
 //               (the same results; the wand file's max_term_weight goes to the device handle), also only with a wand file;
+//               ranked_or_blockmax is ranked_or_maxscore on a handle that also carries block maxima, computed from the index
+//               at start-up (dint_index_max_weights, dint_wand_data_set_block_max_weights);
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -101,13 +104,22 @@ int main(int argc, char** argv) {
             throw std::runtime_error("could not place the index on the device");
         dint_query_index* qi = nullptr;
         dint_ok(dint_query_index_create(docs_dict, d_index, index_bytes, blocks, n_blocks, n_lists, &qi), "dint_query_index_create");
-        dint_wand_data* wand = nullptr;
+        dint_wand_data *wand = nullptr, *wand_blockmax = nullptr;  // (the second: with block maxima, for ranked_or_blockmax)
         if (wand_filename) {  // (the reference maps the wand data once, src/queries.cpp:84-89)
             tool::blob norm_lens, max_term_weight;
             tool::host_ok(dinth_read_wand_data(wand_filename, &norm_lens.h, &max_term_weight.h), "dinth_read_wand_data");
             dint_ok(dint_wand_data_create_with_max_weights(0, static_cast<const float*>(norm_lens.data()), norm_lens.size() / 4,
                                                            static_cast<const float*>(max_term_weight.data()), max_term_weight.size() / 4, &wand),
                     "dint_wand_data_create_with_max_weights");
+            if ((":" + query_type + ":").find(":ranked_or_blockmax:") != std::string::npos) {
+                dint_ok(dint_wand_data_create_with_max_weights(0, static_cast<const float*>(norm_lens.data()), norm_lens.size() / 4,
+                                                               static_cast<const float*>(max_term_weight.data()), max_term_weight.size() / 4,
+                                                               &wand_blockmax),
+                        "dint_wand_data_create_with_max_weights");
+                std::vector<float> term_max(n_lists), block_max(n_blocks);
+                dint_ok(dint_index_max_weights(qi, freqs_dict, wand_blockmax, term_max.data(), block_max.data(), nullptr), "dint_index_max_weights");
+                dint_ok(dint_wand_data_set_block_max_weights(wand_blockmax, block_max.data(), n_blocks), "dint_wand_data_set_block_max_weights");
+            }
         }
         constexpr uint32_t kTopK = 10;  // ranked_and_query(wdata, 10), src/queries.cpp:106-108
         std::vector<float> top_scores;
@@ -120,7 +132,8 @@ int main(int argc, char** argv) {
             a = b + 1;
         }
         for (auto const& t : types) {
-            const bool is_maxscore = t == "ranked_or_maxscore" && wand;
+            const bool is_blockmax = t == "ranked_or_blockmax" && wand_blockmax;
+            const bool is_maxscore = (t == "ranked_or_maxscore" && wand) || is_blockmax;
             const bool is_ranked_or = t == "ranked_or" && wand;
             const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
@@ -134,7 +147,7 @@ int main(int argc, char** argv) {
                 uint64_t fblocks = 0;
                 if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
-                    dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
+                    dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
                                                             nullptr, nullptr),
                             "dint_ranked_or_maxscore_queries");
                 } else if (is_ranked_or) {
@@ -201,6 +214,7 @@ int main(int argc, char** argv) {
             std::cout << ", \"device\": \"" << device_name << "\"}" << std::endl;
         }
         dint_wand_data_destroy(wand);
+        dint_wand_data_destroy(wand_blockmax);
         dint_query_index_destroy(qi);
         dint_free(blocks);
         (void)hipFree(d_index);
