@@ -29,6 +29,7 @@
 #include "dint_query_kernels.hpp"
 #include "dint_or_query_kernels.hpp"
 #include "dint_ranked_query_kernels.hpp"
+#include "dint_ranked_bool_kernels.hpp"
 #include "dint_ranked_or_query_kernels.hpp"
 #include "dint_ranked_or_maxscore_kernels.hpp"
 #include "dint_score_documents_kernels.hpp"
@@ -49,6 +50,7 @@
 #include "host/hip_api_query_and.inc"
 #include "host/hip_api_or_query.inc"
 #include "host/hip_api_ranked_query.inc"
+#include "host/hip_api_ranked_bool.inc"
 #include "host/hip_api_ranked_or_query.inc"
 #include "host/hip_api_ranked_or_maxscore.inc"
 #include "host/hip_api_score_documents.inc"

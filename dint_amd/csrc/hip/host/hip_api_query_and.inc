@@ -1,15 +1,30 @@
 // Part of dint_hip.hip (one translation unit; included from there, in order): extern "C": conjunctive queries (queries.hpp:34-84).
 // ---- conjunctive queries ------------------------------------------------------------------------
 
+// A ranked boolean call's steps behind the AND rounds (hip_api_ranked_bool.inc): per step j and query q, at
+// [j * n_queries + q], the first block and the block count of the query's j-th excluded / optional term in ascending term
+// id (0 blocks: the query has fewer terms, or the list is empty) and the optional term's q_weight. Once staged
+// (bool_stage_steps): the tables and a claim counter per step on the device; at the end h_claims, the counters' values.
+struct bool_steps {
+    std::vector<uint32_t> not_first, not_blocks, should_first, should_blocks;
+    std::vector<float> should_weight;
+    size_t n_not = 0, n_should = 0;  // steps: the most excluded / optional terms of a query
+    const uint32_t *d_not_first = nullptr, *d_not_blocks = nullptr, *d_should_first = nullptr, *d_should_blocks = nullptr;
+    const float* d_should_weight = nullptr;
+    uint32_t* d_step_count = nullptr;  // [0, n_not): the excluded steps, then the optional ones
+    std::vector<uint32_t> h_claims;
+};
+
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split = true,
-                            const ranked_args* rk = nullptr);
+                            const ranked_args* rk = nullptr, bool_steps* extra = nullptr);
 
 // One AND call: what its stages share.
 struct and_call {
     dint_query_index* qi = nullptr;
     const dint_dict* freqs_dict = nullptr;  // and_query<true>: the freqs pass runs
     const ranked_args* rk = nullptr;        // ranked_and: the freqs pass scores and selects
+    bool_steps* extra = nullptr;            // ranked_bool: excluded steps before the freqs pass, optional steps inside it
     size_t n_queries = 0;
     uint64_t* counts = nullptr;
     hipStream_t s = nullptr;
@@ -46,6 +61,12 @@ static bool any_full_block(const and_call& c) {
             if (c.qi->list_len[c.plan.of(q)[j]] >= kBlock) return true;
     return false;
 }
+
+// the extra steps (hip_api_ranked_bool.inc): staged with the call's inputs; the excluded terms' steps and the recount
+// behind the AND rounds; the optional terms' steps behind the freqs pass's required terms
+static void bool_stage_steps(and_call& c, const and_bool_layout& L);
+static int bool_exclude_pass(and_call& c);
+static int bool_should_pass(and_call& c);
 
 // the candidates: the rarest list of every query, a page per block
 static void and_candidate_pages(and_call& c) {
@@ -204,10 +225,13 @@ static int and_batch_form(and_call& c, const and_batch_plan& bp, const and_batch
 // runs: a bound of the pages each decodes (the live candidates at most, and no more blocks than the round's lists have) ----
 static int and_stage_general(and_call& c) {
     dint_query_index* qi = c.qi;
-    const and_general_layout L(c.n_pages, c.term_first.size(), c.n_queries, c.rounds, kCtrlWords, sizeof(fused_step));
+    const bool_steps* const x = c.extra;  // (none: and_general_layout itself)
+    const and_bool_layout L(c.n_pages, c.term_first.size(), c.n_queries, c.rounds, kCtrlWords, sizeof(fused_step), x ? x->not_first.size() : 0,
+                            x ? x->should_first.size() : 0, x ? x->n_not + x->n_should : 0);
     HIP_TRY(qi->stage(std::max(L.words * 4, c.n_queries * sizeof(unsigned long long))));
     if (!qi->inputs.ensure(L.words + 4) || !qi->cand.ensure(c.n_slots) || !qi->target.ensure(c.n_slots)) return DINT_ERR_HIP;
     and_stage_tables(c, L);
+    if (c.extra) bool_stage_steps(c, L);
     std::memset(qi->h(L.ctrl), 0, (L.steps - L.ctrl) * 4);
     c.d_page_block = qi->d(L.page_block);
     c.d_page_query = qi->d(L.page_query);
@@ -443,7 +467,8 @@ static int and_batch_rounds(and_call& c, bool searched0, unsigned long long* hos
 // the host knows — no more blocks than matches can exist, than the terms' lists hold, than the candidate pages for
 // the rarest term — and the pages past the count are empty. Past kAsyncPages the count is read back after all,
 // as in the rounds above. The counts themselves travel to the host with the results.)
-// rk (ranked_and): a score per candidate slot, from 0.0f, summed by ranked_gather_kernel; then ranked_topk. ----
+// rk (ranked_and): a score per candidate slot, from 0.0f, summed by ranked_gather_kernel; then ranked_topk.
+// c.extra (ranked_bool): the optional terms' steps between the two; without it the launches are what they were. ----
 static int and_freqs_pass(and_call& c) {
     dint_query_index* qi = c.qi;
     const size_t n_queries = c.n_queries, n_terms = c.rounds + 1;
@@ -496,6 +521,10 @@ static int and_freqs_pass(and_call& c) {
                            qi->d_needed, d_count);
     }
     HIP_TRY(hipGetLastError());
+    if (c.extra) {
+        const int st = bool_should_pass(c);
+        if (st != DINT_OK) return st;
+    }
     if (rk) {
         const int st = ranked_topk(qi, *rk, c.page_query, n_queries, c.s);
         if (st != DINT_OK) return c.failed(st);
@@ -529,7 +558,7 @@ static int and_copy_back(and_call& c, uint64_t* freq_sums, uint64_t* freq_blocks
 // tails or batch rounds — then, with a freqs dictionary, the freqs / ranked pass, and the copy back.
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split,
-                            const ranked_args* rk) {
+                            const ranked_args* rk, bool_steps* extra) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -538,6 +567,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     c.qi = qi;
     c.freqs_dict = freqs_dict;
     c.rk = rk;
+    c.extra = extra;
     c.n_queries = n_queries;
     c.counts = counts;
     c.s = static_cast<hipStream_t>(stream);
@@ -574,6 +604,10 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     }
     if (st != DINT_OK) return st;
     HIP_TRY(hipGetLastError());
+    if (extra) {
+        st = bool_exclude_pass(c);
+        if (st != DINT_OK) return st;
+    }
     if (freqs_dict) {
         st = and_freqs_pass(c);
         if (st != DINT_OK) return st;

@@ -53,6 +53,19 @@ struct and_general_layout : and_tables_layout {
         steps = take((rounds + 1) * ((step_bytes + 7) / 8 * 2), 2);
     }
 };
+// The general form with a ranked boolean call's extra steps behind it (with none of them: and_general_layout itself, word
+// for word): per excluded step and query {first block, blocks} (n_not_tab = steps * n_queries each), per optional step and
+// query {first block, blocks, q_weight}, then a claim counter per step (zeros, copied in with the rest).
+struct and_bool_layout : and_general_layout {
+    size_t not_first, not_blocks, should_first, should_blocks, should_weight, step_count;
+    and_bool_layout(size_t n_pages, size_t n_tab, size_t n_queries, size_t rounds, size_t ctrl_words, size_t step_bytes, size_t n_not_tab,
+                    size_t n_should_tab, size_t n_steps)
+        : and_general_layout(n_pages, n_tab, n_queries, rounds, ctrl_words, step_bytes) {
+        take_each({&not_first, &not_blocks}, n_not_tab);
+        take_each({&should_first, &should_blocks, &should_weight}, n_should_tab);
+        step_count = take(n_steps);
+    }
+};
 // An OR pass (and the pruned ranked call's seeds): page -> block, page -> term record, then per term record {first
 // block, blocks, first page, query, from} and, ranked, {the records of its query by term id, its query's terms, q_weight}.
 struct or_pass_layout : stage_layout {

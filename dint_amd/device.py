@@ -35,7 +35,7 @@ ABI_SYMBOLS = (
     "dint_list_cache_create", "dint_list_cache_decode", "dint_list_cache_destroy",
     "dint_block_table_create", "dint_block_table_destroy", "dint_block_table_learn", "dint_block_table_ready", "dint_block_table_info_get", "dint_decode_block_table",
     "dint_query_index_create", "dint_query_index_destroy", "dint_and_queries", "dint_and_queries_freqs", "dint_or_queries", "dint_or_queries_freqs",
-    "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_or_queries",
+    "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_bool_queries", "dint_ranked_or_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -129,6 +129,7 @@ def _load():
     lib.dint_wand_data_destroy.restype = None
     lib.dint_wand_data_destroy.argtypes = [vp]
     lib.dint_ranked_and_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, vp]
+    lib.dint_ranked_bool_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_or_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
@@ -599,6 +600,29 @@ class QueryIndex:
         (counts u64[n] = min(k, matches), scores f32[n, k] descending, docids u32[n, k]; equal scores by ascending docID,
         0.0 / 0xFFFFFFFF past a query's count)."""
         return self._ranked("dint_ranked_and_queries", freqs_dict, wand, queries, k)
+
+    def ranked_bool_queries(self, freqs_dict: "Dictionary", wand: "WandData", must, should=None, exclude=None, k: int = 10):
+        """Ranked boolean queries (dint_ranked_bool_queries): per query the documents in every list of
+        must[q] and in no list of exclude[q], scored over the required terms as ranked_and_queries scores them and then over
+        the optional terms of should[q] whose list holds the document, in ascending term id. should / exclude: None, or a
+        sequence per query like must. A query without a required term selects nothing -> (counts u64[n] = min(k, matches),
+        matches u64[n], scores f32[n, k] descending, docids u32[n, k] as ranked_and_queries, blocks decoded behind the AND
+        rounds)."""
+        n = len(must)
+        assert all(c is None or len(c) == n for c in (should, exclude))
+        m_terms, m_offs = _pack_queries(must)
+        packed = [_pack_queries(c) if c is not None else (None, None) for c in (should, exclude)]
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        blocks = C.c_uint64()
+        _check(_lib.dint_ranked_bool_queries(self._h, freqs_dict._h, wand._h, k, m_terms.ctypes.data, m_offs.ctypes.data,
+                                             ptr(packed[0][0]), ptr(packed[0][1]), ptr(packed[1][0]), ptr(packed[1][1]), n,
+                                             counts.ctypes.data, matches.ctypes.data, scores.ctypes.data, docids.ctypes.data,
+                                             C.byref(blocks), self._stream()), "dint_ranked_bool_queries")
+        return counts, matches, scores, docids, blocks.value
 
     def ranked_or_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10):
         """ranked_or_query (include/ds2i/queries.hpp:387-457) for a batch: BM25 top-k of the union, each document's score

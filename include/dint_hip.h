@@ -446,6 +446,44 @@ int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, c
                             const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts,
                             float* scores, uint32_t* docids, void* stream);
 
+/* ---- ranked boolean queries (required, optional and excluded terms; BM25 top-k) over the same query index ----
+ * Replaces: ranked_and_query (include/ds2i/queries.hpp:309-385) generalised to the mix a caller of a BM25 index asks for —
+ * documents that contain ALL of the required terms and NONE of the excluded ones, ranked with the optional terms counted
+ * where they occur (Lucene's MUST / MUST_NOT / SHOULD) — over the cursor primitive next_geq + freq()
+ * (include/dint/dict_posting_list.hpp:126-169), for a batch of queries per call. dint_ranked_and_queries ignores optional
+ * terms and excludes nothing; dint_ranked_or_queries with a large k, filtered by the caller, decodes every block and is
+ * capped at DINT_RANKED_MAX_K; re-scoring dint_ranked_and_queries' top k (dint_score_documents) ranks a top k that was chosen
+ * without the optional terms.
+ * The three clauses are HOST terms / offsets pairs laid out as in every query call (offsets: n_queries + 1 entries); a
+ * pair may be null when the clause is empty for every query. Within a clause repeated terms are one term with multiplicity
+ * qf (query_freqs, queries.hpp:135-148); the clauses are independent: a term in both `must` and `should` is scored once in
+ * each phase, a term in both `must` and `not` matches nothing.
+ * The matches of query q: the documents in every list of must[q] and in no list of not[q]. A QUERY WITHOUT A REQUIRED TERM
+ * SELECTS NOTHING (count 0, outputs empty): the union-driven query is dint_ranked_or_queries', and exclusions over a union
+ * are out of scope. The score of a match d starts at 0.0f; the required terms are added in dint_ranked_and_queries' order
+ * (increasing list length, equal lengths by increasing term id), then the optional terms whose list holds d, in ascending
+ * term id; every addend is q_weight_t * doc_term_weight(freq_t(d), norm_lens[d]), q_weight_t = query_term_weight(qf_t within
+ * its clause, the list's length, wd's num_docs), every operation a binary32 one, uncontracted, as in
+ * dint_ranked_and_queries. An optional term whose list is empty, or ends before d, adds nothing.
+ * matches[q] (HOST, nullable) = the number of matches; counts[q] = min(k, matches); scores, docids (nullable), their order
+ * (descending score, equal scores by ascending docID) and their filler (0.0f / 0xFFFFFFFF) are dint_ranked_and_queries'.
+ * With empty `should` and `not` clauses the call returns dint_ranked_and_queries' answer for the `must` clause, bit for bit.
+ * Lazy: behind the AND rounds of the required terms, the excluded terms — in ascending term id — decode docs parts only,
+ * and only of the blocks the candidates still alive (the intersection's documents no earlier excluded term removed) fall
+ * in; exclusion runs before any scoring, and the required and optional terms decode docs and freqs parts only of the
+ * blocks the MATCHES fall in. A candidate past a list's last docID claims nothing.
+ * *blocks_decoded (nullable) = the block claims of these steps behind the AND rounds. For a call of one query it is exact:
+ * the sum over the excluded, required and optional terms of the distinct blocks just described. In a batch a block that
+ * several queries claim in the same step counts once, so the batch's value is at most the sum of the one-query values.
+ * DINT_ERR_ARG, before anything is launched: what dint_ranked_and_queries refuses (k == 0 or k > DINT_RANKED_MAX_K, a
+ * freqs_dict of another kind or device, a wand handle on another device or one whose num_docs does not exceed the index's
+ * largest docID, null counts or scores), and decreasing offsets or a term >= n_lists in any clause. The handle's lock and
+ * the stream are as for dint_ranked_and_queries; every query takes the round-per-launch form. */
+int dint_ranked_bool_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                             const uint32_t* must_terms, const uint64_t* must_offsets, const uint32_t* should_terms,
+                             const uint64_t* should_offsets, const uint32_t* not_terms, const uint64_t* not_offsets, size_t n_queries,
+                             uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids, uint64_t* blocks_decoded, void* stream);
+
 /* ---- ranked disjunctive queries (BM25 top-k of the union) over the same query index --------------
  * Replaces: ranked_or_query (include/ds2i/queries.hpp:387-457) for a batch of queries per call. (Not a query type of
  * the reference's driver, src/queries.cpp:93-111.)

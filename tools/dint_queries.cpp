@@ -2,7 +2,7 @@
 //
 //   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
-//   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax, several
+//   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool, several
 //               separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
@@ -12,6 +12,10 @@
 //               (the same results; the wand file's max_term_weight goes to the device handle), also only with a wand file;
 //               ranked_or_blockmax is ranked_or_maxscore on a handle that also carries block maxima, computed from the index
 //               at start-up (dint_index_max_weights, dint_wand_data_set_block_max_weights);
+//               ranked_bool (dint_ranked_bool_queries, BM25 top 10 of the documents that hold every required and no
+//               excluded term, the optional terms counted where they occur) reads its query lines as
+//               tokens — +t required, -t excluded, a bare t optional — and so must be the only type of its run; also only
+//               with a wand file;
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -67,12 +71,32 @@ int main(int argc, char** argv) {
             std::cerr << "ERROR: Unknown type " << type << std::endl;  // src/queries.cpp:147-149
             return 0;
         }
+        const bool is_bool = query_type == "ranked_bool";
+        if (!is_bool && (":" + query_type + ":").find(":ranked_bool:") != std::string::npos)
+            throw std::runtime_error("ranked_bool reads its query lines as +t / -t / t tokens: it must be the only query type of a run");
         // read_query (queries.hpp:15-27)
         std::vector<std::vector<uint32_t>> queries;
+        // ranked_bool: `queries` holds the required terms; the optional and excluded ones packed, offsets per query
+        std::vector<uint32_t> should_terms, not_terms;
+        std::vector<uint64_t> should_offs(1, 0), not_offs(1, 0);
         for (std::string line; std::getline(std::cin, line);) {
             std::istringstream iline(line);
             std::vector<uint32_t> q;
-            for (uint32_t t; iline >> t;) q.push_back(t);
+            if (is_bool) {
+                for (std::string tok; iline >> tok;) {
+                    const char sign = tok[0];
+                    const std::string digits = sign == '+' || sign == '-' ? tok.substr(1) : tok;
+                    if (digits.empty() || digits.find_first_not_of("0123456789") != std::string::npos || digits.size() > 10 ||
+                        std::stoull(digits) > 0xFFFFFFFFull)
+                        throw std::runtime_error("ranked_bool: not a term token: " + tok);
+                    const uint32_t t = uint32_t(std::stoull(digits));
+                    (sign == '+' ? q : sign == '-' ? not_terms : should_terms).push_back(t);
+                }
+                should_offs.push_back(should_terms.size());
+                not_offs.push_back(not_terms.size());
+            } else {
+                for (uint32_t t; iline >> t;) q.push_back(t);
+            }
             queries.push_back(q);
         }
         std::cerr << "Loading index from " << index_filename << std::endl;
@@ -82,6 +106,9 @@ int main(int argc, char** argv) {
         const size_t n_lists = size_t(v.header.n_lists);
         for (auto const& q : queries)
             for (uint32_t t : q)
+                if (t >= n_lists) throw std::runtime_error("query term " + std::to_string(t) + " is not a list of this index");
+        for (auto const* clause : {&should_terms, &not_terms})
+            for (uint32_t t : *clause)
                 if (t >= n_lists) throw std::runtime_error("query term " + std::to_string(t) + " is not a list of this index");
 
         std::string device_name = "unknown";
@@ -135,17 +162,24 @@ int main(int argc, char** argv) {
             const bool is_blockmax = t == "ranked_or_blockmax" && wand_blockmax;
             const bool is_maxscore = (t == "ranked_or_maxscore" && wand) || is_blockmax;
             const bool is_ranked_or = t == "ranked_or" && wand;
-            const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore;
+            const bool is_ranked_bool = t == "ranked_bool" && wand;
+            const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore || is_ranked_bool;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
                 std::cerr << "Unsupported query type: " << t << std::endl;  // src/queries.cpp:108-110
                 continue;
             }
             const bool with_freqs = t == "and_freq" || t == "or_freq";
             const bool is_or = t == "or" || t == "or_freq";
-            // one call of the query type's entry: n queries, packed
-            auto run_queries = [&](const uint32_t* q_terms, const uint64_t* q_offs, size_t n, uint64_t* q_counts, uint64_t* q_fsums) {
+            // one call of the query type's entry: n queries, packed (q0: the first of them in the log)
+            auto run_queries = [&](const uint32_t* q_terms, const uint64_t* q_offs, size_t n, uint64_t* q_counts, uint64_t* q_fsums, size_t q0) {
                 uint64_t fblocks = 0;
-                if (is_maxscore) {
+                if (is_ranked_bool) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    dint_ok(dint_ranked_bool_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, should_terms.data(), should_offs.data() + q0,
+                                                     not_terms.data(), not_offs.data() + q0, n, q_counts, nullptr, top_scores.data(), nullptr,
+                                                     nullptr, nullptr),
+                            "dint_ranked_bool_queries");
+                } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
                                                             nullptr, nullptr),
@@ -170,11 +204,12 @@ int main(int argc, char** argv) {
             std::vector<double> query_times;
             uint64_t total = 0, total_one_run = 0;
             for (size_t run = 0; run != runs; ++run) {  // op_perftest
-                for (auto const& q : queries) {
+                for (size_t i = 0; i != queries.size(); ++i) {
+                    auto const& q = queries[i];
                     const uint64_t offs[2] = {0, q.size()};
                     uint64_t results = 0, fsum = 0;
                     const double tick = now_us();
-                    run_queries(q.data(), offs, 1, &results, &fsum);
+                    run_queries(q.data(), offs, 1, &results, &fsum, i);
                     total += results;
                     if (run == 0) total_one_run += results;
                     if (run != 0) query_times.push_back(now_us() - tick);  // first run is not timed
@@ -192,7 +227,7 @@ int main(int argc, char** argv) {
                 double best = 1e300;
                 for (size_t run = 0; run != std::min<size_t>(runs, 4); ++run) {
                     const double tick = now_us();
-                    run_queries(terms.data(), offs.data(), queries.size(), counts.data(), fsums.data());
+                    run_queries(terms.data(), offs.data(), queries.size(), counts.data(), fsums.data(), 0);
                     if (run != 0) best = std::min(best, now_us() - tick);
                 }
                 batch_us = best / double(queries.size());
