@@ -31,6 +31,7 @@
 #include "dint_ranked_query_kernels.hpp"
 #include "dint_ranked_bool_kernels.hpp"
 #include "dint_ranked_or_query_kernels.hpp"
+#include "dint_ranked_or_bool_kernels.hpp"
 #include "dint_ranked_or_maxscore_kernels.hpp"
 #include "dint_score_documents_kernels.hpp"
 #include "dint_wand_kernels.hpp"
@@ -52,6 +53,7 @@
 #include "host/hip_api_ranked_query.inc"
 #include "host/hip_api_ranked_bool.inc"
 #include "host/hip_api_ranked_or_query.inc"
+#include "host/hip_api_ranked_or_bool.inc"
 #include "host/hip_api_ranked_or_maxscore.inc"
 #include "host/hip_api_score_documents.inc"
 #include "host/hip_api_wand.inc"

@@ -7,10 +7,25 @@
 // call's counters. The counters come back once, at the end. The claim flags and tables of the AND forms are not touched.
 // rk (dint_ranked_or_queries, hip_api_ranked_or_query.inc): the pass's probe launch is ranked_or_score_kernel instead, and
 // ranked_topk writes the best keys of the pass's queries to rk->keys at their own offset; the counters are not used.
+// xb (dint_ranked_or_bool_queries, hip_api_ranked_or_bool.inc), with rk: the scoring launch is ranked_or_bool_score_kernel,
+// which also drops the documents in fewer than m lists; the excluded terms' steps (bool_step) and and_count_kernel run
+// between it and ranked_topk, and the counters come back with the last pass. Without xb nothing is launched differently.
+
+// What a ranked OR call with a minimum and exclusions adds to its passes, and what it gets back.
+struct or_bool_args {
+    const uint32_t* m = nullptr;           // per query: the distinct optional terms whose list must hold a match (>= 1)
+    std::vector<uint32_t> not_terms;       // every query's distinct excluded terms, ascending: query q's at [not_at[q], not_at[q + 1])
+    std::vector<uint64_t> not_at;          // n_queries + 1
+    uint64_t eager_blocks = 0;             // out: the blocks the passes decode before any step
+    std::vector<std::vector<uint32_t>> step_claims;  // out: per pass with steps, per step the blocks it claimed
+    std::vector<unsigned long long> h_matches;       // out: the call's counters (a query the call did not run: 0)
+    bool claimed = false;  // a pass of this call has run a step: the handle's claims_dirty is this call's to clear at its end
+};
 
 // The set-up of an OR call, shared with the pruned ranked call (hip_api_ranked_or_maxscore.inc): the plan (longest list
 // first, with multiplicities if with_qf), every query's pages (every block of its distinct terms; a query without any
-// has len 0) and the passes: whole queries, at most `limit` pages each — a query larger than that alone, in a pass sized to it.
+// has len 0, and so has one of fewer distinct terms than its min_match) and the passes: whole queries, at most `limit`
+// pages each — a query larger than that alone, in a pass sized to it.
 struct or_passes {
     query_plan plan;
     std::vector<uint64_t> pages;  // per query
@@ -18,7 +33,8 @@ struct or_passes {
     uint64_t all = 0;
 };
 static int plan_or_passes(const dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries,
-                          bool with_qf, bool with_freqs, uint64_t* counts, uint64_t* freq_sums, or_passes& op) {
+                          bool with_qf, bool with_freqs, uint64_t* counts, uint64_t* freq_sums, or_passes& op,
+                          const uint32_t* min_match = nullptr) {
     query_plan& plan = op.plan;
     const int planned = plan_queries(qi, terms, query_offsets, n_queries, true, with_qf, with_freqs, counts, freq_sums, plan);
     if (planned != DINT_OK) return planned;
@@ -27,6 +43,7 @@ static int plan_or_passes(const dint_query_index* qi, const uint32_t* terms, con
     for (size_t q = 0; q != n_queries; ++q) {
         for (uint32_t j = 0; j != plan.len[q]; ++j) op.pages[q] += qi->blocks_of(plan.of(q)[j]);
         if (op.pages[q] == 0) plan.len[q] = 0;  // (lists without a block)
+        if (min_match && min_match[q] > plan.len[q]) plan.len[q] = 0, op.pages[q] = 0;  // (more lists asked for than the query has)
         op.all += op.pages[q];
     }
     op.first = cut_passes(n_queries, {{op.pages.data(), uint64_t(opt(DINT_OPT_QUERY_OR_PASS_PAGES))}}, false);
@@ -42,16 +59,26 @@ struct or_pass_query {
 // The pass of `qs` on the stream: the inputs (or_pass_layout) staged — in an area
 // of at least min_stage bytes — and copied in, the pages' decode, and or_count_kernel, which adds to d_counts and the
 // sums behind them; or (rk) ranked_or_score_kernel over the union's representatives and ranked_topk, which selects the
-// best rk->k of the queries id0 .. id0 + n_ids - 1 into rk->keys. No wait.
+// best rk->k of the queries id0 .. id0 + n_ids - 1 into rk->keys. No wait. xb (with rk and d_counts): or_bool_layout staged
+// behind the pass's own; between the scoring and the selection, per excluded term of the pass's queries in ascending term
+// id a step over the pass's slots (bool_step: search, claim, the docs parts decoded into qi->probe — the scoring has read
+// the pass's pages by then —, the candidates found killed, release), then and_count_kernel into d_counts from id0 on.
 static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const ranked_args* rk, const std::vector<or_pass_query>& qs,
-                       size_t min_stage, unsigned long long* d_counts, size_t n_counts, uint32_t id0, size_t n_ids, hipStream_t s) {
+                       size_t min_stage, unsigned long long* d_counts, size_t n_counts, uint32_t id0, size_t n_ids, hipStream_t s,
+                       or_bool_args* xb = nullptr) {
     uint64_t n_pages = 0, n_terms = 0;
     for (const or_pass_query& q : qs) {
         n_terms += q.n;
         for (uint32_t j = 0; j != q.n; ++j) n_pages += qi->blocks_of(q.terms[j]);
     }
     const or_pass_layout L(n_pages, n_terms, rk != nullptr);
-    if (qi->stage(std::max<size_t>(L.words * 4, min_stage)) != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
+    size_t n_steps = 0;  // (xb: the most excluded terms of a query of the pass that has pages)
+    if (xb)
+        for (const or_pass_query& q : qs)
+            if (q.n) n_steps = std::max<size_t>(n_steps, xb->not_at[q.id + 1] - xb->not_at[q.id]);
+    const or_bool_layout B(L.words, xb ? n_pages : 0, xb ? n_terms : 0, n_steps * n_ids, n_steps);
+    const size_t up_words = B.words;  // (without xb: L.words)
+    if (qi->stage(std::max<size_t>(up_words * 4, min_stage)) != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     uint32_t *page_block = qi->h(L.page_block), *page_term = qi->h(L.page_term), *term_order = qi->h(L.term_order);
     std::vector<uint32_t> page_query(rk ? n_pages : 0);  // (ranked_topk's: the pass's queries, from 0)
     uint32_t page = 0, rec = 0;
@@ -65,6 +92,7 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
             qi->h(L.term_page)[rec] = page;
             qi->h(L.term_query)[rec] = q.id;
             qi->h(L.term_from)[rec] = from;
+            if (xb) qi->h(B.term_m)[rec] = xb->m[q.id];
             if (rk) {
                 qi->h(L.term_n)[rec] = q.n;
                 qi->h<float>(L.term_weight)[rec] = bm25_query_term_weight(q.qf[j], qi->list_len[l], rk->num_docs);
@@ -76,10 +104,20 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
             }
         }
     }
-    if (!qi->inputs.ensure(L.words) || !qi->sub.ensure(n_pages) || !qi->probe.ensure(n_pages * kPageSlots) ||
+    if (xb) {
+        if (n_pages) std::memcpy(qi->h(B.page_query), page_query.data(), n_pages * 4);
+        std::memset(qi->h(B.not_first), 0, (B.words - B.not_first) * 4);
+        for (const or_pass_query& q : qs)
+            for (uint64_t j = 0, n = q.n ? xb->not_at[q.id + 1] - xb->not_at[q.id] : 0; j != n; ++j) {
+                const uint32_t l = xb->not_terms[xb->not_at[q.id] + j];
+                qi->h(B.not_first)[j * n_ids + (q.id - id0)] = qi->list_first[l];
+                qi->h(B.not_blocks)[j * n_ids + (q.id - id0)] = qi->blocks_of(l);
+            }
+    }
+    if (!qi->inputs.ensure(up_words) || !qi->sub.ensure(n_pages) || !qi->probe.ensure(n_pages * kPageSlots) ||
         (freqs_dict && !qi->fprobe.ensure(n_pages * kPageSlots)))
         return stream_failed(s, DINT_ERR_HIP);
-    HIP_TRY(hipMemcpyAsync(qi->inputs.p, qi->h_stage, L.words * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(qi->inputs.p, qi->h_stage, up_words * 4, hipMemcpyHostToDevice, s));
     const int st = gather_decode_pages(qi, qi->d(L.page_block), nullptr, n_pages, 0, freqs_dict, s);
     if (st != DINT_OK) return stream_failed(s, st);
     or_pass p{};
@@ -110,23 +148,55 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
     rp.norm_lens = rk->norm_lens;
     rp.cand = qi->cand.p;
     rp.score = qi->slot_score.p;
-    hipLaunchKernelGGL(ranked_or_score_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, rp);
+    if (!xb) {
+        hipLaunchKernelGGL(ranked_or_score_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, rp);
+    } else {
+        ranked_or_bool_pass bp{};
+        bp.base = rp;
+        bp.term_m = qi->d(B.term_m);
+        hipLaunchKernelGGL(ranked_or_bool_score_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, bp);
+    }
     if (hipGetLastError() != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
+    if (xb) {
+        const uint64_t n_slots = n_pages * kPageSlots;
+        if (n_steps) {
+            if (!qi->target.ensure(n_slots)) return stream_failed(s, DINT_ERR_HIP);
+            // (or_queries_impl has cleared what an earlier call may have left in the claim set, once for the call)
+            qi->claims_dirty = xb->claimed = true;  // until the call has run to its end (or_queries_impl)
+            const bool_slots slots{qi, nullptr, n_slots, qi->d(B.page_query), n_ids, s};
+            for (size_t j = 0; j != n_steps; ++j) {
+                const int xst = bool_step(slots, qi->d(B.not_first) + j * n_ids, qi->d(B.not_blocks) + j * n_ids, qi->h(B.not_blocks) + j * n_ids,
+                                          nullptr, qi->d(B.step_count) + j);
+                if (xst != DINT_OK) return stream_failed(s, xst);
+            }
+            xb->step_claims.emplace_back(n_steps, 0u);
+            if (hipMemcpyAsync(xb->step_claims.back().data(), qi->d(B.step_count), n_steps * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
+                return stream_failed(s, DINT_ERR_HIP);
+        }
+        hipLaunchKernelGGL(and_count_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, n_slots, qi->d(B.page_query),
+                           d_counts + id0);
+        if (hipGetLastError() != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
+    }
     const int rst = ranked_topk(qi, *rk, page_query, n_ids, s);
     return rst != DINT_OK ? stream_failed(s, rst) : DINT_OK;
 }
 
 static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream,
-                           const ranked_args* rk = nullptr) {
+                           const ranked_args* rk = nullptr, or_bool_args* xb = nullptr) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
     if (n_queries >= 0xFFFFFFFFull) return DINT_ERR_ARG;
     or_passes op;  // (rk: with multiplicities, for the query weights)
-    const int planned = plan_or_passes(qi, terms, query_offsets, n_queries, rk != nullptr, freqs_dict != nullptr, counts, freq_sums, op);
+    const int planned = plan_or_passes(qi, terms, query_offsets, n_queries, rk != nullptr, freqs_dict != nullptr, counts, freq_sums, op,
+                                       xb ? xb->m : nullptr);
     if (planned != DINT_OK) return planned;
     const query_plan& plan = op.plan;
+    if (xb) {
+        xb->eager_blocks = op.all;
+        xb->h_matches.assign(n_queries, 0ull);
+    }
     if (op.all == 0) return DINT_OK;
 
     std::lock_guard<std::mutex> lock(qi->mutex);
@@ -136,6 +206,13 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     if (!qi->freq_sums.ensure(2 * n_queries)) return DINT_ERR_HIP;
     unsigned long long* const d_counts = qi->freq_sums.p;
     HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * n_queries * sizeof(unsigned long long), s));
+    // xb with excluded terms: its steps claim in the handle's dense claim set — cleared here, once for the call, of what a
+    // call that failed between a search and its release left behind (and_send_inputs). A call without steps leaves the
+    // flag and the set alone.
+    if (xb && !xb->not_terms.empty() && qi->claims_dirty) {
+        HIP_TRY(hipMemsetAsync(qi->d_needed, 0, 2 * std::max<size_t>(1, qi->n_blocks) * 4, s));
+        qi->claims_dirty = false;
+    }
     std::vector<or_pass_query> qs;
     for (size_t k = 0; k + 1 < op.first.size(); ++k) {
         const size_t q0 = op.first[k], q1 = op.first[k + 1];
@@ -150,10 +227,12 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         ranked_args pass_rk = rk ? *rk : ranked_args{};
         if (rk) pass_rk.keys += uint64_t(q0) * rk->k;  // (the keys of the pass's queries at their own offset)
         const int st = or_run_pass(qi, freqs_dict, rk ? &pass_rk : nullptr, qs, 2 * n_queries * sizeof(unsigned long long), d_counts,
-                                   n_queries, uint32_t(q0), q1 - q0, s);
+                                   n_queries, uint32_t(q0), q1 - q0, s, xb);
         if (st != DINT_OK) return st;
     }
+    if (xb) HIP_TRY(hipMemcpyAsync(xb->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area: the results go there)
+    if (xb && xb->claimed) qi->claims_dirty = false;  // (this call set it, and every step's claims are released)
     if (rk) return DINT_OK;            // (ranked: the keys are already on the host)
     if (qi->stage(2 * n_queries * sizeof(unsigned long long)) != hipSuccess) return DINT_ERR_HIP;
     unsigned long long* const h_res = static_cast<unsigned long long*>(qi->h_stage);

@@ -67,6 +67,19 @@ static bool any_full_block(const and_call& c) {
 static void bool_stage_steps(and_call& c, const and_bool_layout& L);
 static int bool_exclude_pass(and_call& c);
 static int bool_should_pass(and_call& c);
+// What a step of either clause runs over (bool_step, hip_api_ranked_bool.inc): the candidate slots in qi->cand, 256 to a
+// page, a page to a query — of this call, or of an OR pass (hip_api_or_query.inc).
+struct bool_slots {
+    dint_query_index* qi;
+    const dint_dict* freqs_dict;  // (what an optional step decodes freqs parts with)
+    uint64_t n_slots;
+    const uint32_t* d_page_query;  // device: page -> query, the index into the step's rows
+    size_t n_queries;              // ... and the rows' length
+    hipStream_t s;
+    uint32_t slot_grid() const { return uint32_t(n_slots / kPageSlots); }
+};
+static int bool_step(const bool_slots& b, const uint32_t* first, const uint32_t* nblk, const uint32_t* h_nblk, const float* weight,
+                     uint32_t* d_cnt);
 
 // the candidates: the rarest list of every query, a page per block
 static void and_candidate_pages(and_call& c) {

@@ -34,42 +34,45 @@ static void bool_stage_steps(and_call& c, const and_bool_layout& L) {
     x.d_step_count = qi->d(L.step_count);
 }
 
-// One step: `first` / `nblk` (device) and `h_nblk` (host) are the step's row of its clause's tables; weight null: an
-// excluded term (docs parts only), else an optional one. The claims are the first set's, as in the freqs pass.
-static int bool_step(and_call& c, const uint32_t* first, const uint32_t* nblk, const uint32_t* h_nblk, const float* weight, uint32_t* d_cnt) {
-    dint_query_index* qi = c.qi;
+// One step over the slots `b`: `first` / `nblk` (device) and `h_nblk` (host) are the step's row of its clause's tables;
+// weight null: an excluded term (docs parts only), else an optional one. The claims are the first set's, as in the freqs pass.
+static int bool_step(const bool_slots& b, const uint32_t* first, const uint32_t* nblk, const uint32_t* h_nblk, const float* weight,
+                     uint32_t* d_cnt) {
+    dint_query_index* qi = b.qi;
     const uint32_t tb = 256;
     uint64_t list_blocks = 0;
-    for (size_t q = 0; q != c.n_queries; ++q) list_blocks += h_nblk[q];
-    size_t bound = size_t(std::min<uint64_t>(c.n_slots, list_blocks));
+    for (size_t q = 0; q != b.n_queries; ++q) list_blocks += h_nblk[q];
+    size_t bound = size_t(std::min<uint64_t>(b.n_slots, list_blocks));
     if (bound == 0) return DINT_OK;
-    hipLaunchKernelGGL(bool_search_kernel, dim3(c.slot_grid()), dim3(tb), 0, c.s, qi->cand.p, c.n_slots, c.d_page_query, first, nblk,
+    hipLaunchKernelGGL(bool_search_kernel, dim3(b.slot_grid()), dim3(tb), 0, b.s, qi->cand.p, b.n_slots, b.d_page_query, first, nblk,
                        qi->d_block_max, qi->target.p, qi->d_needed, qi->d_rank, qi->d_touched, d_cnt);
     const uint32_t* d_count = d_cnt;
     const bool sized = weight ? sized_by_bound(bound, {{&qi->probe, bound * kPageSlots}, {&qi->fprobe, bound * kPageSlots}})
                               : sized_by_bound(bound, {{&qi->probe, bound * kPageSlots}});
     if (!sized) {
         uint32_t n_touched = 0;
-        HIP_TRY(hipMemcpyAsync(&n_touched, d_cnt, 4, hipMemcpyDeviceToHost, c.s));
-        HIP_TRY(hipStreamSynchronize(c.s));
+        HIP_TRY(hipMemcpyAsync(&n_touched, d_cnt, 4, hipMemcpyDeviceToHost, b.s));
+        HIP_TRY(hipStreamSynchronize(b.s));
         if (n_touched == 0) return DINT_OK;
         bound = n_touched;
         d_count = nullptr;
     }
     if (!qi->sub.ensure(bound) || !qi->probe.ensure(uint64_t(bound) * kPageSlots) || (weight && !qi->fprobe.ensure(uint64_t(bound) * kPageSlots)))
-        return c.failed(DINT_ERR_HIP);
-    const int st = gather_decode_pages(qi, qi->d_touched, d_count, bound, 0, weight ? c.freqs_dict : nullptr, c.s);
-    if (st != DINT_OK) return c.failed(st);
+        return stream_failed(b.s, DINT_ERR_HIP);
+    const int st = gather_decode_pages(qi, qi->d_touched, d_count, bound, 0, weight ? b.freqs_dict : nullptr, b.s);
+    if (st != DINT_OK) return stream_failed(b.s, st);
     if (weight)
-        hipLaunchKernelGGL(bool_should_gather_kernel, dim3(c.slot_grid()), dim3(tb), 0, c.s, qi->cand.p, c.n_slots, c.d_page_query, qi->d_blocks,
+        hipLaunchKernelGGL(bool_should_gather_kernel, dim3(b.slot_grid()), dim3(tb), 0, b.s, qi->cand.p, b.n_slots, b.d_page_query, qi->d_blocks,
                            qi->target.p, qi->d_rank, qi->probe.p, qi->fprobe.p, weight, qi->slot_kden.p, qi->slot_score.p);
     else
-        hipLaunchKernelGGL(bool_exclude_kernel, dim3(c.slot_grid()), dim3(tb), 0, c.s, qi->cand.p, c.n_slots, qi->d_blocks, qi->target.p,
+        hipLaunchKernelGGL(bool_exclude_kernel, dim3(b.slot_grid()), dim3(tb), 0, b.s, qi->cand.p, b.n_slots, qi->d_blocks, qi->target.p,
                            qi->d_rank, qi->probe.p);
-    hipLaunchKernelGGL(and_release_kernel, dim3(uint32_t((bound + tb - 1) / tb)), dim3(tb), 0, c.s, qi->d_touched, uint32_t(bound), qi->d_needed,
+    hipLaunchKernelGGL(and_release_kernel, dim3(uint32_t((bound + tb - 1) / tb)), dim3(tb), 0, b.s, qi->d_touched, uint32_t(bound), qi->d_needed,
                        d_count);
     return DINT_OK;
 }
+// the slots of an AND call: its candidates
+static bool_slots bool_slots_of(const and_call& c) { return {c.qi, c.freqs_dict, c.n_slots, c.d_page_query, c.n_queries, c.s}; }
 
 // Behind the AND rounds, before anything is scored: the excluded terms' steps, then the matches counted again (the rounds
 // counted the intersection).
@@ -78,7 +81,7 @@ static int bool_exclude_pass(and_call& c) {
     const size_t nq = c.n_queries;
     if (x.n_not == 0) return DINT_OK;
     for (size_t j = 0; j != x.n_not; ++j) {
-        const int st = bool_step(c, x.d_not_first + j * nq, x.d_not_blocks + j * nq, x.not_blocks.data() + j * nq, nullptr, x.d_step_count + j);
+        const int st = bool_step(bool_slots_of(c), x.d_not_first + j * nq, x.d_not_blocks + j * nq, x.not_blocks.data() + j * nq, nullptr, x.d_step_count + j);
         if (st != DINT_OK) return st;
     }
     HIP_TRY(hipMemsetAsync(c.d_counts, 0, nq * sizeof(unsigned long long), c.s));
@@ -92,7 +95,7 @@ static int bool_should_pass(and_call& c) {
     bool_steps& x = *c.extra;
     const size_t nq = c.n_queries;
     for (size_t j = 0; j != x.n_should; ++j) {
-        const int st = bool_step(c, x.d_should_first + j * nq, x.d_should_blocks + j * nq, x.should_blocks.data() + j * nq,
+        const int st = bool_step(bool_slots_of(c), x.d_should_first + j * nq, x.d_should_blocks + j * nq, x.should_blocks.data() + j * nq,
                                  x.d_should_weight + j * nq, x.d_step_count + x.n_not + j);
         if (st != DINT_OK) return st;
     }

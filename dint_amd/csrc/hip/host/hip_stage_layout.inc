@@ -76,6 +76,20 @@ struct or_pass_layout : stage_layout {
         if (ranked) take_each({&term_order, &term_n, &term_weight}, n_terms);
     }
 };
+// What a ranked OR pass with a minimum and exclusions (dint_ranked_or_bool_queries) stages besides, from word `base` on —
+// behind the pass's or_pass_layout, which keeps its words: page -> query of the pass, per term record its query's m, per
+// excluded step and query of the pass {first block, blocks} (n_not_tab = steps * queries each), then a claim counter per
+// step (zeros, copied in with the rest).
+struct or_bool_layout : stage_layout {
+    size_t page_query, term_m, not_first, not_blocks, step_count;
+    or_bool_layout(size_t base, size_t n_pages, size_t n_terms, size_t n_not_tab, size_t n_steps) {
+        words = base;
+        page_query = take(n_pages);
+        term_m = take(n_terms);
+        take_each({&not_first, &not_blocks}, n_not_tab);
+        step_count = take(n_steps);
+    }
+};
 // The pruned ranked call's main stage: per record {first, blocks, page, claimed, q_weight, order, E, query}, per query
 // {from, n, n_E, theta}, per candidate page {page, record}, the other E terms' blocks, then (8-byte aligned) per query
 // {rest, margin} (doubles).

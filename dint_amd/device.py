@@ -36,6 +36,7 @@ ABI_SYMBOLS = (
     "dint_block_table_create", "dint_block_table_destroy", "dint_block_table_learn", "dint_block_table_ready", "dint_block_table_info_get", "dint_decode_block_table",
     "dint_query_index_create", "dint_query_index_destroy", "dint_and_queries", "dint_and_queries_freqs", "dint_or_queries", "dint_or_queries_freqs",
     "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_bool_queries", "dint_ranked_or_queries",
+    "dint_ranked_or_bool_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -131,6 +132,7 @@ def _load():
     lib.dint_ranked_and_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, vp]
     lib.dint_ranked_bool_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_or_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, vp]
+    lib.dint_ranked_or_bool_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
@@ -629,6 +631,35 @@ class QueryIndex:
         summed over the query's terms in ascending term id -> (counts u64[n] = min(k, |union|), scores f32[n, k]
         descending, docids u32[n, k]; equal scores by ascending docID, 0.0 / 0xFFFFFFFF past a query's count)."""
         return self._ranked("dint_ranked_or_queries", freqs_dict, wand, queries, k)
+
+    def ranked_or_bool_queries(self, freqs_dict: "Dictionary", wand: "WandData", should, exclude=None, min_should_match=None,
+                               k: int = 10):
+        """Union-driven ranked boolean queries (dint_ranked_or_bool_queries): per query the documents
+        held by at least m = max(1, min_should_match[q]) of the distinct lists of should[q] and by no list of exclude[q],
+        each with its ranked_or_queries score over should[q] (ascending term id; excluded terms never score). exclude: None,
+        or a sequence per query like should; min_should_match: None (all 1) or an integer per query. m above the query's
+        distinct terms selects nothing -> (counts u64[n] = min(k, matches), matches u64[n], scores f32[n, k] descending,
+        docids u32[n, k] as ranked_or_queries, blocks decoded: every block of the optional terms of the queries that can
+        match, plus the blocks the exclusion steps claimed)."""
+        n = len(should)
+        assert exclude is None or len(exclude) == n
+        s_terms, s_offs = _pack_queries(should)
+        x_terms, x_offs = _pack_queries(exclude) if exclude is not None else (None, None)
+        mins = None
+        if min_should_match is not None:
+            mins = np.ascontiguousarray(min_should_match, dtype=np.uint32)
+            assert mins.shape == (n,)
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        blocks = C.c_uint64()
+        _check(_lib.dint_ranked_or_bool_queries(self._h, freqs_dict._h, wand._h, k, s_terms.ctypes.data, s_offs.ctypes.data,
+                                                ptr(x_terms), ptr(x_offs), ptr(mins), n, counts.ctypes.data, matches.ctypes.data,
+                                                scores.ctypes.data, docids.ctypes.data, C.byref(blocks), self._stream()),
+               "dint_ranked_or_bool_queries")
+        return counts, matches, scores, docids, blocks.value
 
     def ranked_or_maxscore_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10):
         """ranked_or_queries' answer, bit for bit, with MaxScore's pruning: the blocks of low-weight

@@ -459,8 +459,8 @@ int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, c
  * qf (query_freqs, queries.hpp:135-148); the clauses are independent: a term in both `must` and `should` is scored once in
  * each phase, a term in both `must` and `not` matches nothing.
  * The matches of query q: the documents in every list of must[q] and in no list of not[q]. A QUERY WITHOUT A REQUIRED TERM
- * SELECTS NOTHING (count 0, outputs empty): the union-driven query is dint_ranked_or_queries', and exclusions over a union
- * are out of scope. The score of a match d starts at 0.0f; the required terms are added in dint_ranked_and_queries' order
+ * SELECTS NOTHING (count 0, outputs empty): the union-driven query, with exclusions and a minimum number of optional terms,
+ * is dint_ranked_or_bool_queries'. The score of a match d starts at 0.0f; the required terms are added in dint_ranked_and_queries' order
  * (increasing list length, equal lengths by increasing term id), then the optional terms whose list holds d, in ascending
  * term id; every addend is q_weight_t * doc_term_weight(freq_t(d), norm_lens[d]), q_weight_t = query_term_weight(qf_t within
  * its clause, the list's length, wd's num_docs), every operation a binary32 one, uncontracted, as in
@@ -483,6 +483,43 @@ int dint_ranked_bool_queries(dint_query_index* qi, const dint_dict* freqs_dict, 
                              const uint32_t* must_terms, const uint64_t* must_offsets, const uint32_t* should_terms,
                              const uint64_t* should_offsets, const uint32_t* not_terms, const uint64_t* not_offsets, size_t n_queries,
                              uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids, uint64_t* blocks_decoded, void* stream);
+
+/* ---- union-driven ranked boolean queries (optional terms, a minimum of them, excluded terms; BM25 top-k) ----
+ * Replaces: ranked_or_query (include/ds2i/queries.hpp:387-457) with the two filters a free-text query asks for — "some of
+ * these words, at least m of them, and none of those" (Lucene's pure SHOULD with MUST_NOT and minimum_should_match) — for a
+ * batch of queries per call; the excluded terms run over next_geq (include/dint/dict_posting_list.hpp:126-169).
+ * dint_ranked_or_queries excludes nothing and asks for one term; filtering its output needs a k above DINT_RANKED_MAX_K as
+ * soon as an excluded term is frequent; dint_ranked_bool_queries selects nothing without a required term.
+ * Clauses: `should` and `not` are HOST terms / offsets pairs laid out as in dint_ranked_bool_queries (offsets: n_queries + 1
+ * entries); the `not` pair may be null: no exclusions. Repeated terms within `should` are one term with multiplicity qf
+ * (query_freqs, queries.hpp:135-148); repeats in `not` are one term. The clauses are independent: a term in both matches
+ * nothing through that term's list (every document of the list is excluded).
+ * m: min_should_match is a HOST array of n_queries (null: all 1); m_q = max(1, min_should_match[q]) counts the DISTINCT
+ * optional terms whose list holds the document. m_q above the query's number of distinct optional terms selects nothing.
+ * The matches of query q: the documents held by at least m_q of the distinct should[q] lists and by no not[q] list.
+ * The score of a match is exactly dint_ranked_or_queries' score over should[q]: from 0.0f, the terms whose list holds the
+ * document in ascending term id, q_weight_t * doc_term_weight(freq_t(d), norm_lens[d]) each (bm25_add), every operation a
+ * binary32 one, uncontracted. Excluded terms never score. With no exclusions and every m_q <= 1 the call returns
+ * dint_ranked_or_queries' counts, scores and docIDs bit for bit. With m_q equal to the number of distinct terms the
+ * documents are the intersection's, but the sums keep dint_ranked_or_queries' order (ascending term id), not
+ * dint_ranked_and_queries' (increasing list length): the scores of the two calls may differ in the last place.
+ * matches[q] (HOST, nullable) = the number of matches; counts[q] = min(k, matches); scores, docids (nullable), their order
+ * (descending score, equal scores by ascending docID) and their filler (0.0f / 0xFFFFFFFF) are the other ranked calls'.
+ * *blocks_decoded (nullable) = an eager and a lazy part. Eager, dint_ranked_or_queries' unit: every block of every distinct
+ * optional term of every query that can match (a query with no block in its lists, or with m_q above its distinct terms,
+ * decodes nothing and returns zeros). Lazy, the claims of the exclusion steps: per excluded term, in ascending term id, the
+ * blocks whose docs part was decoded because a candidate that survived the m-filter and the earlier exclusions falls in
+ * them; a candidate past a list's last docID claims nothing. The value is exact for a call of one query; in a batch a block
+ * that several queries claim in the same step counts once, so the batch's value is at most the sum of the one-query values.
+ * DINT_ERR_ARG, before anything is launched (no output is written): everything dint_ranked_or_queries refuses (k == 0 or
+ * k > DINT_RANKED_MAX_K, a freqs_dict of another kind or device, a wand handle on another device or one whose num_docs does
+ * not exceed the index's largest docID, null counts or scores), decreasing offsets, and a term >= n_lists in either clause.
+ * The handle's lock, the stream and the passes (DINT_OPT_QUERY_OR_PASS_PAGES: whole queries, sized by their optional
+ * terms' blocks) are dint_ranked_or_queries'; there is no option of its own. */
+int dint_ranked_or_bool_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                const uint32_t* should_terms, const uint64_t* should_offsets, const uint32_t* not_terms,
+                                const uint64_t* not_offsets, const uint32_t* min_should_match, size_t n_queries, uint64_t* counts,
+                                uint64_t* matches, float* scores, uint32_t* docids, uint64_t* blocks_decoded, void* stream);
 
 /* ---- ranked disjunctive queries (BM25 top-k of the union) over the same query index --------------
  * Replaces: ranked_or_query (include/ds2i/queries.hpp:387-457) for a batch of queries per call. (Not a query type of

@@ -2,8 +2,8 @@
 //
 //   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
-//   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool, several
-//               separated by ':'
+//   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
+//               ranked_or_bool, several separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
@@ -16,6 +16,10 @@
 //               excluded term, the optional terms counted where they occur) reads its query lines as
 //               tokens — +t required, -t excluded, a bare t optional — and so must be the only type of its run; also only
 //               with a wand file;
+//               ranked_or_bool (dint_ranked_or_bool_queries, BM25 top 10 of the documents that hold at least m of the optional
+//               and no excluded term) reads its lines as tokens too — a bare t optional, -t excluded,
+//               ~m the line's minimum (at most one; without it 1) — refuses +t, and must be the only type of its run as
+//               well; also only with a wand file;
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -74,10 +78,14 @@ int main(int argc, char** argv) {
         const bool is_bool = query_type == "ranked_bool";
         if (!is_bool && (":" + query_type + ":").find(":ranked_bool:") != std::string::npos)
             throw std::runtime_error("ranked_bool reads its query lines as +t / -t / t tokens: it must be the only query type of a run");
+        const bool is_or_bool = query_type == "ranked_or_bool";
+        if (!is_or_bool && (":" + query_type + ":").find(":ranked_or_bool:") != std::string::npos)
+            throw std::runtime_error("ranked_or_bool reads its query lines as t / -t / ~m tokens: it must be the only query type of a run");
         // read_query (queries.hpp:15-27)
         std::vector<std::vector<uint32_t>> queries;
         // ranked_bool: `queries` holds the required terms; the optional and excluded ones packed, offsets per query
-        std::vector<uint32_t> should_terms, not_terms;
+        // ranked_or_bool: `queries` holds the optional terms; the excluded ones packed, and every line's minimum
+        std::vector<uint32_t> should_terms, not_terms, mins;
         std::vector<uint64_t> should_offs(1, 0), not_offs(1, 0);
         for (std::string line; std::getline(std::cin, line);) {
             std::istringstream iline(line);
@@ -93,6 +101,21 @@ int main(int argc, char** argv) {
                     (sign == '+' ? q : sign == '-' ? not_terms : should_terms).push_back(t);
                 }
                 should_offs.push_back(should_terms.size());
+                not_offs.push_back(not_terms.size());
+            } else if (is_or_bool) {
+                bool has_min = false;
+                for (std::string tok; iline >> tok;) {
+                    const char sign = tok[0];
+                    if (sign == '+') throw std::runtime_error("ranked_or_bool: no required terms (+t): that query is ranked_bool's: " + tok);
+                    const std::string digits = sign == '-' || sign == '~' ? tok.substr(1) : tok;
+                    if (digits.empty() || digits.find_first_not_of("0123456789") != std::string::npos || digits.size() > 10 ||
+                        std::stoull(digits) > 0xFFFFFFFFull || (sign == '~' && has_min))
+                        throw std::runtime_error("ranked_or_bool: not a term token: " + tok);
+                    const uint32_t t = uint32_t(std::stoull(digits));
+                    if (sign == '~') has_min = true, mins.push_back(t);
+                    else (sign == '-' ? not_terms : q).push_back(t);
+                }
+                if (!has_min) mins.push_back(1);
                 not_offs.push_back(not_terms.size());
             } else {
                 for (uint32_t t; iline >> t;) q.push_back(t);
@@ -163,7 +186,8 @@ int main(int argc, char** argv) {
             const bool is_maxscore = (t == "ranked_or_maxscore" && wand) || is_blockmax;
             const bool is_ranked_or = t == "ranked_or" && wand;
             const bool is_ranked_bool = t == "ranked_bool" && wand;
-            const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore || is_ranked_bool;
+            const bool is_ranked_or_bool = t == "ranked_or_bool" && wand;
+            const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
                 std::cerr << "Unsupported query type: " << t << std::endl;  // src/queries.cpp:108-110
                 continue;
@@ -179,6 +203,11 @@ int main(int argc, char** argv) {
                                                      not_terms.data(), not_offs.data() + q0, n, q_counts, nullptr, top_scores.data(), nullptr,
                                                      nullptr, nullptr),
                             "dint_ranked_bool_queries");
+                } else if (is_ranked_or_bool) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    dint_ok(dint_ranked_or_bool_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, not_terms.data(), not_offs.data() + q0,
+                                                        mins.data() + q0, n, q_counts, nullptr, top_scores.data(), nullptr, nullptr, nullptr),
+                            "dint_ranked_or_bool_queries");
                 } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
