@@ -3,7 +3,8 @@
 // host/ by subsystem and are included here in order — common helpers, handles and the query calls' staged layouts first,
 // then the extern "C" block (opened in host/hip_api_common.inc, closed at the end of this file): dictionary, vroom
 // decode, in-index decode, the query index and its page decodes, query planning, AND, OR, ranked AND, ranked OR and
-// pruned ranked OR queries, scores of given documents, statistics, host-pointer calls, list cache.
+// pruned ranked OR queries, scores of given documents, maxima from the index, the index checked against its collection,
+// statistics, host-pointer calls, list cache.
 #include "dint_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -35,6 +36,7 @@
 #include "dint_ranked_or_maxscore_kernels.hpp"
 #include "dint_score_documents_kernels.hpp"
 #include "dint_wand_kernels.hpp"
+#include "dint_check_kernels.hpp"
 #include "dint_stats_kernels.hpp"
 
 #include "host/hip_common.inc"
@@ -57,6 +59,7 @@
 #include "host/hip_api_ranked_or_maxscore.inc"
 #include "host/hip_api_score_documents.inc"
 #include "host/hip_api_wand.inc"
+#include "host/hip_api_check.inc"
 #include "host/hip_api_stats.inc"
 #include "host/hip_api_host_calls.inc"
 #include "host/hip_api_list_cache.inc"

@@ -9,6 +9,8 @@ void dint_query_index_destroy(dint_query_index* qi) {
                     static_cast<void*>(qi->d_rank), static_cast<void*>(qi->d_touched)})
         if (p) (void)hipFree(p);
     if (qi->h_stage) (void)hipHostFree(qi->h_stage);
+    for (void* p : qi->h_expect)
+        if (p) (void)hipHostFree(p);
     delete qi;
 }
 
@@ -36,6 +38,7 @@ int dint_query_index_create(const dint_dict* docs_dict, const uint8_t* d_index, 
             delete qi;
             return DINT_ERR_FORMAT;
         }
+        if (b != 0 && blocks[b - 1].list == l && blocks[b - 1].n != 256) qi->whole_blocks = false;
         prev_list = l;
         qi->list_first[l + 1] += 1;
         qi->list_len[l] += blocks[b].n;

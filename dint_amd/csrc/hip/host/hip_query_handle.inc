@@ -64,6 +64,13 @@ struct dint_query_index {
     // the pruned ranked OR call (hip_api_ranked_or_maxscore.inc): per claim flag of a pass, the flag and its place in the
     // touched list; the touched blocks; {touched count, per query of the pass its claims}
     device_buffer<uint32_t> ms_flag, ms_rank, ms_touched, ms_count;
+    // dint_check_index (hip_api_check.inc): every block of a list but its last holds 256 postings (the in-index layout:
+    // block j of a list is its positions [256 j, 256 j + n)); two pinned staging buffers of a pass's expected postings
+    // and their device copies, alternating
+    bool whole_blocks = true;
+    void* h_expect[2] = {nullptr, nullptr};
+    size_t h_expect_cap = 0;  // bytes, of each
+    device_buffer<uint32_t> expect[2];
     std::mutex mutex;
 
     uint32_t blocks_of(uint32_t l) const { return list_first[l + 1] - list_first[l]; }

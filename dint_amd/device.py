@@ -7,6 +7,7 @@ without a GPU fails with DINT_ERR_NO_DEVICE.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -38,7 +39,7 @@ ABI_SYMBOLS = (
     "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_bool_queries", "dint_ranked_or_queries",
     "dint_ranked_or_bool_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
-    "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
+    "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_check_index", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
 
 #: dint_block_ref (include/dint_hip.h)
@@ -65,6 +66,23 @@ class StreamStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in (
         "lists", "ints", "payload_bytes", "codewords", "run_codewords", "exceptions16", "exceptions32",
         "hot_codewords", "hot_ints", "wide_blocks", "narrow_blocks")]
+
+
+class CollectionView(C.Structure):  # dint_collection_view
+    _fields_ = [("docs", C.c_void_p), ("freqs", C.c_void_p), ("docs_at", C.c_void_p), ("freqs_at", C.c_void_p),
+                ("list_len", C.c_void_p), ("n_lists", C.c_size_t)]
+
+
+class IndexMismatch(C.Structure):  # dint_index_mismatch
+    _fields_ = [("kind", C.c_uint32), ("list", C.c_uint32), ("position", C.c_uint64), ("expected", C.c_uint64),
+                ("got", C.c_uint64)]
+
+
+#: dint_index_mismatch.kind (DINT_CHECK_*)
+CHECK_OK, CHECK_LENGTH, CHECK_DOCID, CHECK_FREQ = 0, 1, 2, 3
+
+#: what QueryIndex.check reports as the first mismatch
+Mismatch = collections.namedtuple("Mismatch", "kind list position expected got")
 
 
 def _load():
@@ -138,6 +156,7 @@ def _load():
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_index_max_weights.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.dint_wand_data_set_block_max_weights.argtypes = [vp, vp, sz]
+    lib.dint_check_index.argtypes = [vp, vp, C.POINTER(CollectionView), C.POINTER(u64), C.POINTER(IndexMismatch), vp]
     lib.dint_count_ngrams.argtypes = [C.c_int, C.c_int, vp, u64, vp, u64, C.c_uint32, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_float)]
     lib.dint_select_ngrams.argtypes = [C.c_int, vp, u64, u64, vp, sz, C.c_uint32, C.POINTER(sz)]
     lib.dint_debug_wave_scan.argtypes = [vp, vp]
@@ -711,6 +730,26 @@ class QueryIndex:
         _check(_lib.dint_index_max_weights(self._h, freqs_dict._h, wand._h, mtw.ctypes.data if mtw.size else None,
                                            bmw.ctypes.data if with_blocks else None, self._stream()), "dint_index_max_weights")
         return (mtw, bmw) if with_blocks else mtw
+
+    def check(self, freqs_dict, docs, freqs, docs_at, freqs_at, list_len):
+        """The index checked against its collection on the device (dint_check_index; the reference's
+        verify_collection): list i of the collection is docs[docs_at[i] : docs_at[i] + list_len[i]] (u32; offsets and
+        lengths u64) and freqs[freqs_at[i] : ...]; freqs_dict, freqs and freqs_at None: docIDs only. Returns
+        (n_mismatches, first): wrong lengths + wrong postings, and None or the Mismatch (kind, list, position, expected,
+        got) the reference's walk would have stopped at."""
+        def arr(a, dtype):
+            return None if a is None else np.ascontiguousarray(a, dtype=dtype)
+
+        docs, freqs = arr(docs, np.uint32), arr(freqs, np.uint32)
+        docs_at, freqs_at, list_len = arr(docs_at, np.uint64), arr(freqs_at, np.uint64), arr(list_len, np.uint64)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        view = CollectionView(ptr(docs), ptr(freqs), ptr(docs_at), ptr(freqs_at), ptr(list_len), 0 if list_len is None else list_len.size)
+        n, first = C.c_uint64(), IndexMismatch()
+        _check(_lib.dint_check_index(self._h, freqs_dict._h if freqs_dict is not None else None, C.byref(view), C.byref(n),
+                                     C.byref(first), self._stream()), "dint_check_index")
+        if first.kind == CHECK_OK:
+            return n.value, None
+        return n.value, Mismatch(first.kind, first.list, first.position, first.expected, first.got)
 
 
 class WandData:

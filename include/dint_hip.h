@@ -604,6 +604,57 @@ int dint_index_max_weights(dint_query_index* qi, const dint_dict* freqs_dict, co
  * be missing, never wrong (every returned pair is a document of the union with its exact score, in order). */
 int dint_wand_data_set_block_max_weights(dint_wand_data* wd, const float* block_max_weight, size_t n_blocks);
 
+/* ---- an index checked against its collection, on the device ------------------------------------------------------
+ * Replaces: verify_collection (include/ds2i/verify_collection.hpp:7-52), the walk behind `create_freq_index --check` and
+ * the check_index tool (src/check_index.cpp): every list of the collection beside the index's enumerator, stopping at the
+ * first wrong length, docID or freq. Here the whole index is compared and the mismatches are counted; the one the
+ * reference would have stopped at is reported.
+ * view (HOST): the collection as its files hold it, nothing copied: list i is docs[docs_at[i] .. + list_len[i]) and, with
+ * freqs, freqs[freqs_at[i] .. + list_len[i]).
+ * Lengths are compared on the host (:18-24): list i's length in the query index against view->list_len[i]. A list of wrong
+ * length counts as ONE mismatch and none of its postings is compared. Of every other list each posting is compared with
+ * the decoded docID (:30-37) and, when view->freqs and freqs_dict are given, with the decoded freq() (:39-46); pass both or
+ * neither. A posting whose docID or freq (or both) differs counts once. *n_mismatches = wrong lengths + wrong postings.
+ * *first (nullable) = the mismatch the reference would have stopped at: the lowest list; within it LENGTH before any
+ * posting, otherwise the lowest position; at that position DOCID before FREQ. `expected` is the collection's value (LENGTH:
+ * its length), `got` the index's; position is 0 for LENGTH. No mismatch: kind DINT_CHECK_OK, every other field 0.
+ * Both outputs are a function of (index, view) alone: a sum and a minimum over the postings, independent of the pass size,
+ * the order of the passes and the timing of the atomics that form them. `got` is read from that one block decoded again.
+ * DINT_OK whether or not there are mismatches: a mismatch is a result, not an error.
+ * Every block is decoded once, in dint_index_max_weights' passes (consecutive blocks, at most DINT_OPT_QUERY_OR_PASS_PAGES
+ * pages and at most 16384), under the handle's lock; the collection's postings of a pass are staged through two pinned
+ * buffers of the handle (32.25 MiB each at most) by a copy stream of the call's own, beside the pass before it. The call
+ * returns after synchronising `stream`.
+ * DINT_ERR_ARG, before anything is launched: a null qi, view or n_mismatches; view->n_lists different from the index's list
+ * count; null docs / docs_at / list_len (freqs_at with freqs) when n_lists != 0; freqs without freqs_dict or freqs_dict
+ * without freqs; a freqs_dict of another kind or device than the docs dictionary; a query index created from a block table
+ * in which a block that is not its list's last holds fewer than 256 postings (not the in-index layout: block j of a list
+ * would not be its positions [256 j, 256 j + n)). An index of zero blocks returns DINT_OK with the length comparisons only. */
+#define DINT_CHECK_OK 0
+#define DINT_CHECK_LENGTH 1 /* verify_collection.hpp:18-24 */
+#define DINT_CHECK_DOCID 2  /* :30-37 */
+#define DINT_CHECK_FREQ 3   /* :39-46 */
+
+typedef struct dint_collection_view {
+    const uint32_t* docs;     /* words of the .docs file (or any array)                */
+    const uint32_t* freqs;    /* words of the .freqs file; null: docIDs only           */
+    const uint64_t* docs_at;  /* [n_lists] word offset in docs of list i's first docID */
+    const uint64_t* freqs_at; /* [n_lists] word offset in freqs of list i's first freq */
+    const uint64_t* list_len; /* [n_lists] postings of list i                          */
+    size_t n_lists;
+} dint_collection_view;
+
+typedef struct dint_index_mismatch {
+    uint32_t kind;     /* DINT_CHECK_* */
+    uint32_t list;
+    uint64_t position; /* within the list; 0 for LENGTH */
+    uint64_t expected; /* the collection's value (LENGTH: its length) */
+    uint64_t got;      /* the index's */
+} dint_index_mismatch;
+
+int dint_check_index(dint_query_index* qi, const dint_dict* freqs_dict, const dint_collection_view* view, uint64_t* n_mismatches,
+                     dint_index_mismatch* first, void* stream);
+
 /* ---- BM25 scores and term frequencies of caller-given documents over the same query index -----------
  * Replaces: the cursor primitive under every query, document_enumerator::next_geq(d) then freq()
  * (include/dint/dict_posting_list.hpp:126-169), with ranked_or_query's sums (include/ds2i/queries.hpp:387-457), for a batch

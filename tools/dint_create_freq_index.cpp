@@ -11,7 +11,8 @@
 // container (dint/index_file.hpp — the reference's succinct::mapper::freeze format is not reproducible here).
 // One stats line on stdout with the reference's keys where they apply (type, worker_threads, construction_time) plus sizes.
 // The reference's `--check` re-decodes the index on the CPU (verify_collection.hpp); this repo has no CPU decoder in the
-// product — check an index on the device: tests/test_gpu_index.py, dint_decode_posting_blocks.
+// product and this tool stays a host-only program — check the written index on the device with dint_check_index
+// (tools/dint_check_index.cpp): `dint_check_index <index_type> <output_filename> <collection_basename>`.
 #include <chrono>
 #include <cstdlib>
 #include <iostream>
@@ -53,7 +54,7 @@ int main(int argc, char** argv) {
             std::string a = argv[i];
             if (a == "--greedy") greedy = 1;
             else if (a == "--threads" && i + 1 < argc) threads = std::max(1, std::atoi(argv[++i]));
-            else if (a == "--check") std::cerr << "--check: not available on the CPU (see the header of this tool)" << std::endl;
+            else if (a == "--check") std::cerr << "--check: not available on the CPU; run dint_check_index <index_type> <output_filename> <collection_basename>" << std::endl;
             else if (!output_filename && a.rfind("--", 0) != 0) output_filename = argv[i];
             else throw std::runtime_error("unknown parameter");
         }
