@@ -34,6 +34,34 @@ __device__ __forceinline__ uint32_t list_block_of(const uint32_t* block_max, uin
     return lower_bound_u32(block_max + fb, nb, d);
 }
 
+// The blocks of a list that can hold a docID of [lo, hi): the positions [p0, p1) of its nb blocks, whose last docIDs are
+// block_max[0 .. nb) — p0 the first block that ends at or past lo, p1 one past the first block that ends at or past
+// hi - 1 (a block past that one begins past hi - 1). lo >= hi, or a list that ends before lo: no block (p0 == p1). Every
+// posting d of the list with lo <= d < hi lies in a block of [p0, p1); only blocks p0 and p1 - 1 may also hold postings
+// outside the range.
+// constexpr, and so callable from the host's planning as from a kernel: the ranged calls plan their pages on the host, over
+// the handle's own copy of the maxima (lower_bound_u32 above is the kernels' alone).
+struct block_span {
+    uint32_t p0, p1;
+    constexpr uint32_t size() const { return p1 - p0; }
+};
+constexpr uint32_t first_block_reaching(const uint32_t* block_max, uint32_t nb, uint32_t d) {
+    uint32_t at = 0, len = nb;
+    while (len) {
+        const uint32_t half = len >> 1;
+        const bool right = block_max[at + half] < d;
+        at = right ? at + half + 1 : at;
+        len = right ? len - half - 1 : half;
+    }
+    return at;
+}
+constexpr block_span list_blocks_in_range(const uint32_t* block_max, uint32_t nb, uint32_t lo, uint32_t hi) {
+    if (lo >= hi) return {0, 0};
+    const uint32_t p0 = first_block_reaching(block_max, nb, lo);
+    const uint32_t last = first_block_reaching(block_max, nb, hi - 1);
+    return {p0, last < nb ? last + 1 : nb};
+}
+
 // Is d in the list, and where? The list's blocks lie decoded in pages of `docs`, block position pos in page
 // page_of(pos) (asked only for a block d can be in). -> the page's first slot in docs and d's position in the page (its
 // freq is at the same slot of the freqs pages), or hit == kAbsent. blocks[b].n: the docIDs of block b of the index.

@@ -10,6 +10,9 @@
 // xb (dint_ranked_or_bool_queries, hip_api_ranked_or_bool.inc), with rk: the scoring launch is ranked_or_bool_score_kernel,
 // which also drops the documents in fewer than m lists; the excluded terms' steps (bool_step) and and_count_kernel run
 // between it and ranked_topk, and the counters come back with the last pass. Without xb nothing is launched differently.
+// rg (dint_ranked_or_range_queries, hip_api_ranked_range.inc), with rk: the pages are the blocks in every query's docID range
+// only, the scoring launch is ranked_or_range_score_kernel, which counts the matches into the call's counters, and those
+// come back with the last pass. Without rg nothing is planned or launched differently.
 
 // What a ranked OR call with a minimum and exclusions adds to its passes, and what it gets back.
 struct or_bool_args {
@@ -34,15 +37,15 @@ struct or_passes {
 };
 static int plan_or_passes(const dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries,
                           bool with_qf, bool with_freqs, uint64_t* counts, uint64_t* freq_sums, or_passes& op,
-                          const uint32_t* min_match = nullptr) {
+                          const uint32_t* min_match = nullptr, const range_args* rg = nullptr) {
     query_plan& plan = op.plan;
     const int planned = plan_queries(qi, terms, query_offsets, n_queries, true, with_qf, with_freqs, counts, freq_sums, plan);
     if (planned != DINT_OK) return planned;
     op.pages.assign(n_queries, 0);
     op.all = 0;
     for (size_t q = 0; q != n_queries; ++q) {
-        for (uint32_t j = 0; j != plan.len[q]; ++j) op.pages[q] += qi->blocks_of(plan.of(q)[j]);
-        if (op.pages[q] == 0) plan.len[q] = 0;  // (lists without a block)
+        for (uint32_t j = 0; j != plan.len[q]; ++j) op.pages[q] += blocks_in_range(qi, plan.of(q)[j], rg ? &rg->ranges[q] : nullptr).size();
+        if (op.pages[q] == 0) plan.len[q] = 0;  // (lists without a block, or without one in the query's range)
         if (min_match && min_match[q] > plan.len[q]) plan.len[q] = 0, op.pages[q] = 0;  // (more lists asked for than the query has)
         op.all += op.pages[q];
     }
@@ -55,6 +58,7 @@ static int plan_or_passes(const dint_query_index* qi, const uint32_t* terms, con
 struct or_pass_query {
     uint32_t id, n;
     const uint32_t *terms, *qf;
+    const dint_doc_range* range = nullptr;  // (a ranged call: the query's; else none)
 };
 // The pass of `qs` on the stream: the inputs (or_pass_layout) staged — in an area
 // of at least min_stage bytes — and copied in, the pages' decode, and or_count_kernel, which adds to d_counts and the
@@ -63,13 +67,15 @@ struct or_pass_query {
 // behind the pass's own; between the scoring and the selection, per excluded term of the pass's queries in ascending term
 // id a step over the pass's slots (bool_step: search, claim, the docs parts decoded into qi->probe — the scoring has read
 // the pass's pages by then —, the candidates found killed, release), then and_count_kernel into d_counts from id0 on.
+// ranged (with rk and d_counts; every query of qs has its range): a term record's blocks are its list's blocks in range,
+// or_range_layout staged behind the pass's own, and ranked_or_range_score_kernel scores, adding the matches to d_counts.
 static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const ranked_args* rk, const std::vector<or_pass_query>& qs,
                        size_t min_stage, unsigned long long* d_counts, size_t n_counts, uint32_t id0, size_t n_ids, hipStream_t s,
-                       or_bool_args* xb = nullptr) {
+                       or_bool_args* xb = nullptr, bool ranged = false) {
     uint64_t n_pages = 0, n_terms = 0;
     for (const or_pass_query& q : qs) {
         n_terms += q.n;
-        for (uint32_t j = 0; j != q.n; ++j) n_pages += qi->blocks_of(q.terms[j]);
+        for (uint32_t j = 0; j != q.n; ++j) n_pages += blocks_in_range(qi, q.terms[j], q.range).size();
     }
     const or_pass_layout L(n_pages, n_terms, rk != nullptr);
     size_t n_steps = 0;  // (xb: the most excluded terms of a query of the pass that has pages)
@@ -77,7 +83,8 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
         for (const or_pass_query& q : qs)
             if (q.n) n_steps = std::max<size_t>(n_steps, xb->not_at[q.id + 1] - xb->not_at[q.id]);
     const or_bool_layout B(L.words, xb ? n_pages : 0, xb ? n_terms : 0, n_steps * n_ids, n_steps);
-    const size_t up_words = B.words;  // (without xb: L.words)
+    const or_range_layout R(B.words, ranged ? n_terms : 0);
+    const size_t up_words = R.words;  // (without xb and not ranged: L.words)
     if (qi->stage(std::max<size_t>(up_words * 4, min_stage)) != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     uint32_t *page_block = qi->h(L.page_block), *page_term = qi->h(L.page_term), *term_order = qi->h(L.term_order);
     std::vector<uint32_t> page_query(rk ? n_pages : 0);  // (ranked_topk's: the pass's queries, from 0)
@@ -87,8 +94,9 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
         if (rk) sort_records_by_term(term_order, from, q.n, q.terms);
         for (uint32_t j = 0; j != q.n; ++j, ++rec) {
             const uint32_t l = q.terms[j];
-            qi->h(L.term_first)[rec] = qi->list_first[l];
-            qi->h(L.term_blocks)[rec] = qi->blocks_of(l);
+            const block_span in = blocks_in_range(qi, l, q.range);  // (no range: every block of the list)
+            qi->h(L.term_first)[rec] = qi->list_first[l] + in.p0;
+            qi->h(L.term_blocks)[rec] = in.size();
             qi->h(L.term_page)[rec] = page;
             qi->h(L.term_query)[rec] = q.id;
             qi->h(L.term_from)[rec] = from;
@@ -97,7 +105,8 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
                 qi->h(L.term_n)[rec] = q.n;
                 qi->h<float>(L.term_weight)[rec] = bm25_query_term_weight(q.qf[j], qi->list_len[l], rk->num_docs);
             }
-            for (uint32_t b = qi->list_first[l]; b != qi->list_first[l + 1]; ++b, ++page) {
+            if (ranged) qi->h(R.term_lo)[rec] = q.range->lo, qi->h(R.term_hi)[rec] = q.range->hi;
+            for (uint32_t b = qi->list_first[l] + in.p0; b != qi->list_first[l] + in.p1; ++b, ++page) {
                 page_block[page] = b;
                 page_term[page] = rec;
                 if (rk) page_query[page] = q.id - id0;
@@ -148,7 +157,14 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
     rp.norm_lens = rk->norm_lens;
     rp.cand = qi->cand.p;
     rp.score = qi->slot_score.p;
-    if (!xb) {
+    if (ranged) {
+        ranked_or_range_pass gp{};
+        gp.base = rp;
+        gp.term_lo = qi->d(R.term_lo);
+        gp.term_hi = qi->d(R.term_hi);
+        gp.matches = d_counts;
+        hipLaunchKernelGGL(ranked_or_range_score_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, gp);
+    } else if (!xb) {
         hipLaunchKernelGGL(ranked_or_score_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, rp);
     } else {
         ranked_or_bool_pass bp{};
@@ -183,19 +199,23 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
 
 static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream,
-                           const ranked_args* rk = nullptr, or_bool_args* xb = nullptr) {
+                           const ranked_args* rk = nullptr, or_bool_args* xb = nullptr, range_args* rg = nullptr) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
     if (n_queries >= 0xFFFFFFFFull) return DINT_ERR_ARG;
     or_passes op;  // (rk: with multiplicities, for the query weights)
     const int planned = plan_or_passes(qi, terms, query_offsets, n_queries, rk != nullptr, freqs_dict != nullptr, counts, freq_sums, op,
-                                       xb ? xb->m : nullptr);
+                                       xb ? xb->m : nullptr, rg);
     if (planned != DINT_OK) return planned;
     const query_plan& plan = op.plan;
     if (xb) {
         xb->eager_blocks = op.all;
         xb->h_matches.assign(n_queries, 0ull);
+    }
+    if (rg) {
+        rg->blocks = op.all;
+        rg->h_matches.assign(n_queries, 0ull);
     }
     if (op.all == 0) return DINT_OK;
 
@@ -220,16 +240,17 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         qs.clear();
         for (size_t q = q0; q != q1; ++q) {
             n_pages += op.pages[q];
-            qs.push_back({uint32_t(q), plan.len[q], plan.of(q), rk ? plan.qf_of(q) : nullptr});
+            qs.push_back({uint32_t(q), plan.len[q], plan.of(q), rk ? plan.qf_of(q) : nullptr, rg ? &rg->ranges[q] : nullptr});
         }
         if (n_pages == 0) continue;
         if (k != 0) HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area)
         ranked_args pass_rk = rk ? *rk : ranked_args{};
         if (rk) pass_rk.keys += uint64_t(q0) * rk->k;  // (the keys of the pass's queries at their own offset)
         const int st = or_run_pass(qi, freqs_dict, rk ? &pass_rk : nullptr, qs, 2 * n_queries * sizeof(unsigned long long), d_counts,
-                                   n_queries, uint32_t(q0), q1 - q0, s, xb);
+                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr);
         if (st != DINT_OK) return st;
     }
+    if (rg) HIP_TRY(hipMemcpyAsync(rg->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (xb) HIP_TRY(hipMemcpyAsync(xb->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area: the results go there)
     if (xb && xb->claimed) qi->claims_dirty = false;  // (this call set it, and every step's claims are released)

@@ -28,7 +28,8 @@ int dint_query_index_create(const dint_dict* docs_dict, const uint8_t* d_index, 
     qi->n_blocks = n_blocks;
     qi->list_first.assign(n_lists + 1, 0);
     qi->list_len.assign(n_lists, 0);
-    std::vector<uint32_t> maxs(n_blocks);
+    std::vector<uint32_t>& maxs = qi->block_max;  // (kept: the ranged calls plan their pages on the host)
+    maxs.assign(n_blocks, 0u);
     uint32_t prev_list = 0;
     for (size_t b = 0; b != n_blocks; ++b) {
         const uint32_t l = blocks[b].list;

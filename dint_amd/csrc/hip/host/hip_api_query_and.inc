@@ -17,7 +17,7 @@ struct bool_steps {
 
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split = true,
-                            const ranked_args* rk = nullptr, bool_steps* extra = nullptr);
+                            const ranked_args* rk = nullptr, bool_steps* extra = nullptr, range_args* rg = nullptr);
 
 // One AND call: what its stages share.
 struct and_call {
@@ -25,6 +25,7 @@ struct and_call {
     const dint_dict* freqs_dict = nullptr;  // and_query<true>: the freqs pass runs
     const ranked_args* rk = nullptr;        // ranked_and: the freqs pass scores and selects
     bool_steps* extra = nullptr;            // ranked_bool: excluded steps before the freqs pass, optional steps inside it
+    range_args* rg = nullptr;               // a ranged call: candidates from the rarest list's blocks in range, the others killed
     size_t n_queries = 0;
     uint64_t* counts = nullptr;
     hipStream_t s = nullptr;
@@ -45,6 +46,7 @@ struct and_call {
     std::vector<unsigned long long> h_sums;
     std::vector<uint32_t> h_freq_counts;
     std::vector<float> h_qweights;
+    std::vector<uint32_t> h_ranges;  // a ranged call: per query {lo, hi}, on their way in (the call waits before it returns)
 
     uint32_t* ctrl_of_round(size_t r) const { return d_ctrl + (r + 1) * kCtrlWords; }  // (d_ctrl itself: the candidates' decode)
     uint32_t slot_grid() const { return uint32_t(n_pages); }                           // 256 slots per page = one workgroup
@@ -81,7 +83,7 @@ struct bool_slots {
 static int bool_step(const bool_slots& b, const uint32_t* first, const uint32_t* nblk, const uint32_t* h_nblk, const float* weight,
                      uint32_t* d_cnt);
 
-// the candidates: the rarest list of every query, a page per block
+// the candidates: the rarest list of every query, a page per block (a ranged call: per block in the query's range)
 static void and_candidate_pages(and_call& c) {
     c.page_block.reserve(c.n_queries + 64);
     c.page_query.reserve(c.n_queries + 64);
@@ -89,7 +91,8 @@ static void and_candidate_pages(and_call& c) {
         if (c.plan.len[q] == 0) continue;
         c.rounds = std::max<size_t>(c.rounds, c.plan.len[q] - 1);
         const uint32_t rarest = c.plan.of(q)[0];
-        for (uint32_t b = c.qi->list_first[rarest]; b != c.qi->list_first[rarest + 1]; ++b) {
+        const block_span in = blocks_in_range(c.qi, rarest, c.rg ? &c.rg->ranges[q] : nullptr);
+        for (uint32_t b = c.qi->list_first[rarest] + in.p0; b != c.qi->list_first[rarest] + in.p1; ++b) {
             c.page_block.push_back(b);
             c.page_query.push_back(uint32_t(q));
         }
@@ -378,15 +381,27 @@ static int and_fused_form(and_call& c) {
 }
 
 // ---- the other forms' beginning: the copy in; the candidates decoded, the first round's search riding along where the
-// one-launch decode runs (*searched) ----
+// one-launch decode runs (*searched). A ranged call: no search rides along — range_kill_kernel retires the candidates
+// outside their query's range behind the decode, and the first round's search is and_batch_rounds' own launch, so a
+// boundary candidate claims nothing ----
 static int and_candidates(and_call& c, bool* searched) {
     const int sent = and_send_inputs(c, true);
     if (sent != DINT_OK) return sent;
     const query_pages search0 = and_first_search(c);
     const int st = decode_pages_counted(c.qi, c.d_page_block, nullptr, c.n_pages, c.qi->cand.p, c.d_ctrl, 1u, c.s,
-                                        c.rounds && c.round_bound[0] ? &search0 : nullptr, searched);
+                                        !c.rg && c.rounds && c.round_bound[0] ? &search0 : nullptr, searched);
     if (st != DINT_OK) return c.failed(st);
     c.qi->claims_dirty = true;  // until the call has run to its end
+    if (c.rg) {
+        c.h_ranges.resize(2 * c.n_queries);
+        for (size_t q = 0; q != c.n_queries; ++q) c.h_ranges[2 * q] = c.rg->ranges[q].lo, c.h_ranges[2 * q + 1] = c.rg->ranges[q].hi;
+        if (!c.qi->q_ranges.ensure(c.h_ranges.size())) return c.failed(DINT_ERR_HIP);
+        if (hipMemcpyAsync(c.qi->q_ranges.p, c.h_ranges.data(), c.h_ranges.size() * 4, hipMemcpyHostToDevice, c.s) != hipSuccess)
+            return c.failed(DINT_ERR_HIP);
+        hipLaunchKernelGGL(range_kill_kernel, dim3(c.slot_grid()), dim3(kPageSlots), 0, c.s, c.qi->cand.p, c.n_slots, c.d_page_query,
+                           c.qi->q_ranges.p);
+        if (hipGetLastError() != hipSuccess) return c.failed(DINT_ERR_HIP);
+    }
     return DINT_OK;
 }
 
@@ -571,7 +586,7 @@ static int and_copy_back(and_call& c, uint64_t* freq_sums, uint64_t* freq_blocks
 // tails or batch rounds — then, with a freqs dictionary, the freqs / ranked pass, and the copy back.
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split,
-                            const ranked_args* rk, bool_steps* extra) {
+                            const ranked_args* rk, bool_steps* extra, range_args* rg) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -581,12 +596,14 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     c.freqs_dict = freqs_dict;
     c.rk = rk;
     c.extra = extra;
+    c.rg = rg;
     c.n_queries = n_queries;
     c.counts = counts;
     c.s = static_cast<hipStream_t>(stream);
     const int planned = plan_queries(qi, terms, query_offsets, n_queries, false, rk != nullptr, freqs_dict != nullptr, counts, freq_sums, c.plan);
     if (planned != DINT_OK) return planned;
     and_candidate_pages(c);
+    if (rg) rg->blocks = c.n_pages;
     if (c.n_pages == 0) return DINT_OK;
     bool mixed = false;
     const int split = may_split ? and_mixed_split(c, stream, &mixed) : DINT_OK;
@@ -603,7 +620,8 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     }
     int st = and_stage_general(c);
     if (st != DINT_OK) return st;
-    const bool fused_form = c.small_rounds && c.n_pages <= tail_pages() && c.n_pages <= fused_pages();
+    // (a ranged call never takes the one-launch form: its candidates die between their decode and the first search)
+    const bool fused_form = !rg && c.small_rounds && c.n_pages <= tail_pages() && c.n_pages <= fused_pages();
     // the last probe hands the results over itself (a few pages: every workgroup of it passes through one counter)
     c.results_to_host = !freqs_dict && qi->d_stage != nullptr && c.n_pages <= 4096;
     unsigned long long* const host_counts = c.results_to_host ? static_cast<unsigned long long*>(qi->d_stage) : nullptr;

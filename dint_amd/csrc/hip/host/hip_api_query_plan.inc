@@ -75,6 +75,21 @@ static float bm25_query_term_weight(uint32_t qf, uint64_t df, uint64_t num_docs)
 static int ranked_topk(dint_query_index* qi, const ranked_args& rk, const std::vector<uint32_t>& page_query, size_t n_queries,
                        hipStream_t s);
 
+// A ranged call (hip_api_ranked_range.inc): every query's docID range, and what the call reports besides its answer. Where
+// a call takes a null one there is no range: nothing is planned or launched differently.
+struct range_args {
+    const dint_doc_range* ranges = nullptr;     // per query of the call: [lo, hi)
+    uint64_t blocks = 0;                        // out: the pages the call planned (OR: every term's blocks in range; AND: the rarest's)
+    std::vector<unsigned long long> h_matches;  // out (OR): per query the union's documents in range
+};
+// The blocks of list l that can hold a docID of *r, as positions in the list (list_blocks_in_range over the handle's own
+// copy of the block maxima); r null: every block.
+static block_span blocks_in_range(const dint_query_index* qi, uint32_t l, const dint_doc_range* r) {
+    const uint32_t nb = qi->blocks_of(l);
+    if (!r) return {0, nb};
+    return list_blocks_in_range(qi->block_max.data() + qi->list_first[l], nb, r->lo, r->hi);
+}
+
 // the *_queries_freqs entries: a freqs dictionary of the index's device and kind, and somewhere for the sums
 static bool freqs_args_ok(const dint_query_index* qi, const dint_dict* freqs_dict, const uint64_t* freq_sums) {
     return freqs_dict && freq_sums && (!qi || (freqs_dict->device == qi->docs->device && freqs_dict->kind == qi->docs->kind));

@@ -33,6 +33,7 @@ struct dint_query_index {
     std::vector<uint32_t> list_len;    // postings per list
     dint_block_ref* d_blocks = nullptr;
     uint32_t* d_block_max = nullptr;
+    std::vector<uint32_t> block_max;  // the host's copy of d_block_max: the ranged calls find their blocks in range here
     uint32_t* d_needed = nullptr;   // n_blocks, zero between rounds
     uint32_t* d_rank = nullptr;     // n_blocks
     uint32_t* d_touched = nullptr;  // n_blocks
@@ -64,6 +65,8 @@ struct dint_query_index {
     // the pruned ranked OR call (hip_api_ranked_or_maxscore.inc): per claim flag of a pass, the flag and its place in the
     // touched list; the touched blocks; {touched count, per query of the pass its claims}
     device_buffer<uint32_t> ms_flag, ms_rank, ms_touched, ms_count;
+    // the ranged ranked AND call (hip_api_ranked_range.inc): per query {lo, hi}
+    device_buffer<uint32_t> q_ranges;
     // dint_check_index (hip_api_check.inc): every block of a list but its last holds 256 postings (the in-index layout:
     // block j of a list is its positions [256 j, 256 j + n)); two pinned staging buffers of a pass's expected postings
     // and their device copies, alternating

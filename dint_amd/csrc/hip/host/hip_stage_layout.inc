@@ -90,6 +90,15 @@ struct or_bool_layout : stage_layout {
         step_count = take(n_steps);
     }
 };
+// What a ranged ranked OR pass (dint_ranked_or_range_queries) stages besides, from word `base` on — behind the pass's
+// or_pass_layout, which keeps its words: per term record its query's range {lo, hi}.
+struct or_range_layout : stage_layout {
+    size_t term_lo, term_hi;
+    or_range_layout(size_t base, size_t n_terms) {
+        words = base;
+        take_each({&term_lo, &term_hi}, n_terms);
+    }
+};
 // The pruned ranked call's main stage: per record {first, blocks, page, claimed, q_weight, order, E, query}, per query
 // {from, n, n_E, theta}, per candidate page {page, record}, the other E terms' blocks, then (8-byte aligned) per query
 // {rest, margin} (doubles).

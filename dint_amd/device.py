@@ -37,7 +37,7 @@ ABI_SYMBOLS = (
     "dint_block_table_create", "dint_block_table_destroy", "dint_block_table_learn", "dint_block_table_ready", "dint_block_table_info_get", "dint_decode_block_table",
     "dint_query_index_create", "dint_query_index_destroy", "dint_and_queries", "dint_and_queries_freqs", "dint_or_queries", "dint_or_queries_freqs",
     "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_bool_queries", "dint_ranked_or_queries",
-    "dint_ranked_or_bool_queries",
+    "dint_ranked_or_bool_queries", "dint_ranked_or_range_queries", "dint_ranked_and_range_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_check_index", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -151,6 +151,8 @@ def _load():
     lib.dint_ranked_bool_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_or_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, vp]
     lib.dint_ranked_or_bool_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_or_range_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_range_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
@@ -679,6 +681,41 @@ class QueryIndex:
                                                 scores.ctypes.data, docids.ctypes.data, C.byref(blocks), self._stream()),
                "dint_ranked_or_bool_queries")
         return counts, matches, scores, docids, blocks.value
+
+    def _ranked_range(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, ranges, k: int, with_stats: bool):
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        pairs = None
+        if ranges is not None:
+            wide = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)  # (int64 first: a value past u32 is refused, not wrapped)
+            assert wide.shape == (n, 2) and (n == 0 or (wide.min() >= 0 and wide.max() <= 0xFFFFFFFF))
+            pairs = np.ascontiguousarray(wide, dtype=np.uint32)  # dint_doc_range {lo, hi}
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 pairs.ctypes.data if pairs is not None else None, n, counts.ctypes.data, matches.ctypes.data,
+                                 scores.ctypes.data, docids.ctypes.data, C.byref(blocks), self._stream()), fn)
+        return (counts, scores, docids, matches, blocks.value) if with_stats else (counts, scores, docids)
+
+    def ranked_or_range_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, ranges, k: int = 10,
+                                with_stats: bool = False):
+        """ranked_or_queries over the documents of a docID interval per query (dint_ranked_or_range_queries, DESIGN.md
+        4d-range): ranges is an (n, 2) array-like of u32, query q ranking over ranges[q][0] <= docID < ranges[q][1], or None
+        (every query unrestricted). A match scores exactly what ranked_or_queries gives it; only the blocks that can hold a
+        docID of the range are decoded -> (counts u64[n] = min(k, matches), scores f32[n, k], docids u32[n, k] as
+        ranked_or_queries) and, with_stats, (matches u64[n]: the union's documents in range, blocks decoded: every distinct
+        term's blocks in range, summed over the queries)."""
+        return self._ranked_range("dint_ranked_or_range_queries", freqs_dict, wand, queries, ranges, k, with_stats)
+
+    def ranked_and_range_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, ranges, k: int = 10,
+                                 with_stats: bool = False):
+        """ranked_and_queries over the documents of a docID interval per query (dint_ranked_and_range_queries, DESIGN.md
+        4d-range): arguments and outputs as ranked_or_range_queries; matches: the intersection's documents in range, blocks
+        decoded: the candidate pages, i.e. the blocks in range of every query's rarest list."""
+        return self._ranked_range("dint_ranked_and_range_queries", freqs_dict, wand, queries, ranges, k, with_stats)
 
     def ranked_or_maxscore_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10):
         """ranked_or_queries' answer, bit for bit, with MaxScore's pruning: the blocks of low-weight

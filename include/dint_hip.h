@@ -565,6 +565,52 @@ int dint_ranked_or_maxscore_queries(dint_query_index* qi, const dint_dict* freqs
                                     const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries, uint64_t* counts,
                                     float* scores, uint32_t* docids, uint64_t* blocks_read, void* stream);
 
+/* ---- docID-range ranked queries (BM25 top-k of the union / the intersection within a docID interval) ----
+ * Replaces: ranked_or_query / ranked_and_query (include/ds2i/queries.hpp:309-457) with a restriction of every query to a
+ * half-open docID interval — a site or host of a URL-ordered collection, a date range of a time-ordered one, a document
+ * shard of a shared index, a page of a walk through the docID space past DINT_RANKED_MAX_K — for a batch of queries per
+ * call. dint_ranked_or_queries / dint_ranked_and_queries with a large k, filtered by the caller, are capped at
+ * DINT_RANKED_MAX_K and decode every block of every term (OR) or seed from the whole rarest list (AND).
+ * ranges (HOST, n_queries entries; null: every query unrestricted): query q ranks over the docIDs lo <= d < hi.
+ * The matches of query q: the documents of the unranged call's match set (the union of its lists for
+ * dint_ranked_or_range_queries, the intersection for dint_ranked_and_range_queries) with lo_q <= d < hi_q. lo_q >= hi_q
+ * selects nothing and decodes nothing. [0, 0xFFFFFFFF) is unrestricted (docIDs are below 0xFFFFFFFF); with it, or with
+ * null ranges, counts, scores and docids are the unranged call's, bit for bit.
+ * The score of a match is EXACTLY the unranged call's — the same terms in the same order (OR: ascending term id; AND:
+ * increasing list length, equal lengths by increasing term id), the same binary32 operations, and q_weight_t still from the
+ * WHOLE list's length and wd's num_docs: the range filters, it does not re-weight. Merging the answers of ranges that tile
+ * the docID space (by descending score, equal scores by ascending docID) therefore reproduces the unranged answer.
+ * matches[q] (HOST, nullable) = the number of matches in range; counts[q] = min(k, matches[q]); scores, docids (nullable),
+ * their order (descending score, equal scores by ascending docID) and their filler (0.0f / 0xFFFFFFFF) are the other
+ * ranked calls'.
+ * Skipping: of a list only the blocks that can hold a docID of the range are decoded. A block with dint_block_ref fields
+ * base and max is in range iff max >= lo && base < hi; as positions of a list with block maxima M[0 .. nb) these are
+ * [p0, p1), p0 = lower_bound(M, lo), p1 = min(nb, lower_bound(M, hi - 1) + 1). At most two blocks a term (the first and the
+ * last in range) hold documents outside the range; those are dropped on the device before they are scored or probe anything.
+ * *blocks_decoded (nullable), exact for any batch — OR: the sum over the queries and over their distinct terms of the
+ * list's blocks in range (dint_or_queries_freqs' unit: a block in the lists of several queries counts once per query; on
+ * the unrestricted range, every block of every distinct term); AND: the candidate pages, i.e. the blocks in range of each
+ * query's rarest list (shortest, equal lengths by term id), summed over the queries. The blocks the AND rounds and its
+ * scoring claim behind that are the unranged call's lazy ones, for in-range candidates only, and are not counted.
+ * DINT_ERR_ARG, before anything is launched (no output is written): what the unranged calls refuse — k == 0 or
+ * k > DINT_RANKED_MAX_K, a term >= n_lists, decreasing offsets, null counts or scores, a freqs_dict of another kind or
+ * device than the docs dictionary, a wand handle on another device or one whose num_docs does not exceed the index's
+ * largest docID. Any lo / hi pair is legal. Terms, query_offsets, the handle's lock and the stream are as for the unranged
+ * calls. The OR call runs in dint_ranked_or_queries' passes (DINT_OPT_QUERY_OR_PASS_PAGES), sized by the blocks IN RANGE, so a
+ * batch of narrow ranges packs more queries into a pass; the AND call takes the round-per-launch form with the first
+ * round's search as a launch of its own (never the one-launch forms: DESIGN.md 4d-range). */
+typedef struct dint_doc_range {
+    uint32_t lo, hi; /* [lo, hi) */
+} dint_doc_range;
+int dint_ranked_or_range_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                 const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_range* ranges,
+                                 size_t n_queries, uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids,
+                                 uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_range_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                  const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_range* ranges,
+                                  size_t n_queries, uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids,
+                                  uint64_t* blocks_decoded, void* stream);
+
 /* ---- the wand data's BM25 maxima from the index, on the device; block maxima for the pruned call --------------
  * Replaces: the max_term_weight half of wand_data's constructor (include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp),
  * which walks the uncompressed collection posting by posting, by one decode of the INDEX: a caller that has only what this

@@ -3,7 +3,7 @@
 //   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
 //   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
-//               ranked_or_bool, several separated by ':'
+//               ranked_or_bool | ranked_or_range | ranked_and_range, several separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
@@ -20,6 +20,10 @@
 //               and no excluded term) reads its lines as tokens too — a bare t optional, -t excluded,
 //               ~m the line's minimum (at most one; without it 1) — refuses +t, and must be the only type of its run as
 //               well; also only with a wand file;
+//               ranked_or_range / ranked_and_range (dint_ranked_or_range_queries, dint_ranked_and_range_queries: ranked_or /
+//               ranked_and over the documents of a docID interval) read their lines as term ids plus at
+//               most one @lo:hi token — the line's half-open range [lo, hi); without it the line is unrestricted — and so
+//               each must be the only type of its run; also only with a wand file; output and keys are ranked_or's;
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -81,12 +85,17 @@ int main(int argc, char** argv) {
         const bool is_or_bool = query_type == "ranked_or_bool";
         if (!is_or_bool && (":" + query_type + ":").find(":ranked_or_bool:") != std::string::npos)
             throw std::runtime_error("ranked_or_bool reads its query lines as t / -t / ~m tokens: it must be the only query type of a run");
+        const bool is_range = query_type == "ranked_or_range" || query_type == "ranked_and_range";
+        for (const char* ranged : {"ranked_or_range", "ranked_and_range"})
+            if (!is_range && (":" + query_type + ":").find(std::string(":") + ranged + ":") != std::string::npos)
+                throw std::runtime_error(std::string(ranged) + " reads its query lines as term ids and one @lo:hi token: it must be the only query type of a run");
         // read_query (queries.hpp:15-27)
         std::vector<std::vector<uint32_t>> queries;
         // ranked_bool: `queries` holds the required terms; the optional and excluded ones packed, offsets per query
         // ranked_or_bool: `queries` holds the optional terms; the excluded ones packed, and every line's minimum
         std::vector<uint32_t> should_terms, not_terms, mins;
         std::vector<uint64_t> should_offs(1, 0), not_offs(1, 0);
+        std::vector<dint_doc_range> ranges;  // ranked_*_range: every line's range
         for (std::string line; std::getline(std::cin, line);) {
             std::istringstream iline(line);
             std::vector<uint32_t> q;
@@ -117,6 +126,28 @@ int main(int argc, char** argv) {
                 }
                 if (!has_min) mins.push_back(1);
                 not_offs.push_back(not_terms.size());
+            } else if (is_range) {
+                auto number = [&](const std::string& digits, const std::string& tok) {
+                    if (digits.empty() || digits.find_first_not_of("0123456789") != std::string::npos || digits.size() > 10 ||
+                        std::stoull(digits) > 0xFFFFFFFFull)
+                        throw std::runtime_error(query_type + ": not a term id or an @lo:hi range: " + tok);
+                    return uint32_t(std::stoull(digits));
+                };
+                bool has_range = false;
+                dint_doc_range r{0u, 0xFFFFFFFFu};
+                for (std::string tok; iline >> tok;) {
+                    if (tok[0] != '@') {
+                        q.push_back(number(tok, tok));
+                        continue;
+                    }
+                    if (has_range) throw std::runtime_error(query_type + ": more than one @lo:hi range on a line: " + tok);
+                    const size_t colon = tok.find(':');
+                    if (colon == std::string::npos) throw std::runtime_error(query_type + ": not a term id or an @lo:hi range: " + tok);
+                    r.lo = number(tok.substr(1, colon - 1), tok);
+                    r.hi = number(tok.substr(colon + 1), tok);
+                    has_range = true;
+                }
+                ranges.push_back(r);
             } else {
                 for (uint32_t t; iline >> t;) q.push_back(t);
             }
@@ -187,7 +218,9 @@ int main(int argc, char** argv) {
             const bool is_ranked_or = t == "ranked_or" && wand;
             const bool is_ranked_bool = t == "ranked_bool" && wand;
             const bool is_ranked_or_bool = t == "ranked_or_bool" && wand;
-            const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool;
+            const bool is_or_range = t == "ranked_or_range" && wand, is_and_range = t == "ranked_and_range" && wand;
+            const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
+                                   is_or_range || is_and_range;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
                 std::cerr << "Unsupported query type: " << t << std::endl;  // src/queries.cpp:108-110
                 continue;
@@ -208,6 +241,16 @@ int main(int argc, char** argv) {
                     dint_ok(dint_ranked_or_bool_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, not_terms.data(), not_offs.data() + q0,
                                                         mins.data() + q0, n, q_counts, nullptr, top_scores.data(), nullptr, nullptr, nullptr),
                             "dint_ranked_or_bool_queries");
+                } else if (is_or_range || is_and_range) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    if (is_or_range)
+                        dint_ok(dint_ranked_or_range_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, ranges.data() + q0, n, q_counts, nullptr,
+                                                             top_scores.data(), nullptr, nullptr, nullptr),
+                                "dint_ranked_or_range_queries");
+                    else
+                        dint_ok(dint_ranked_and_range_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, ranges.data() + q0, n, q_counts, nullptr,
+                                                              top_scores.data(), nullptr, nullptr, nullptr),
+                                "dint_ranked_and_range_queries");
                 } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
