@@ -13,6 +13,10 @@
 // rg (dint_ranked_or_range_queries, hip_api_ranked_range.inc), with rk: the pages are the blocks in every query's docID range
 // only, the scoring launch is ranked_or_range_score_kernel, which counts the matches into the call's counters, and those
 // come back with the last pass. Without rg nothing is planned or launched differently.
+// fl (dint_ranked_or_filtered_queries, hip_api_doc_filter.inc), with rk and without rg: the pages are every term's LIVE blocks
+// under the call's filter, the term records still describe the whole lists, the scoring launch is
+// ranked_or_filtered_score_kernel, which finds a block's page through the filter's live rank and counts the matches into
+// the call's counters; those come back with the last pass. Without fl nothing is planned or launched differently.
 
 // What a ranked OR call with a minimum and exclusions adds to its passes, and what it gets back.
 struct or_bool_args {
@@ -37,15 +41,15 @@ struct or_passes {
 };
 static int plan_or_passes(const dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries,
                           bool with_qf, bool with_freqs, uint64_t* counts, uint64_t* freq_sums, or_passes& op,
-                          const uint32_t* min_match = nullptr, const range_args* rg = nullptr) {
+                          const uint32_t* min_match = nullptr, const range_args* rg = nullptr, const filter_args* fl = nullptr) {
     query_plan& plan = op.plan;
     const int planned = plan_queries(qi, terms, query_offsets, n_queries, true, with_qf, with_freqs, counts, freq_sums, plan);
     if (planned != DINT_OK) return planned;
     op.pages.assign(n_queries, 0);
     op.all = 0;
     for (size_t q = 0; q != n_queries; ++q) {
-        for (uint32_t j = 0; j != plan.len[q]; ++j) op.pages[q] += blocks_in_range(qi, plan.of(q)[j], rg ? &rg->ranges[q] : nullptr).size();
-        if (op.pages[q] == 0) plan.len[q] = 0;  // (lists without a block, or without one in the query's range)
+        for (uint32_t j = 0; j != plan.len[q]; ++j) op.pages[q] += planned_blocks(qi, plan.of(q)[j], rg ? &rg->ranges[q] : nullptr, fl);
+        if (op.pages[q] == 0) plan.len[q] = 0;  // (lists without a block, or without one in the query's range / live under the filter)
         if (min_match && min_match[q] > plan.len[q]) plan.len[q] = 0, op.pages[q] = 0;  // (more lists asked for than the query has)
         op.all += op.pages[q];
     }
@@ -69,13 +73,15 @@ struct or_pass_query {
 // the pass's pages by then —, the candidates found killed, release), then and_count_kernel into d_counts from id0 on.
 // ranged (with rk and d_counts; every query of qs has its range): a term record's blocks are its list's blocks in range,
 // or_range_layout staged behind the pass's own, and ranked_or_range_score_kernel scores, adding the matches to d_counts.
+// fl (with rk and d_counts, not ranged): a term record's pages are its list's live blocks, the record itself the whole
+// list's; nothing more is staged, and ranked_or_filtered_score_kernel scores, adding the matches to d_counts.
 static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const ranked_args* rk, const std::vector<or_pass_query>& qs,
                        size_t min_stage, unsigned long long* d_counts, size_t n_counts, uint32_t id0, size_t n_ids, hipStream_t s,
-                       or_bool_args* xb = nullptr, bool ranged = false) {
+                       or_bool_args* xb = nullptr, bool ranged = false, const filter_args* fl = nullptr) {
     uint64_t n_pages = 0, n_terms = 0;
     for (const or_pass_query& q : qs) {
         n_terms += q.n;
-        for (uint32_t j = 0; j != q.n; ++j) n_pages += blocks_in_range(qi, q.terms[j], q.range).size();
+        for (uint32_t j = 0; j != q.n; ++j) n_pages += planned_blocks(qi, q.terms[j], q.range, fl);
     }
     const or_pass_layout L(n_pages, n_terms, rk != nullptr);
     size_t n_steps = 0;  // (xb: the most excluded terms of a query of the pass that has pages)
@@ -106,10 +112,12 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
                 qi->h<float>(L.term_weight)[rec] = bm25_query_term_weight(q.qf[j], qi->list_len[l], rk->num_docs);
             }
             if (ranged) qi->h(R.term_lo)[rec] = q.range->lo, qi->h(R.term_hi)[rec] = q.range->hi;
-            for (uint32_t b = qi->list_first[l] + in.p0; b != qi->list_first[l] + in.p1; ++b, ++page) {
+            for (uint32_t b = qi->list_first[l] + in.p0; b != qi->list_first[l] + in.p1; ++b) {
+                if (!block_planned(fl, b)) continue;  // (a filter: the live blocks only)
                 page_block[page] = b;
                 page_term[page] = rec;
                 if (rk) page_query[page] = q.id - id0;
+                ++page;
             }
         }
     }
@@ -157,7 +165,13 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
     rp.norm_lens = rk->norm_lens;
     rp.cand = qi->cand.p;
     rp.score = qi->slot_score.p;
-    if (ranged) {
+    if (fl) {
+        ranked_or_filtered_pass fp{};
+        fp.base = rp;
+        fp.filter = fl->filter->view();
+        fp.matches = d_counts;
+        hipLaunchKernelGGL(ranked_or_filtered_score_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, fp);
+    } else if (ranged) {
         ranked_or_range_pass gp{};
         gp.base = rp;
         gp.term_lo = qi->d(R.term_lo);
@@ -199,14 +213,15 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
 
 static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream,
-                           const ranked_args* rk = nullptr, or_bool_args* xb = nullptr, range_args* rg = nullptr) {
+                           const ranked_args* rk = nullptr, or_bool_args* xb = nullptr, range_args* rg = nullptr,
+                           filter_args* fl = nullptr) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
     if (n_queries >= 0xFFFFFFFFull) return DINT_ERR_ARG;
     or_passes op;  // (rk: with multiplicities, for the query weights)
     const int planned = plan_or_passes(qi, terms, query_offsets, n_queries, rk != nullptr, freqs_dict != nullptr, counts, freq_sums, op,
-                                       xb ? xb->m : nullptr, rg);
+                                       xb ? xb->m : nullptr, rg, fl);
     if (planned != DINT_OK) return planned;
     const query_plan& plan = op.plan;
     if (xb) {
@@ -216,6 +231,10 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     if (rg) {
         rg->blocks = op.all;
         rg->h_matches.assign(n_queries, 0ull);
+    }
+    if (fl) {
+        fl->blocks = op.all;
+        fl->h_matches.assign(n_queries, 0ull);
     }
     if (op.all == 0) return DINT_OK;
 
@@ -247,9 +266,10 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         ranked_args pass_rk = rk ? *rk : ranked_args{};
         if (rk) pass_rk.keys += uint64_t(q0) * rk->k;  // (the keys of the pass's queries at their own offset)
         const int st = or_run_pass(qi, freqs_dict, rk ? &pass_rk : nullptr, qs, 2 * n_queries * sizeof(unsigned long long), d_counts,
-                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr);
+                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl);
         if (st != DINT_OK) return st;
     }
+    if (fl) HIP_TRY(hipMemcpyAsync(fl->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (rg) HIP_TRY(hipMemcpyAsync(rg->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (xb) HIP_TRY(hipMemcpyAsync(xb->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));  // (the last pass's inputs have left the staging area: the results go there)

@@ -17,7 +17,8 @@ struct bool_steps {
 
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split = true,
-                            const ranked_args* rk = nullptr, bool_steps* extra = nullptr, range_args* rg = nullptr);
+                            const ranked_args* rk = nullptr, bool_steps* extra = nullptr, range_args* rg = nullptr,
+                            filter_args* fl = nullptr);
 
 // One AND call: what its stages share.
 struct and_call {
@@ -26,6 +27,7 @@ struct and_call {
     const ranked_args* rk = nullptr;        // ranked_and: the freqs pass scores and selects
     bool_steps* extra = nullptr;            // ranked_bool: excluded steps before the freqs pass, optional steps inside it
     range_args* rg = nullptr;               // a ranged call: candidates from the rarest list's blocks in range, the others killed
+    filter_args* fl = nullptr;              // a filtered call: candidates from the rarest list's live blocks, the others killed
     size_t n_queries = 0;
     uint64_t* counts = nullptr;
     hipStream_t s = nullptr;
@@ -83,7 +85,8 @@ struct bool_slots {
 static int bool_step(const bool_slots& b, const uint32_t* first, const uint32_t* nblk, const uint32_t* h_nblk, const float* weight,
                      uint32_t* d_cnt);
 
-// the candidates: the rarest list of every query, a page per block (a ranged call: per block in the query's range)
+// the candidates: the rarest list of every query, a page per block (a ranged call: per block in the query's range; a
+// filtered call: per live block)
 static void and_candidate_pages(and_call& c) {
     c.page_block.reserve(c.n_queries + 64);
     c.page_query.reserve(c.n_queries + 64);
@@ -93,6 +96,7 @@ static void and_candidate_pages(and_call& c) {
         const uint32_t rarest = c.plan.of(q)[0];
         const block_span in = blocks_in_range(c.qi, rarest, c.rg ? &c.rg->ranges[q] : nullptr);
         for (uint32_t b = c.qi->list_first[rarest] + in.p0; b != c.qi->list_first[rarest] + in.p1; ++b) {
+            if (!block_planned(c.fl, b)) continue;
             c.page_block.push_back(b);
             c.page_query.push_back(uint32_t(q));
         }
@@ -383,13 +387,13 @@ static int and_fused_form(and_call& c) {
 // ---- the other forms' beginning: the copy in; the candidates decoded, the first round's search riding along where the
 // one-launch decode runs (*searched). A ranged call: no search rides along — range_kill_kernel retires the candidates
 // outside their query's range behind the decode, and the first round's search is and_batch_rounds' own launch, so a
-// boundary candidate claims nothing ----
+// boundary candidate claims nothing. A filtered call: the same, with filter_kill_kernel ----
 static int and_candidates(and_call& c, bool* searched) {
     const int sent = and_send_inputs(c, true);
     if (sent != DINT_OK) return sent;
     const query_pages search0 = and_first_search(c);
     const int st = decode_pages_counted(c.qi, c.d_page_block, nullptr, c.n_pages, c.qi->cand.p, c.d_ctrl, 1u, c.s,
-                                        !c.rg && c.rounds && c.round_bound[0] ? &search0 : nullptr, searched);
+                                        !c.rg && !c.fl && c.rounds && c.round_bound[0] ? &search0 : nullptr, searched);
     if (st != DINT_OK) return c.failed(st);
     c.qi->claims_dirty = true;  // until the call has run to its end
     if (c.rg) {
@@ -400,6 +404,10 @@ static int and_candidates(and_call& c, bool* searched) {
             return c.failed(DINT_ERR_HIP);
         hipLaunchKernelGGL(range_kill_kernel, dim3(c.slot_grid()), dim3(kPageSlots), 0, c.s, c.qi->cand.p, c.n_slots, c.d_page_query,
                            c.qi->q_ranges.p);
+        if (hipGetLastError() != hipSuccess) return c.failed(DINT_ERR_HIP);
+    }
+    if (c.fl) {
+        hipLaunchKernelGGL(filter_kill_kernel, dim3(c.slot_grid()), dim3(kPageSlots), 0, c.s, c.qi->cand.p, c.n_slots, c.fl->filter->view());
         if (hipGetLastError() != hipSuccess) return c.failed(DINT_ERR_HIP);
     }
     return DINT_OK;
@@ -586,7 +594,7 @@ static int and_copy_back(and_call& c, uint64_t* freq_sums, uint64_t* freq_blocks
 // tails or batch rounds — then, with a freqs dictionary, the freqs / ranked pass, and the copy back.
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split,
-                            const ranked_args* rk, bool_steps* extra, range_args* rg) {
+                            const ranked_args* rk, bool_steps* extra, range_args* rg, filter_args* fl) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -597,6 +605,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     c.rk = rk;
     c.extra = extra;
     c.rg = rg;
+    c.fl = fl;
     c.n_queries = n_queries;
     c.counts = counts;
     c.s = static_cast<hipStream_t>(stream);
@@ -604,6 +613,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     if (planned != DINT_OK) return planned;
     and_candidate_pages(c);
     if (rg) rg->blocks = c.n_pages;
+    if (fl) fl->blocks = c.n_pages;
     if (c.n_pages == 0) return DINT_OK;
     bool mixed = false;
     const int split = may_split ? and_mixed_split(c, stream, &mixed) : DINT_OK;
@@ -620,8 +630,8 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     }
     int st = and_stage_general(c);
     if (st != DINT_OK) return st;
-    // (a ranged call never takes the one-launch form: its candidates die between their decode and the first search)
-    const bool fused_form = !rg && c.small_rounds && c.n_pages <= tail_pages() && c.n_pages <= fused_pages();
+    // (a ranged or filtered call never takes the one-launch form: its candidates die between their decode and the first search)
+    const bool fused_form = !rg && !fl && c.small_rounds && c.n_pages <= tail_pages() && c.n_pages <= fused_pages();
     // the last probe hands the results over itself (a few pages: every workgroup of it passes through one counter)
     c.results_to_host = !freqs_dict && qi->d_stage != nullptr && c.n_pages <= 4096;
     unsigned long long* const host_counts = c.results_to_host ? static_cast<unsigned long long*>(qi->d_stage) : nullptr;

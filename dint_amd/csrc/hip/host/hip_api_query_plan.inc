@@ -90,6 +90,33 @@ static block_span blocks_in_range(const dint_query_index* qi, uint32_t l, const 
     return list_blocks_in_range(qi->block_max.data() + qi->list_first[l], nb, r->lo, r->hi);
 }
 
+// A document filter (dint_doc_filter_create, hip_api_doc_filter.inc): a bitmap over the docID space and, for the query
+// index it was made for, which blocks are live under it. Immutable once created.
+struct dint_doc_filter {
+    const dint_query_index* qi = nullptr;  // the index whose block table live / live_before follow
+    int device = 0;
+    uint64_t num_docs = 0, n_set = 0, n_blocks = 0;
+    uint64_t* d_bits = nullptr;             // ceil(num_docs / 64) words, masked at num_docs (at least one word)
+    uint32_t* d_live_before = nullptr;      // n_blocks + 1
+    std::vector<uint8_t> live;              // the host's copy of the flags: the filtered calls plan their pages here
+    std::vector<uint32_t> live_before;      // ... and of d_live_before: a list's live blocks in O(1)
+    doc_filter_view view() const { return doc_filter_view{d_bits, uint32_t(num_docs), d_live_before}; }
+};
+// A filtered call (hip_api_doc_filter.inc): its filter, and what the call reports besides its answer. Where a call takes a
+// null one there is no filter: nothing is planned or launched differently.
+struct filter_args {
+    const dint_doc_filter* filter = nullptr;
+    uint64_t blocks = 0;                        // out: the pages the call planned (OR: every term's live blocks; AND: the rarest's)
+    std::vector<unsigned long long> h_matches;  // out (OR): per query the union's documents in the filter
+};
+// The pages a call plans for list l: its blocks in range (r null: every block), or under a filter its live blocks.
+static uint32_t planned_blocks(const dint_query_index* qi, uint32_t l, const dint_doc_range* r, const filter_args* fl) {
+    if (fl) return fl->filter->live_before[qi->list_first[l + 1]] - fl->filter->live_before[qi->list_first[l]];
+    return blocks_in_range(qi, l, r).size();
+}
+// ... and whether block b (of the index) is one of them, for a b inside the list's span in range
+static bool block_planned(const filter_args* fl, uint32_t b) { return !fl || fl->filter->live[b] != 0; }
+
 // the *_queries_freqs entries: a freqs dictionary of the index's device and kind, and somewhere for the sums
 static bool freqs_args_ok(const dint_query_index* qi, const dint_dict* freqs_dict, const uint64_t* freq_sums) {
     return freqs_dict && freq_sums && (!qi || (freqs_dict->device == qi->docs->device && freqs_dict->kind == qi->docs->kind));

@@ -38,6 +38,7 @@ ABI_SYMBOLS = (
     "dint_query_index_create", "dint_query_index_destroy", "dint_and_queries", "dint_and_queries_freqs", "dint_or_queries", "dint_or_queries_freqs",
     "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_bool_queries", "dint_ranked_or_queries",
     "dint_ranked_or_bool_queries", "dint_ranked_or_range_queries", "dint_ranked_and_range_queries",
+    "dint_doc_filter_create", "dint_doc_filter_info_get", "dint_doc_filter_destroy", "dint_ranked_or_filtered_queries", "dint_ranked_and_filtered_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_check_index", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -71,6 +72,10 @@ class StreamStats(C.Structure):
 class CollectionView(C.Structure):  # dint_collection_view
     _fields_ = [("docs", C.c_void_p), ("freqs", C.c_void_p), ("docs_at", C.c_void_p), ("freqs_at", C.c_void_p),
                 ("list_len", C.c_void_p), ("n_lists", C.c_size_t)]
+
+
+class DocFilterInfo(C.Structure):  # dint_doc_filter_info
+    _fields_ = [(k, C.c_uint64) for k in ("num_docs", "n_set", "n_blocks", "live_blocks")]
 
 
 class IndexMismatch(C.Structure):  # dint_index_mismatch
@@ -153,6 +158,12 @@ def _load():
     lib.dint_ranked_or_bool_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_or_range_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_and_range_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_doc_filter_create.argtypes = [vp, vp, u64, C.POINTER(vp)]
+    lib.dint_doc_filter_info_get.argtypes = [vp, C.POINTER(DocFilterInfo)]
+    lib.dint_doc_filter_destroy.argtypes = [vp]
+    lib.dint_doc_filter_destroy.restype = None
+    lib.dint_ranked_or_filtered_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_filtered_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
@@ -717,6 +728,45 @@ class QueryIndex:
         decoded: the candidate pages, i.e. the blocks in range of every query's rarest list."""
         return self._ranked_range("dint_ranked_and_range_queries", freqs_dict, wand, queries, ranges, k, with_stats)
 
+    def doc_filter(self, mask_or_docids, num_docs=None, form=None) -> "DocFilter":
+        """A document filter for this index (dint_doc_filter_create) from a bool array (document d in
+        the filter iff mask[d]; num_docs defaults to its length), a u64 array of bitmap words (bit d & 63 of word d >> 6;
+        num_docs defaults to 64 * its length; with num_docs, exactly ceil(num_docs / 64) words) or a sequence of docIDs
+        (num_docs defaults to the largest + 1; those at or past a given num_docs are left out). form ("mask", "words" or
+        "docids") says which it is; without it the dtype does (bool, u64, anything else), so docIDs held in a u64 array
+        need form="docids". Close it before the index."""
+        return DocFilter(self, mask_or_docids, num_docs, form)
+
+    def _ranked_filtered(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, doc_filter, k: int, with_stats: bool):
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 doc_filter._h if doc_filter is not None else None, n, counts.ctypes.data, matches.ctypes.data,
+                                 scores.ctypes.data, docids.ctypes.data, C.byref(blocks), self._stream()), fn)
+        return (counts, scores, docids, matches, blocks.value) if with_stats else (counts, scores, docids)
+
+    def ranked_or_filtered_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, doc_filter, k: int = 10,
+                                   with_stats: bool = False):
+        """ranked_or_queries over the documents of one filter for the whole batch (dint_ranked_or_filtered_queries, DESIGN.md
+        4d-filter): doc_filter is a DocFilter of this index, or None (unrestricted). A match scores exactly what
+        ranked_or_queries gives it; only the live blocks — those whose docID span holds a document of the filter — are
+        decoded -> (counts u64[n] = min(k, matches), scores f32[n, k], docids u32[n, k] as ranked_or_queries) and,
+        with_stats, (matches u64[n]: the union's documents in the filter, blocks decoded: every distinct term's live blocks,
+        summed over the queries)."""
+        return self._ranked_filtered("dint_ranked_or_filtered_queries", freqs_dict, wand, queries, doc_filter, k, with_stats)
+
+    def ranked_and_filtered_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, doc_filter, k: int = 10,
+                                    with_stats: bool = False):
+        """ranked_and_queries over the documents of one filter (dint_ranked_and_filtered_queries):
+        arguments and outputs as ranked_or_filtered_queries; matches: the intersection's documents in the filter, blocks
+        decoded: the candidate pages, i.e. the live blocks of every query's rarest list."""
+        return self._ranked_filtered("dint_ranked_and_filtered_queries", freqs_dict, wand, queries, doc_filter, k, with_stats)
+
     def ranked_or_maxscore_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10):
         """ranked_or_queries' answer, bit for bit, with MaxScore's pruning: the blocks of low-weight
         lists that no candidate able to reach the top k falls in are not decoded. `wand` must carry max_term_weight ->
@@ -787,6 +837,63 @@ class QueryIndex:
         if first.kind == CHECK_OK:
             return n.value, None
         return n.value, Mismatch(first.kind, first.list, first.position, first.expected, first.got)
+
+
+def doc_filter_words(mask_or_docids, num_docs=None, form=None):
+    """What QueryIndex.doc_filter hands the library: (u64 bitmap words, num_docs) from a bool mask, u64 words or docIDs.
+    form: "mask", "words" or "docids"; None: by dtype — bool, u64, anything else. A u64 array taken as words must have
+    exactly ceil(num_docs / 64) of them where num_docs is given: docIDs that happen to be u64 are refused, not misread."""
+    a = np.asarray(mask_or_docids)
+    if form is None:
+        form = "mask" if a.dtype == np.bool_ else "words" if a.dtype == np.uint64 else "docids"
+    if form not in ("mask", "words", "docids"):
+        raise ValueError("form is 'mask', 'words' or 'docids'")
+    if form == "mask":
+        a = a.astype(np.bool_, copy=False)
+        n = a.size if num_docs is None else int(num_docs)
+        bits = np.zeros(-(-n // 64) * 64, dtype=np.uint8)
+        bits[:min(n, a.size)] = a.reshape(-1)[:n]
+        words = np.packbits(bits, bitorder="little").view("<u8")
+    elif form == "words":
+        n = 64 * a.size if num_docs is None else int(num_docs)
+        if a.size != -(-n // 64):
+            raise ValueError(f"{a.size} bitmap words for num_docs = {n}: ceil(num_docs / 64) = {-(-n // 64)} are needed "
+                             "(docIDs in a u64 array: pass form='docids')")
+        words = a.reshape(-1).astype(np.uint64)
+    else:
+        d = a.astype(np.int64).reshape(-1)
+        assert d.size == 0 or (d.min() >= 0 and d.max() < 0xFFFFFFFF)
+        n = (int(d.max()) + 1 if d.size else 0) if num_docs is None else int(num_docs)
+        d = d[d < n]
+        words = np.zeros(-(-n // 64), dtype=np.uint64)
+        np.bitwise_or.at(words, d >> 6, np.uint64(1) << (d & 63).astype(np.uint64))
+    return np.ascontiguousarray(words, dtype=np.uint64), n
+
+
+class DocFilter:
+    """A document filter of one QueryIndex (dint_doc_filter): a bitmap over the docID space and, found
+    on the device when it is made, which blocks of the index can hold a document of it. Immutable; one filter serves
+    any number of ranked_*_filtered_queries calls, from several threads. It keeps its index alive; close() it first."""
+
+    def __init__(self, index: "QueryIndex", mask_or_docids, num_docs=None, form=None):
+        words, n = doc_filter_words(mask_or_docids, num_docs, form)
+        self.index = index
+        self._h = C.c_void_p()
+        _check(_lib.dint_doc_filter_create(index._h, words.ctypes.data if words.size else None, n, C.byref(self._h)),
+               "dint_doc_filter_create")
+
+    @property
+    def info(self) -> DocFilterInfo:
+        out = DocFilterInfo()
+        _check(_lib.dint_doc_filter_info_get(self._h, C.byref(out)), "dint_doc_filter_info_get")
+        return out
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:  # (None at interpreter shutdown)
+            _lib.dint_doc_filter_destroy(h)
+
+    __del__ = close
 
 
 class WandData:

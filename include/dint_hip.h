@@ -611,6 +611,70 @@ int dint_ranked_and_range_queries(dint_query_index* qi, const dint_dict* freqs_d
                                   size_t n_queries, uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids,
                                   uint64_t* blocks_decoded, void* stream);
 
+/* ---- document-filter ranked queries (BM25 top-k of the union / the intersection within a set of documents) ----
+ * Replaces: ranked_or_query / ranked_and_query (include/ds2i/queries.hpp:309-457) with a restriction of a whole call to an
+ * arbitrary set of documents, given as a bitmap over the docID space — the documents not deleted, a category, a language, a
+ * tenant, an access list — for a batch of queries per call under ONE filter. The unfiltered calls with a large k, filtered
+ * by the caller, are capped at DINT_RANKED_MAX_K and decode every block for nothing; the range calls take one interval a
+ * query.
+ * A filter handle (dint_doc_filter_create): bits is a HOST array of ceil(num_docs / 64) words, document d in the filter iff
+ * d < num_docs and bit (d & 63) of word (d >> 6) is set. The handle keeps its own copy (bits may be released at once) and
+ * ignores the bits at and past num_docs of the last word. num_docs may be smaller or larger than the index's largest
+ * docID: docIDs at or past it are not in the filter. num_docs == 0: the empty filter, bits may be null.
+ * num_docs > 0xFFFFFFFF, a null qi or out: DINT_ERR_ARG. The handle belongs to the query index it was created for — it
+ * holds, for that index's block table, which blocks are LIVE: a block with dint_block_ref fields base and max is live iff
+ * the filter holds a document d with base <= d <= max (and d < num_docs). These are found on the device at creation (a rank
+ * directory of the bitmap, a thread per block, a prefix count of the live blocks), under the index's lock, which the handle
+ * takes at no other time. It is immutable afterwards, usable from several host threads at once, and must be destroyed
+ * before its index. dint_doc_filter_info_get: n_set = the documents in the filter, n_blocks = the index's blocks,
+ * live_blocks = the live ones.
+ * The filtered calls, filter one handle for the whole call: the matches of query q are the documents of the unfiltered
+ * call's match set (the union of its lists for dint_ranked_or_filtered_queries, the intersection for
+ * dint_ranked_and_filtered_queries) that are in the filter. An empty filter selects nothing and decodes nothing. A null
+ * filter is unrestricted — the range calls on null ranges — and a filter with every bit set up to at least the index's
+ * largest docID + 1 gives the same: counts, scores and docids are the unfiltered call's, bit for bit. A filter that holds
+ * exactly the docIDs [lo, hi) gives the range call's counts, matches, scores, docids and *blocks_decoded on that range
+ * (live and in range are one rule for an interval).
+ * The score of a match is EXACTLY the unfiltered call's — the same terms in the same order (OR: ascending term id; AND:
+ * increasing list length, equal lengths by increasing term id), the same binary32 operations, and q_weight_t still from the
+ * WHOLE list's length and wd's num_docs: the filter filters, it does not re-weight.
+ * matches[q] (HOST, nullable) = the number of matches in the filter; counts[q] = min(k, matches[q]); scores, docids
+ * (nullable), their order (descending score, equal scores by ascending docID) and their filler (0.0f / 0xFFFFFFFF) are the
+ * other ranked calls'.
+ * Skipping: of a list only the live blocks are decoded, wherever they lie in the list. What a live block holds outside the
+ * filter is dropped on the device before it is scored or probes anything. A scattered filter leaves almost every block
+ * live (a block of 256 postings is dead only if none of the docIDs it spans is in the filter): there the drop is what
+ * pays, the skipping pays for clustered filters.
+ * *blocks_decoded (nullable), exact for any batch — OR: the sum over the queries and over their distinct terms of the
+ * list's live blocks; AND: the candidate pages, i.e. the live blocks of each query's rarest list (shortest, equal lengths
+ * by term id), summed over the queries. The blocks the AND rounds and its scoring claim behind that are the unfiltered
+ * call's lazy ones, for candidates in the filter only, and are not counted.
+ * DINT_ERR_ARG, before anything is launched (no output is written): what the unfiltered calls refuse — k == 0 or
+ * k > DINT_RANKED_MAX_K, a term >= n_lists, decreasing offsets, null counts or scores, a freqs_dict of another kind or
+ * device than the docs dictionary, a wand handle on another device or one whose num_docs does not exceed the index's
+ * largest docID — and a filter created for another query index. Terms, query_offsets, the handle's lock and the stream
+ * are as for the unfiltered calls. The OR call runs in dint_ranked_or_queries' passes (DINT_OPT_QUERY_OR_PASS_PAGES), sized by
+ * the LIVE blocks; the AND call takes the round-per-launch form with the first round's search as a launch of its own, as
+ * the range call does. A filter per query, and a filter combined with a range, are out of scope. */
+typedef struct dint_doc_filter dint_doc_filter;
+typedef struct dint_doc_filter_info {
+    uint64_t num_docs;    /* as given to dint_doc_filter_create                  */
+    uint64_t n_set;       /* documents in the filter                             */
+    uint64_t n_blocks;    /* blocks of the query index                           */
+    uint64_t live_blocks; /* ... whose [base, max] holds a document of the filter */
+} dint_doc_filter_info;
+int dint_doc_filter_create(dint_query_index* qi, const uint64_t* bits, uint64_t num_docs, dint_doc_filter** out);
+int dint_doc_filter_info_get(const dint_doc_filter* f, dint_doc_filter_info* info);
+void dint_doc_filter_destroy(dint_doc_filter* f);
+int dint_ranked_or_filtered_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                    const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                    size_t n_queries, uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids,
+                                    uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_filtered_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                     const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                     size_t n_queries, uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids,
+                                     uint64_t* blocks_decoded, void* stream);
+
 /* ---- the wand data's BM25 maxima from the index, on the device; block maxima for the pruned call --------------
  * Replaces: the max_term_weight half of wand_data's constructor (include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp),
  * which walks the uncompressed collection posting by posting, by one decode of the INDEX: a caller that has only what this

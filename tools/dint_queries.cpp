@@ -1,9 +1,10 @@
 // dint_queries — the reference's `queries` tool (src/queries.cpp:15-153) for the DINT index types, on the device path.
 //
-//   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] < query_log
+//   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] [--filter FILE] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
 //   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
-//               ranked_or_bool | ranked_or_range | ranked_and_range, several separated by ':'
+//               ranked_or_bool | ranked_or_range | ranked_and_range | ranked_or_filtered | ranked_and_filtered, several
+//               separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
@@ -24,6 +25,11 @@
 //               ranked_and over the documents of a docID interval) read their lines as term ids plus at
 //               most one @lo:hi token — the line's half-open range [lo, hi); without it the line is unrestricted — and so
 //               each must be the only type of its run; also only with a wand file; output and keys are ranked_or's;
+//               ranked_or_filtered / ranked_and_filtered (dint_ranked_or_filtered_queries, dint_ranked_and_filtered_queries:
+//               ranked_or / ranked_and over the documents of one filter for the whole log) need
+//               --filter FILE — every line a docID `d` or a half-open interval `lo:hi`, the filter their union
+//               (doc_filter_file.hpp) — and each must be the only type of its run; a filtered type without --filter is a
+//               usage error; also only with a wand file; the query lines, output and keys are ranked_or's;
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -38,6 +44,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <numeric>
 #include <sstream>
@@ -46,6 +53,7 @@
 
 #include "dint/index_file.hpp"
 #include "dint_hip.h"
+#include "doc_filter_file.hpp"
 #include "tool_common.hpp"
 
 static void dint_ok(int st, const char* what) {
@@ -57,7 +65,7 @@ static double now_us() {
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] < query_log"
+        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] < query_log"
                   << std::endl;
         return 1;
     }
@@ -65,12 +73,14 @@ int main(int argc, char** argv) {
         std::string type = argv[1], query_type = argv[2];
         const char* index_filename = argv[3];
         const char* wand_filename = nullptr;
+        const char* filter_filename = nullptr;
         bool batch = false;
         size_t runs = 10 + 1;  // src/queries.cpp:13
         for (int i = 4; i < argc; ++i) {
             std::string a = argv[i];
             if (a == "--batch") batch = true;
             else if (a == "--runs" && i + 1 < argc) runs = size_t(std::max(2, std::atoi(argv[++i])));
+            else if (a == "--filter" && i + 1 < argc) filter_filename = argv[++i];
             else if (!wand_filename && a.rfind("--", 0) != 0) wand_filename = argv[i];
             else throw std::runtime_error("unknown parameter");
         }
@@ -89,6 +99,21 @@ int main(int argc, char** argv) {
         for (const char* ranged : {"ranked_or_range", "ranked_and_range"})
             if (!is_range && (":" + query_type + ":").find(std::string(":") + ranged + ":") != std::string::npos)
                 throw std::runtime_error(std::string(ranged) + " reads its query lines as term ids and one @lo:hi token: it must be the only query type of a run");
+        const bool is_filtered = query_type == "ranked_or_filtered" || query_type == "ranked_and_filtered";
+        for (const char* filtered : {"ranked_or_filtered", "ranked_and_filtered"})
+            if (!is_filtered && (":" + query_type + ":").find(std::string(":") + filtered + ":") != std::string::npos)
+                throw std::runtime_error(std::string(filtered) + " answers its whole log under --filter: it must be the only query type of a run");
+        if (is_filtered && !filter_filename) {
+            std::cerr << query_type << " needs --filter FILE (every line a docID d or an interval lo:hi)" << std::endl;
+            return 1;
+        }
+        if (!is_filtered && filter_filename) throw std::runtime_error("--filter goes with ranked_or_filtered or ranked_and_filtered only");
+        tool::doc_filter_bits filter_bits;
+        if (is_filtered) {
+            std::ifstream ff(filter_filename);
+            if (!ff) throw std::runtime_error(std::string("could not open the filter file ") + filter_filename);
+            filter_bits = tool::parse_doc_filter(ff);
+        }
         // read_query (queries.hpp:15-27)
         std::vector<std::vector<uint32_t>> queries;
         // ranked_bool: `queries` holds the required terms; the optional and excluded ones packed, offsets per query
@@ -202,6 +227,8 @@ int main(int argc, char** argv) {
                 dint_ok(dint_wand_data_set_block_max_weights(wand_blockmax, block_max.data(), n_blocks), "dint_wand_data_set_block_max_weights");
             }
         }
+        dint_doc_filter* doc_filter = nullptr;  // ranked_*_filtered: the run's filter
+        if (is_filtered) dint_ok(dint_doc_filter_create(qi, filter_bits.words.data(), filter_bits.num_docs, &doc_filter), "dint_doc_filter_create");
         constexpr uint32_t kTopK = 10;  // ranked_and_query(wdata, 10), src/queries.cpp:106-108
         std::vector<float> top_scores;
 
@@ -219,8 +246,9 @@ int main(int argc, char** argv) {
             const bool is_ranked_bool = t == "ranked_bool" && wand;
             const bool is_ranked_or_bool = t == "ranked_or_bool" && wand;
             const bool is_or_range = t == "ranked_or_range" && wand, is_and_range = t == "ranked_and_range" && wand;
+            const bool is_or_filtered = t == "ranked_or_filtered" && wand, is_and_filtered = t == "ranked_and_filtered" && wand;
             const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
-                                   is_or_range || is_and_range;
+                                   is_or_range || is_and_range || is_or_filtered || is_and_filtered;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
                 std::cerr << "Unsupported query type: " << t << std::endl;  // src/queries.cpp:108-110
                 continue;
@@ -251,6 +279,16 @@ int main(int argc, char** argv) {
                         dint_ok(dint_ranked_and_range_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, ranges.data() + q0, n, q_counts, nullptr,
                                                               top_scores.data(), nullptr, nullptr, nullptr),
                                 "dint_ranked_and_range_queries");
+                } else if (is_or_filtered || is_and_filtered) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    if (is_or_filtered)
+                        dint_ok(dint_ranked_or_filtered_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, n, q_counts, nullptr,
+                                                                top_scores.data(), nullptr, nullptr, nullptr),
+                                "dint_ranked_or_filtered_queries");
+                    else
+                        dint_ok(dint_ranked_and_filtered_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, n, q_counts, nullptr,
+                                                                 top_scores.data(), nullptr, nullptr, nullptr),
+                                "dint_ranked_and_filtered_queries");
                 } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
@@ -320,6 +358,7 @@ int main(int argc, char** argv) {
             if (batch_us >= 0) std::cout << ", \"batch_us_per_query\": " << batch_us;
             std::cout << ", \"device\": \"" << device_name << "\"}" << std::endl;
         }
+        dint_doc_filter_destroy(doc_filter);
         dint_wand_data_destroy(wand);
         dint_wand_data_destroy(wand_blockmax);
         dint_query_index_destroy(qi);
