@@ -17,6 +17,10 @@
 // under the call's filter, the term records still describe the whole lists, the scoring launch is
 // ranked_or_filtered_score_kernel, which finds a block's page through the filter's live rank and counts the matches into
 // the call's counters; those come back with the last pass. Without fl nothing is planned or launched differently.
+// fa (dint_ranked_or_faceted_queries, hip_api_facets.inc), with rk and with rg or fl: the pass's page -> query table is staged
+// besides, and facet_count_kernel runs between the scoring launch and ranked_topk, over the pass's slots in cand; it adds
+// to the call's facet rows, cleared once per call, which come back with the last pass. Without fa nothing is planned or
+// launched differently.
 
 // What a ranked OR call with a minimum and exclusions adds to its passes, and what it gets back.
 struct or_bool_args {
@@ -75,9 +79,10 @@ struct or_pass_query {
 // or_range_layout staged behind the pass's own, and ranked_or_range_score_kernel scores, adding the matches to d_counts.
 // fl (with rk and d_counts, not ranged): a term record's pages are its list's live blocks, the record itself the whole
 // list's; nothing more is staged, and ranked_or_filtered_score_kernel scores, adding the matches to d_counts.
+// fa (with rk; its rows cleared): or_facet_layout staged behind the others, facet_count_kernel behind the scoring launch.
 static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const ranked_args* rk, const std::vector<or_pass_query>& qs,
                        size_t min_stage, unsigned long long* d_counts, size_t n_counts, uint32_t id0, size_t n_ids, hipStream_t s,
-                       or_bool_args* xb = nullptr, bool ranged = false, const filter_args* fl = nullptr) {
+                       or_bool_args* xb = nullptr, bool ranged = false, const filter_args* fl = nullptr, const facet_args* fa = nullptr) {
     uint64_t n_pages = 0, n_terms = 0;
     for (const or_pass_query& q : qs) {
         n_terms += q.n;
@@ -90,7 +95,8 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
             if (q.n) n_steps = std::max<size_t>(n_steps, xb->not_at[q.id + 1] - xb->not_at[q.id]);
     const or_bool_layout B(L.words, xb ? n_pages : 0, xb ? n_terms : 0, n_steps * n_ids, n_steps);
     const or_range_layout R(B.words, ranged ? n_terms : 0);
-    const size_t up_words = R.words;  // (without xb and not ranged: L.words)
+    const or_facet_layout F(R.words, fa ? n_pages : 0);
+    const size_t up_words = F.words;  // (without xb and fa and not ranged: L.words)
     if (qi->stage(std::max<size_t>(up_words * 4, min_stage)) != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     uint32_t *page_block = qi->h(L.page_block), *page_term = qi->h(L.page_term), *term_order = qi->h(L.term_order);
     std::vector<uint32_t> page_query(rk ? n_pages : 0);  // (ranked_topk's: the pass's queries, from 0)
@@ -121,6 +127,7 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
             }
         }
     }
+    if (fa && n_pages) std::memcpy(qi->h(F.page_query), page_query.data(), n_pages * 4);
     if (xb) {
         if (n_pages) std::memcpy(qi->h(B.page_query), page_query.data(), n_pages * 4);
         std::memset(qi->h(B.not_first), 0, (B.words - B.not_first) * 4);
@@ -207,6 +214,7 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
                            d_counts + id0);
         if (hipGetLastError() != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     }
+    if (fa && facet_count_launch(qi, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     const int rst = ranked_topk(qi, *rk, page_query, n_ids, s);
     return rst != DINT_OK ? stream_failed(s, rst) : DINT_OK;
 }
@@ -214,7 +222,7 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
 static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream,
                            const ranked_args* rk = nullptr, or_bool_args* xb = nullptr, range_args* rg = nullptr,
-                           filter_args* fl = nullptr) {
+                           filter_args* fl = nullptr, facet_args* fa = nullptr) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -236,11 +244,16 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         fl->blocks = op.all;
         fl->h_matches.assign(n_queries, 0ull);
     }
+    facet_rows_begin(fa, n_queries);
     if (op.all == 0) return DINT_OK;
 
     std::lock_guard<std::mutex> lock(qi->mutex);
     HIP_TRY(hipSetDevice(qi->docs->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (fa) {
+        const int cleared = facet_rows_clear(qi, fa, n_queries, s);
+        if (cleared != DINT_OK) return cleared;
+    }
     // the call's counters: counts[n_queries] then freq sums[n_queries], cleared once, added to by every pass
     if (!qi->freq_sums.ensure(2 * n_queries)) return DINT_ERR_HIP;
     unsigned long long* const d_counts = qi->freq_sums.p;
@@ -266,9 +279,10 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         ranked_args pass_rk = rk ? *rk : ranked_args{};
         if (rk) pass_rk.keys += uint64_t(q0) * rk->k;  // (the keys of the pass's queries at their own offset)
         const int st = or_run_pass(qi, freqs_dict, rk ? &pass_rk : nullptr, qs, 2 * n_queries * sizeof(unsigned long long), d_counts,
-                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl);
+                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl, fa);
         if (st != DINT_OK) return st;
     }
+    if (fa && facet_rows_back(fa, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (fl) HIP_TRY(hipMemcpyAsync(fl->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (rg) HIP_TRY(hipMemcpyAsync(rg->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (xb) HIP_TRY(hipMemcpyAsync(xb->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));

@@ -117,6 +117,49 @@ static uint32_t planned_blocks(const dint_query_index* qi, uint32_t l, const din
 // ... and whether block b (of the index) is one of them, for a b inside the list's span in range
 static bool block_planned(const filter_args* fl, uint32_t b) { return !fl || fl->filter->live[b] != 0; }
 
+// A facets handle (dint_doc_facets_create, hip_api_facets.inc): docID -> group, a word per document on the device, and the
+// groups' sizes on the host. It belongs to a device, not to a query index. Immutable once created.
+struct dint_doc_facets {
+    int device = 0;
+    uint64_t num_docs = 0, n_grouped = 0;
+    uint32_t n_groups = 0;
+    uint32_t* d_group_of = nullptr;  // max(1, num_docs) words
+    std::vector<uint32_t> sizes;     // n_groups: the documents of every group
+    doc_facets_view view() const { return doc_facets_view{d_group_of, uint32_t(num_docs), n_groups}; }
+};
+// A faceted call (hip_api_facets.inc): the handle, the call's rows on the device — n_queries * n_groups counters in the
+// query index's facet_rows workspace, cleared once per call, added to by every pass — and where they go on the host. Where a
+// call takes a null one there are no facets: nothing is planned or launched differently.
+struct facet_args {
+    const dint_doc_facets* facets = nullptr;
+    uint32_t* d_rows = nullptr;  // (set by facet_rows_clear)
+    uint32_t* h_rows = nullptr;  // the caller's facet_counts
+    size_t words(size_t n_queries) const { return n_queries * size_t(facets->n_groups); }
+};
+// the call is planned and has refused nothing: every row is zero until a pass says otherwise
+static void facet_rows_begin(const facet_args* fa, size_t n_queries) {
+    if (fa) std::fill(fa->h_rows, fa->h_rows + fa->words(n_queries), 0u);
+}
+// under the index's lock, once per call, in front of its first counting launch
+static int facet_rows_clear(dint_query_index* qi, facet_args* fa, size_t n_queries, hipStream_t s) {
+    if (!qi->facet_rows.ensure(fa->words(n_queries))) return DINT_ERR_HIP;
+    fa->d_rows = qi->facet_rows.p;
+    HIP_TRY(hipMemsetAsync(fa->d_rows, 0, fa->words(n_queries) * 4, s));
+    return DINT_OK;
+}
+// facet_count_kernel over the n_pages pages of qi->cand; d_page_query[page] + q0: the page's query of the call
+static int facet_count_launch(const dint_query_index* qi, const facet_args* fa, uint64_t n_pages, const uint32_t* d_page_query, uint32_t q0,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(facet_count_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, n_pages * kPageSlots, d_page_query, q0,
+                       fa->facets->view(), fa->d_rows);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// ... and the rows' way back, on the stream, in front of the call's last wait
+static int facet_rows_back(const facet_args* fa, size_t n_queries, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(fa->h_rows, fa->d_rows, fa->words(n_queries) * 4, hipMemcpyDeviceToHost, s));
+    return DINT_OK;
+}
+
 // the *_queries_freqs entries: a freqs dictionary of the index's device and kind, and somewhere for the sums
 static bool freqs_args_ok(const dint_query_index* qi, const dint_dict* freqs_dict, const uint64_t* freq_sums) {
     return freqs_dict && freq_sums && (!qi || (freqs_dict->device == qi->docs->device && freqs_dict->kind == qi->docs->kind));

@@ -67,6 +67,8 @@ struct dint_query_index {
     device_buffer<uint32_t> ms_flag, ms_rank, ms_touched, ms_count;
     // the ranged ranked AND call (hip_api_ranked_range.inc): per query {lo, hi}
     device_buffer<uint32_t> q_ranges;
+    // the faceted ranked calls (hip_api_facets.inc): per query of the call a row of n_groups counters
+    device_buffer<uint32_t> facet_rows;
     // dint_check_index (hip_api_check.inc): every block of a list but its last holds 256 postings (the in-index layout:
     // block j of a list is its positions [256 j, 256 j + n)); two pinned staging buffers of a pass's expected postings
     // and their device copies, alternating

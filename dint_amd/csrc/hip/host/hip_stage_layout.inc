@@ -99,6 +99,15 @@ struct or_range_layout : stage_layout {
         take_each({&term_lo, &term_hi}, n_terms);
     }
 };
+// What a faceted ranked OR pass (dint_ranked_or_faceted_queries) stages besides, from word `base` on — behind the pass's
+// other layouts, which keep their words: page -> query of the pass (facet_count_kernel's; the selection has the host's copy).
+struct or_facet_layout : stage_layout {
+    size_t page_query;
+    or_facet_layout(size_t base, size_t n_pages) {
+        words = base;
+        page_query = take(n_pages);
+    }
+};
 // The pruned ranked call's main stage: per record {first, blocks, page, claimed, q_weight, order, E, query}, per query
 // {from, n, n_E, theta}, per candidate page {page, record}, the other E terms' blocks, then (8-byte aligned) per query
 // {rest, margin} (doubles).

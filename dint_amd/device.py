@@ -39,6 +39,8 @@ ABI_SYMBOLS = (
     "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_bool_queries", "dint_ranked_or_queries",
     "dint_ranked_or_bool_queries", "dint_ranked_or_range_queries", "dint_ranked_and_range_queries",
     "dint_doc_filter_create", "dint_doc_filter_info_get", "dint_doc_filter_destroy", "dint_ranked_or_filtered_queries", "dint_ranked_and_filtered_queries",
+    "dint_doc_facets_create", "dint_doc_facets_info_get", "dint_doc_facets_group_sizes", "dint_doc_facets_destroy",
+    "dint_ranked_or_faceted_queries", "dint_ranked_and_faceted_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_check_index", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -76,6 +78,10 @@ class CollectionView(C.Structure):  # dint_collection_view
 
 class DocFilterInfo(C.Structure):  # dint_doc_filter_info
     _fields_ = [(k, C.c_uint64) for k in ("num_docs", "n_set", "n_blocks", "live_blocks")]
+
+
+class DocFacetsInfo(C.Structure):  # dint_doc_facets_info
+    _fields_ = [(k, C.c_uint64) for k in ("num_docs", "n_groups", "n_grouped")]
 
 
 class IndexMismatch(C.Structure):  # dint_index_mismatch
@@ -164,6 +170,13 @@ def _load():
     lib.dint_doc_filter_destroy.restype = None
     lib.dint_ranked_or_filtered_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_and_filtered_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_doc_facets_create.argtypes = [C.c_int, vp, u64, u32, C.POINTER(vp)]
+    lib.dint_doc_facets_info_get.argtypes = [vp, C.POINTER(DocFacetsInfo)]
+    lib.dint_doc_facets_group_sizes.argtypes = [vp, vp]
+    lib.dint_doc_facets_destroy.argtypes = [vp]
+    lib.dint_doc_facets_destroy.restype = None
+    lib.dint_ranked_or_faceted_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_faceted_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
@@ -767,6 +780,35 @@ class QueryIndex:
         decoded: the candidate pages, i.e. the live blocks of every query's rarest list."""
         return self._ranked_filtered("dint_ranked_and_filtered_queries", freqs_dict, wand, queries, doc_filter, k, with_stats)
 
+    def _ranked_faceted(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, facets, doc_filter, k: int, with_stats: bool):
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        rows = np.zeros((n, facets.n_groups), dtype=np.uint32)
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 doc_filter._h if doc_filter is not None else None, facets._h, n, counts.ctypes.data,
+                                 matches.ctypes.data, scores.ctypes.data, docids.ctypes.data, rows.ctypes.data, C.byref(blocks),
+                                 self._stream()), fn)
+        return (counts, scores, docids, matches, blocks.value, rows) if with_stats else (counts, scores, docids, rows)
+
+    def ranked_or_faceted_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, facets: "DocFacets", filter=None,
+                                  k: int = 10, with_stats: bool = False):
+        """ranked_or_filtered_queries with the matches counted per document group (dint_ranked_or_faceted_queries, DESIGN.md
+        4d-facets): facets is a DocFacets on this index's device, filter a DocFilter of this index or None (unrestricted)
+        -> what ranked_or_filtered_queries returns for (queries, filter, k, with_stats), bit for bit, and behind it
+        rows u32[n, n_groups]: rows[q, g] = the matches of query q in group g, over every match, not over the top k."""
+        return self._ranked_faceted("dint_ranked_or_faceted_queries", freqs_dict, wand, queries, facets, filter, k, with_stats)
+
+    def ranked_and_faceted_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, facets: "DocFacets", filter=None,
+                                   k: int = 10, with_stats: bool = False):
+        """ranked_and_filtered_queries with the matches counted per document group (dint_ranked_and_faceted_queries):
+        arguments and outputs as ranked_or_faceted_queries, over the intersection."""
+        return self._ranked_faceted("dint_ranked_and_faceted_queries", freqs_dict, wand, queries, facets, filter, k, with_stats)
+
     def ranked_or_maxscore_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10):
         """ranked_or_queries' answer, bit for bit, with MaxScore's pruning: the blocks of low-weight
         lists that no candidate able to reach the top k falls in are not decoded. `wand` must carry max_term_weight ->
@@ -892,6 +934,66 @@ class DocFilter:
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None:  # (None at interpreter shutdown)
             _lib.dint_doc_filter_destroy(h)
+
+    __del__ = close
+
+
+FACET_NONE = 0xFFFFFFFF        # DINT_FACET_NONE (include/dint_hip.h): a document in no group
+FACETS_MAX_GROUPS = 65536      # DINT_FACETS_MAX_GROUPS
+
+
+def doc_facets_map(group_of, n_groups=None):
+    """What DocFacets hands the library: (u32 map, n_groups) from any integer array or sequence; a negative entry or None
+    is FACET_NONE (and so is FACET_NONE itself). n_groups defaults to the largest group + 1 (1 if no document is in a
+    group). Entries at or past a given n_groups are passed on: the library refuses them (DINT_ERR_ARG)."""
+    if not isinstance(group_of, np.ndarray):
+        group_of = [-1 if g is None else g for g in group_of]
+    a = np.asarray(group_of)
+    if a.dtype == object:
+        a = np.array([-1 if g is None else int(g) for g in a.reshape(-1)], dtype=np.int64)
+    if a.size and a.dtype.kind not in "iu":
+        raise TypeError("group_of holds integers (negative or None: in no group)")
+    a = a.reshape(-1)
+    if a.dtype.kind == "u":
+        if a.size and int(a.max()) > FACET_NONE:
+            raise ValueError("a group does not fit 32 bits")
+        m = a.astype(np.uint32)
+    else:
+        a = a.astype(np.int64)
+        if a.size and int(a.max()) > FACET_NONE:
+            raise ValueError("a group does not fit 32 bits")
+        m = np.where(a < 0, FACET_NONE, a).astype(np.uint32)
+    if n_groups is None:
+        real = m[m != FACET_NONE]
+        n_groups = int(real.max()) + 1 if real.size else 1
+    return np.ascontiguousarray(m, dtype=np.uint32), int(n_groups)
+
+
+class DocFacets:
+    """A document -> group map on a device (dint_doc_facets): group_of[d] is document d's group, a
+    negative entry or None no group, and so is every document at or past len(group_of). It belongs to no index — it
+    describes documents — holds 4 bytes per document on the device, is immutable and serves any number of
+    ranked_*_faceted_queries calls, from several threads. Creation raises DintError (DINT_ERR_ARG) for n_groups of 0 or above
+    FACETS_MAX_GROUPS and for an entry at or past n_groups."""
+
+    def __init__(self, device: int, group_of, n_groups=None):
+        m, n_groups = doc_facets_map(group_of, n_groups)
+        if not 0 <= n_groups <= 0xFFFFFFFF:
+            raise ValueError("n_groups does not fit 32 bits")
+        self.device = device
+        self._h = C.c_void_p()
+        _check(_lib.dint_doc_facets_create(device, m.ctypes.data if m.size else None, m.size, n_groups, C.byref(self._h)),
+               "dint_doc_facets_create")
+        info = DocFacetsInfo()
+        _check(_lib.dint_doc_facets_info_get(self._h, C.byref(info)), "dint_doc_facets_info_get")
+        self.num_docs, self.n_groups, self.n_grouped = int(info.num_docs), int(info.n_groups), int(info.n_grouped)
+        self.group_sizes = np.zeros(self.n_groups, dtype=np.uint32)
+        _check(_lib.dint_doc_facets_group_sizes(self._h, self.group_sizes.ctypes.data), "dint_doc_facets_group_sizes")
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:  # (None at interpreter shutdown)
+            _lib.dint_doc_facets_destroy(h)
 
     __del__ = close
 

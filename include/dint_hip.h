@@ -675,6 +675,54 @@ int dint_ranked_and_filtered_queries(dint_query_index* qi, const dint_dict* freq
                                      size_t n_queries, uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids,
                                      uint64_t* blocks_decoded, void* stream);
 
+/* ---- facet counts of the ranked queries (how many matches each document group holds) -----------------------------
+ * Adds: what a cursor engine computes with a facet collector beside its top-k collector (ranked_or_query / ranked_and_query,
+ * include/ds2i/queries.hpp:309-457, have none) — per query and per group of documents (a category, a site, a tenant, a
+ * date) the number of the query's matches in the group, for a batch of queries, in the call that ranks them. One filtered
+ * call per group answers the same, and decodes and scores everything once per group.
+ * A facets handle (dint_doc_facets_create): group_of is a HOST array of num_docs words; document d belongs to group
+ * group_of[d], or to no group if that word is DINT_FACET_NONE or d >= num_docs. The handle takes its device as
+ * dint_wand_data_create does and belongs to no query index: it describes documents, not blocks, and survives an index
+ * rebuild. It keeps its own copy of the map on the device, 4 BYTES PER DOCUMENT (group_of may be released at once), is
+ * immutable and usable from several host threads at once. DINT_ERR_ARG (no handle): n_groups == 0,
+ * n_groups > DINT_FACETS_MAX_GROUPS, num_docs > 0xFFFFFFFF, a null array with num_docs > 0, a null out, or any entry that
+ * is neither below n_groups nor DINT_FACET_NONE — found on the device: creation copies the map and runs one launch over
+ * it, which also counts the group sizes (the whole collection's histogram) with the device function the queries count
+ * with. dint_doc_facets_info_get: n_grouped = the documents in some group; dint_doc_facets_group_sizes: sizes[g] (HOST,
+ * n_groups words) = the documents of group g; both from the host, no device work.
+ * The faceted calls: counts, matches, scores, docids and *blocks_decoded are bit for bit what
+ * dint_ranked_or_filtered_queries / dint_ranked_and_filtered_queries return for the same arguments (filter null: the
+ * unfiltered answer with the matches counted). facet_counts (HOST, n_queries * n_groups words):
+ * facet_counts[q * n_groups + g] = the number of matches of query q whose group is g — over EVERY match, not over the top
+ * k — so the row's sum plus the matches in no group equals matches[q]; an empty query, or one without a match, has a row
+ * of zeros. The counts are integer sums: exact and the same from run to run.
+ * DINT_ERR_ARG, before anything is written or launched: whatever the filtered calls refuse, a null facets or facet_counts,
+ * a facets handle on another device than the index, n_queries * n_groups > 2^28 (the caller batches). The rows are a
+ * workspace of the query index (4 bytes * n_queries * n_groups, grow-only), cleared once per call. Terms, query_offsets,
+ * the handle's lock and the stream are as for the filtered calls; besides their launches a call runs one counting launch
+ * per OR pass / per AND call, which reads the candidate slots once more. Facets on the other query
+ * forms, several maps per call, score sums and the best document per group are out of scope. */
+#define DINT_FACET_NONE 0xFFFFFFFFu   /* a document in no group */
+#define DINT_FACETS_MAX_GROUPS 65536u
+typedef struct dint_doc_facets dint_doc_facets;
+typedef struct dint_doc_facets_info {
+    uint64_t num_docs;  /* as given to dint_doc_facets_create */
+    uint64_t n_groups;  /* as given to dint_doc_facets_create */
+    uint64_t n_grouped; /* documents in some group            */
+} dint_doc_facets_info;
+int dint_doc_facets_create(int device, const uint32_t* group_of, uint64_t num_docs, uint32_t n_groups, dint_doc_facets** out);
+int dint_doc_facets_info_get(const dint_doc_facets* f, dint_doc_facets_info* info);
+int dint_doc_facets_group_sizes(const dint_doc_facets* f, uint32_t* sizes);
+void dint_doc_facets_destroy(dint_doc_facets* f);
+int dint_ranked_or_faceted_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                   const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                   const dint_doc_facets* facets, size_t n_queries, uint64_t* counts, uint64_t* matches, float* scores,
+                                   uint32_t* docids, uint32_t* facet_counts, uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_faceted_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                    const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                    const dint_doc_facets* facets, size_t n_queries, uint64_t* counts, uint64_t* matches, float* scores,
+                                    uint32_t* docids, uint32_t* facet_counts, uint64_t* blocks_decoded, void* stream);
+
 /* ---- the wand data's BM25 maxima from the index, on the device; block maxima for the pruned call --------------
  * Replaces: the max_term_weight half of wand_data's constructor (include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp),
  * which walks the uncompressed collection posting by posting, by one decode of the INDEX: a caller that has only what this

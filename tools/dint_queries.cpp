@@ -1,10 +1,10 @@
 // dint_queries — the reference's `queries` tool (src/queries.cpp:15-153) for the DINT index types, on the device path.
 //
-//   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] [--filter FILE] < query_log
+//   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] [--filter FILE] [--facets FILE] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
 //   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
-//               ranked_or_bool | ranked_or_range | ranked_and_range | ranked_or_filtered | ranked_and_filtered, several
-//               separated by ':'
+//               ranked_or_bool | ranked_or_range | ranked_and_range | ranked_or_filtered | ranked_and_filtered |
+//               ranked_or_faceted | ranked_and_faceted, several separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
@@ -30,6 +30,13 @@
 //               --filter FILE — every line a docID `d` or a half-open interval `lo:hi`, the filter their union
 //               (doc_filter_file.hpp) — and each must be the only type of its run; a filtered type without --filter is a
 //               usage error; also only with a wand file; the query lines, output and keys are ranked_or's;
+//               ranked_or_faceted / ranked_and_faceted (dint_ranked_or_faceted_queries, dint_ranked_and_faceted_queries:
+//               ranked_or / ranked_and with the matches counted per document group) need --facets FILE —
+//               every line `d g` or `lo:hi g`, later lines win, a document no line names is in no group
+//               (doc_facets_file.hpp) — take --filter FILE as an option, and each must be the only type of its run; a
+//               faceted type without --facets is a usage error; also only with a wand file; the query lines, output and
+//               keys are ranked_or's, and the JSON line carries besides "matches" (every match of the log),
+//               "n_groups" and "facet_totals" (per group, the matches of the log's queries in it);
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -53,6 +60,7 @@
 
 #include "dint/index_file.hpp"
 #include "dint_hip.h"
+#include "doc_facets_file.hpp"
 #include "doc_filter_file.hpp"
 #include "tool_common.hpp"
 
@@ -65,7 +73,7 @@ static double now_us() {
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] < query_log"
+        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] < query_log"
                   << std::endl;
         return 1;
     }
@@ -74,6 +82,7 @@ int main(int argc, char** argv) {
         const char* index_filename = argv[3];
         const char* wand_filename = nullptr;
         const char* filter_filename = nullptr;
+        const char* facets_filename = nullptr;
         bool batch = false;
         size_t runs = 10 + 1;  // src/queries.cpp:13
         for (int i = 4; i < argc; ++i) {
@@ -81,6 +90,7 @@ int main(int argc, char** argv) {
             if (a == "--batch") batch = true;
             else if (a == "--runs" && i + 1 < argc) runs = size_t(std::max(2, std::atoi(argv[++i])));
             else if (a == "--filter" && i + 1 < argc) filter_filename = argv[++i];
+            else if (a == "--facets" && i + 1 < argc) facets_filename = argv[++i];
             else if (!wand_filename && a.rfind("--", 0) != 0) wand_filename = argv[i];
             else throw std::runtime_error("unknown parameter");
         }
@@ -107,9 +117,26 @@ int main(int argc, char** argv) {
             std::cerr << query_type << " needs --filter FILE (every line a docID d or an interval lo:hi)" << std::endl;
             return 1;
         }
-        if (!is_filtered && filter_filename) throw std::runtime_error("--filter goes with ranked_or_filtered or ranked_and_filtered only");
+        const bool is_faceted = query_type == "ranked_or_faceted" || query_type == "ranked_and_faceted";
+        for (const char* faceted : {"ranked_or_faceted", "ranked_and_faceted"})
+            if (!is_faceted && (":" + query_type + ":").find(std::string(":") + faceted + ":") != std::string::npos)
+                throw std::runtime_error(std::string(faceted) + " answers its whole log under --facets: it must be the only query type of a run");
+        if (is_faceted && !facets_filename) {
+            std::cerr << query_type << " needs --facets FILE (every line `d g` or `lo:hi g`: document d, or every document of [lo, hi), is in group g)"
+                      << std::endl;
+            return 1;
+        }
+        if (!is_faceted && facets_filename) throw std::runtime_error("--facets goes with ranked_or_faceted or ranked_and_faceted only");
+        if (!is_filtered && !is_faceted && filter_filename)
+            throw std::runtime_error("--filter goes with ranked_or_filtered, ranked_and_filtered, ranked_or_faceted or ranked_and_faceted only");
+        tool::doc_facets_map facets_map;
+        if (is_faceted) {
+            std::ifstream ff(facets_filename);
+            if (!ff) throw std::runtime_error(std::string("could not open the facets file ") + facets_filename);
+            facets_map = tool::parse_doc_facets(ff);
+        }
         tool::doc_filter_bits filter_bits;
-        if (is_filtered) {
+        if (filter_filename) {
             std::ifstream ff(filter_filename);
             if (!ff) throw std::runtime_error(std::string("could not open the filter file ") + filter_filename);
             filter_bits = tool::parse_doc_filter(ff);
@@ -228,7 +255,13 @@ int main(int argc, char** argv) {
             }
         }
         dint_doc_filter* doc_filter = nullptr;  // ranked_*_filtered: the run's filter
-        if (is_filtered) dint_ok(dint_doc_filter_create(qi, filter_bits.words.data(), filter_bits.num_docs, &doc_filter), "dint_doc_filter_create");
+        if (filter_filename) dint_ok(dint_doc_filter_create(qi, filter_bits.words.data(), filter_bits.num_docs, &doc_filter), "dint_doc_filter_create");
+        dint_doc_facets* doc_facets = nullptr;  // ranked_*_faceted: the run's map, and a call's rows and matches
+        if (is_faceted)
+            dint_ok(dint_doc_facets_create(0, facets_map.group_of.data(), facets_map.num_docs, facets_map.n_groups, &doc_facets), "dint_doc_facets_create");
+        const size_t n_groups = facets_map.n_groups;
+        std::vector<uint32_t> facet_rows;
+        std::vector<uint64_t> facet_matches;
         constexpr uint32_t kTopK = 10;  // ranked_and_query(wdata, 10), src/queries.cpp:106-108
         std::vector<float> top_scores;
 
@@ -247,8 +280,9 @@ int main(int argc, char** argv) {
             const bool is_ranked_or_bool = t == "ranked_or_bool" && wand;
             const bool is_or_range = t == "ranked_or_range" && wand, is_and_range = t == "ranked_and_range" && wand;
             const bool is_or_filtered = t == "ranked_or_filtered" && wand, is_and_filtered = t == "ranked_and_filtered" && wand;
+            const bool is_or_faceted = t == "ranked_or_faceted" && wand, is_and_faceted = t == "ranked_and_faceted" && wand;
             const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
-                                   is_or_range || is_and_range || is_or_filtered || is_and_filtered;
+                                   is_or_range || is_and_range || is_or_filtered || is_and_filtered || is_or_faceted || is_and_faceted;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
                 std::cerr << "Unsupported query type: " << t << std::endl;  // src/queries.cpp:108-110
                 continue;
@@ -289,6 +323,18 @@ int main(int argc, char** argv) {
                         dint_ok(dint_ranked_and_filtered_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, n, q_counts, nullptr,
                                                                  top_scores.data(), nullptr, nullptr, nullptr),
                                 "dint_ranked_and_filtered_queries");
+                } else if (is_or_faceted || is_and_faceted) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    facet_rows.resize(n * n_groups);
+                    facet_matches.resize(n);
+                    if (is_or_faceted)
+                        dint_ok(dint_ranked_or_faceted_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_facets, n, q_counts,
+                                                               facet_matches.data(), top_scores.data(), nullptr, facet_rows.data(), nullptr, nullptr),
+                                "dint_ranked_or_faceted_queries");
+                    else
+                        dint_ok(dint_ranked_and_faceted_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_facets, n, q_counts,
+                                                                facet_matches.data(), top_scores.data(), nullptr, facet_rows.data(), nullptr, nullptr),
+                                "dint_ranked_and_faceted_queries");
                 } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
@@ -313,6 +359,9 @@ int main(int argc, char** argv) {
             };
             std::vector<double> query_times;
             uint64_t total = 0, total_one_run = 0;
+            // a faceted type: per group the matches of the log's queries in it, and every match of the log (the first run's)
+            std::vector<uint64_t> facet_totals(is_faceted ? n_groups : 0, 0);
+            uint64_t all_matches = 0;
             for (size_t run = 0; run != runs; ++run) {  // op_perftest
                 for (size_t i = 0; i != queries.size(); ++i) {
                     auto const& q = queries[i];
@@ -322,6 +371,10 @@ int main(int argc, char** argv) {
                     run_queries(q.data(), offs, 1, &results, &fsum, i);
                     total += results;
                     if (run == 0) total_one_run += results;
+                    if (run == 0 && is_faceted) {
+                        all_matches += facet_matches[0];
+                        for (size_t g = 0; g != n_groups; ++g) facet_totals[g] += facet_rows[g];
+                    }
                     if (run != 0) query_times.push_back(now_us() - tick);  // first run is not timed
                 }
             }
@@ -347,6 +400,12 @@ int main(int argc, char** argv) {
                 if (batch_total != total_one_run)
                     throw std::runtime_error("the batch call counted " + std::to_string(batch_total) + " results, the one-query calls " +
                                              std::to_string(total_one_run));
+                if (is_faceted) {  // ... and count the same matches per group
+                    std::vector<uint64_t> batch_totals(n_groups, 0);
+                    for (size_t q = 0; q != queries.size(); ++q)
+                        for (size_t g = 0; g != n_groups; ++g) batch_totals[g] += facet_rows[q * n_groups + g];
+                    if (batch_totals != facet_totals) throw std::runtime_error("the batch call and the one-query calls counted other facet totals");
+                }
             }
             if (query_times.empty()) continue;
             std::sort(query_times.begin(), query_times.end());
@@ -356,8 +415,14 @@ int main(int argc, char** argv) {
             std::cout << "{\"type\": \"" << type << "\", \"query\": \"" << t << "\", \"avg\": " << avg << ", \"q50\": " << q50
                       << ", \"q90\": " << q90 << ", \"q95\": " << q95;
             if (batch_us >= 0) std::cout << ", \"batch_us_per_query\": " << batch_us;
+            if (is_faceted) {
+                std::cout << ", \"matches\": " << all_matches << ", \"n_groups\": " << n_groups << ", \"facet_totals\": [";
+                for (size_t g = 0; g != n_groups; ++g) std::cout << (g ? ", " : "") << facet_totals[g];
+                std::cout << "]";
+            }
             std::cout << ", \"device\": \"" << device_name << "\"}" << std::endl;
         }
+        dint_doc_facets_destroy(doc_facets);
         dint_doc_filter_destroy(doc_filter);
         dint_wand_data_destroy(wand);
         dint_wand_data_destroy(wand_blockmax);
