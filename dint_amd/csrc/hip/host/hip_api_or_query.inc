@@ -21,6 +21,10 @@
 // besides, and facet_count_kernel runs between the scoring launch and ranked_topk, over the pass's slots in cand; it adds
 // to the call's facet rows, cleared once per call, which come back with the last pass. Without fa nothing is planned or
 // launched differently.
+// ca (dint_ranked_or_collapsed_queries, hip_api_collapse.inc), with fa: behind facet_count_kernel, collapse_best_kernel and
+// collapse_keep_kernel over the pass's slots — a pass holds whole queries, so a query's slots are complete — and behind
+// ranked_topk collapse_hits_kernel over the pass's keys, at the pass's query offset; the table, the counters and the hits are
+// cleared once per call and come back with the last pass. Without ca nothing is planned or launched differently.
 
 // What a ranked OR call with a minimum and exclusions adds to its passes, and what it gets back.
 struct or_bool_args {
@@ -80,9 +84,11 @@ struct or_pass_query {
 // fl (with rk and d_counts, not ranged): a term record's pages are its list's live blocks, the record itself the whole
 // list's; nothing more is staged, and ranked_or_filtered_score_kernel scores, adding the matches to d_counts.
 // fa (with rk; its rows cleared): or_facet_layout staged behind the others, facet_count_kernel behind the scoring launch.
+// ca (with fa; its workspaces cleared): the two collapse launches behind that one, collapse_hits_kernel behind the selection.
 static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const ranked_args* rk, const std::vector<or_pass_query>& qs,
                        size_t min_stage, unsigned long long* d_counts, size_t n_counts, uint32_t id0, size_t n_ids, hipStream_t s,
-                       or_bool_args* xb = nullptr, bool ranged = false, const filter_args* fl = nullptr, const facet_args* fa = nullptr) {
+                       or_bool_args* xb = nullptr, bool ranged = false, const filter_args* fl = nullptr, const facet_args* fa = nullptr,
+                       const collapse_args* ca = nullptr) {
     uint64_t n_pages = 0, n_terms = 0;
     for (const or_pass_query& q : qs) {
         n_terms += q.n;
@@ -215,14 +221,17 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
         if (hipGetLastError() != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     }
     if (fa && facet_count_launch(qi, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
+    if (ca && collapse_launch(qi, ca, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     const int rst = ranked_topk(qi, *rk, page_query, n_ids, s);
-    return rst != DINT_OK ? stream_failed(s, rst) : DINT_OK;
+    if (rst != DINT_OK) return stream_failed(s, rst);
+    if (ca && collapse_hits_launch(qi, ca, fa, n_ids, id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
+    return DINT_OK;
 }
 
 static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream,
                            const ranked_args* rk = nullptr, or_bool_args* xb = nullptr, range_args* rg = nullptr,
-                           filter_args* fl = nullptr, facet_args* fa = nullptr) {
+                           filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -245,6 +254,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         fl->h_matches.assign(n_queries, 0ull);
     }
     facet_rows_begin(fa, n_queries);
+    collapse_begin(ca, n_queries);
     if (op.all == 0) return DINT_OK;
 
     std::lock_guard<std::mutex> lock(qi->mutex);
@@ -252,6 +262,10 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (fa) {
         const int cleared = facet_rows_clear(qi, fa, n_queries, s);
+        if (cleared != DINT_OK) return cleared;
+    }
+    if (ca) {
+        const int cleared = collapse_clear(qi, ca, fa, n_queries, s);
         if (cleared != DINT_OK) return cleared;
     }
     // the call's counters: counts[n_queries] then freq sums[n_queries], cleared once, added to by every pass
@@ -279,10 +293,11 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         ranked_args pass_rk = rk ? *rk : ranked_args{};
         if (rk) pass_rk.keys += uint64_t(q0) * rk->k;  // (the keys of the pass's queries at their own offset)
         const int st = or_run_pass(qi, freqs_dict, rk ? &pass_rk : nullptr, qs, 2 * n_queries * sizeof(unsigned long long), d_counts,
-                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl, fa);
+                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl, fa, ca);
         if (st != DINT_OK) return st;
     }
     if (fa && facet_rows_back(fa, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
+    if (ca && collapse_back(ca, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (fl) HIP_TRY(hipMemcpyAsync(fl->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (rg) HIP_TRY(hipMemcpyAsync(rg->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (xb) HIP_TRY(hipMemcpyAsync(xb->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));

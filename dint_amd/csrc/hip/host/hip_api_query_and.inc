@@ -18,7 +18,7 @@ struct bool_steps {
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split = true,
                             const ranked_args* rk = nullptr, bool_steps* extra = nullptr, range_args* rg = nullptr,
-                            filter_args* fl = nullptr, facet_args* fa = nullptr);
+                            filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr);
 
 // One AND call: what its stages share.
 struct and_call {
@@ -29,6 +29,7 @@ struct and_call {
     range_args* rg = nullptr;               // a ranged call: candidates from the rarest list's blocks in range, the others killed
     filter_args* fl = nullptr;              // a filtered call: candidates from the rarest list's live blocks, the others killed
     facet_args* fa = nullptr;               // a faceted call (ranked): the survivors' groups counted in front of the selection
+    collapse_args* ca = nullptr;            // a collapsed call (with fa): of every group only the best survivor is selected from
     size_t n_queries = 0;
     uint64_t* counts = nullptr;
     hipStream_t s = nullptr;
@@ -507,7 +508,9 @@ static int and_batch_rounds(and_call& c, bool searched0, unsigned long long* hos
 // rk (ranked_and): a score per candidate slot, from 0.0f, summed by ranked_gather_kernel; then ranked_topk.
 // c.extra (ranked_bool): the optional terms' steps between the two; without it the launches are what they were.
 // c.fa (with rk): the facet rows cleared, then facet_count_kernel over the survivors in cand directly in front of
-// ranked_topk; the rows travel to the host with the sums. ----
+// ranked_topk; the rows travel to the host with the sums.
+// c.ca (with c.fa): its workspaces cleared, collapse_best_kernel and collapse_keep_kernel behind facet_count_kernel — the
+// call is one pass, so every query's slots are complete — and collapse_hits_kernel behind ranked_topk. ----
 static int and_freqs_pass(and_call& c) {
     dint_query_index* qi = c.qi;
     const size_t n_queries = c.n_queries, n_terms = c.rounds + 1;
@@ -569,8 +572,18 @@ static int and_freqs_pass(and_call& c) {
         if (st == DINT_OK) st = facet_count_launch(qi, c.fa, c.n_pages, c.d_page_query, 0u, c.s);
         if (st != DINT_OK) return c.failed(st);
     }
+    if (rk && c.fa && c.ca) {
+        int st = collapse_clear(qi, c.ca, c.fa, n_queries, c.s);
+        if (st == DINT_OK) st = collapse_launch(qi, c.ca, c.fa, c.n_pages, c.d_page_query, 0u, c.s);
+        if (st != DINT_OK) return c.failed(st);
+    }
     if (rk) {
         const int st = ranked_topk(qi, *rk, c.page_query, n_queries, c.s);
+        if (st != DINT_OK) return c.failed(st);
+    }
+    if (rk && c.fa && c.ca) {
+        int st = collapse_hits_launch(qi, c.ca, c.fa, n_queries, 0u, c.s);
+        if (st == DINT_OK) st = collapse_back(c.ca, n_queries, c.s);
         if (st != DINT_OK) return c.failed(st);
     }
     if (rk && c.fa && facet_rows_back(c.fa, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
@@ -603,7 +616,8 @@ static int and_copy_back(and_call& c, uint64_t* freq_sums, uint64_t* freq_blocks
 // tails or batch rounds — then, with a freqs dictionary, the freqs / ranked pass, and the copy back.
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split,
-                            const ranked_args* rk, bool_steps* extra, range_args* rg, filter_args* fl, facet_args* fa) {
+                            const ranked_args* rk, bool_steps* extra, range_args* rg, filter_args* fl, facet_args* fa,
+                            collapse_args* ca) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -616,6 +630,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     c.rg = rg;
     c.fl = fl;
     c.fa = fa;
+    c.ca = ca;
     c.n_queries = n_queries;
     c.counts = counts;
     c.s = static_cast<hipStream_t>(stream);
@@ -625,6 +640,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     if (rg) rg->blocks = c.n_pages;
     if (fl) fl->blocks = c.n_pages;
     facet_rows_begin(fa, n_queries);
+    collapse_begin(ca, n_queries);
     if (c.n_pages == 0) return DINT_OK;
     bool mixed = false;
     const int split = may_split ? and_mixed_split(c, stream, &mixed) : DINT_OK;

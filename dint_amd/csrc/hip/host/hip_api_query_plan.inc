@@ -133,12 +133,12 @@ struct dint_doc_facets {
 struct facet_args {
     const dint_doc_facets* facets = nullptr;
     uint32_t* d_rows = nullptr;  // (set by facet_rows_clear)
-    uint32_t* h_rows = nullptr;  // the caller's facet_counts
+    uint32_t* h_rows = nullptr;  // the caller's facet_counts (a collapsed call: null where the caller asks for no rows)
     size_t words(size_t n_queries) const { return n_queries * size_t(facets->n_groups); }
 };
 // the call is planned and has refused nothing: every row is zero until a pass says otherwise
 static void facet_rows_begin(const facet_args* fa, size_t n_queries) {
-    if (fa) std::fill(fa->h_rows, fa->h_rows + fa->words(n_queries), 0u);
+    if (fa && fa->h_rows) std::fill(fa->h_rows, fa->h_rows + fa->words(n_queries), 0u);
 }
 // under the index's lock, once per call, in front of its first counting launch
 static int facet_rows_clear(dint_query_index* qi, facet_args* fa, size_t n_queries, hipStream_t s) {
@@ -156,7 +156,71 @@ static int facet_count_launch(const dint_query_index* qi, const facet_args* fa, 
 }
 // ... and the rows' way back, on the stream, in front of the call's last wait
 static int facet_rows_back(const facet_args* fa, size_t n_queries, hipStream_t s) {
+    if (!fa->h_rows) return DINT_OK;  // (a collapsed call that keeps its rows on the device)
     HIP_TRY(hipMemcpyAsync(fa->h_rows, fa->d_rows, fa->words(n_queries) * 4, hipMemcpyDeviceToHost, s));
+    return DINT_OK;
+}
+
+// A collapsed call (hip_api_collapse.inc): a faceted call — it needs fa, whose rows and staged page -> query table it
+// reuses — that lets only the best document of every group into the selection. Its workspaces are the query index's, sized
+// and cleared once per call (collapse_clear): the table of best keys, 8 bytes per (query, group), the survivors' counters,
+// and the hits' groups and group matches, n_queries * k words each; per pass the slots' groups. Where a call takes a null
+// one nothing is planned or launched differently.
+struct collapse_args {
+    uint32_t k = 0;
+    uint32_t *h_hit_groups = nullptr, *h_hit_group_matches = nullptr;  // the caller's, n_queries * k each
+    std::vector<unsigned long long> h_collapsed;                       // per query: the kept documents
+    unsigned long long *d_best = nullptr, *d_collapsed = nullptr;      // (set by collapse_clear)
+    uint32_t *d_hit_groups = nullptr, *d_hit_group_matches = nullptr;
+};
+// the call is planned and has refused nothing: no query has kept a document or has a hit until a pass says otherwise
+static void collapse_begin(collapse_args* ca, size_t n_queries) {
+    if (!ca) return;
+    ca->h_collapsed.assign(n_queries, 0ull);
+    std::fill(ca->h_hit_groups, ca->h_hit_groups + n_queries * ca->k, kFacetNone);
+    std::fill(ca->h_hit_group_matches, ca->h_hit_group_matches + n_queries * ca->k, 0u);
+}
+// under the index's lock, once per call, in front of its first launch: the table (a live key is never 0) and the counters
+// zero, every hit in no group with no matches
+static int collapse_clear(dint_query_index* qi, collapse_args* ca, const facet_args* fa, size_t n_queries, hipStream_t s) {
+    const size_t n_best = fa->words(n_queries), n_hits = n_queries * ca->k;
+    if (!qi->collapse_best.ensure(n_best + n_queries) || !qi->collapse_hits.ensure(2 * n_hits)) return DINT_ERR_HIP;
+    ca->d_best = qi->collapse_best.p;
+    ca->d_collapsed = ca->d_best + n_best;
+    ca->d_hit_groups = qi->collapse_hits.p;
+    ca->d_hit_group_matches = ca->d_hit_groups + n_hits;
+    HIP_TRY(hipMemsetAsync(ca->d_best, 0, (n_best + n_queries) * sizeof(unsigned long long), s));
+    HIP_TRY(hipMemsetAsync(ca->d_hit_groups, 0xFF, n_hits * 4, s));
+    HIP_TRY(hipMemsetAsync(ca->d_hit_group_matches, 0, n_hits * 4, s));
+    return DINT_OK;
+}
+// collapse_best_kernel and collapse_keep_kernel over the n_pages pages of qi->cand, behind facet_count_launch (the rows
+// count every match) and in front of ranked_topk; d_page_query[page] + q0: the page's query of the call
+static int collapse_launch(dint_query_index* qi, const collapse_args* ca, const facet_args* fa, uint64_t n_pages,
+                           const uint32_t* d_page_query, uint32_t q0, hipStream_t s) {
+    const uint64_t n_slots = n_pages * kPageSlots;
+    if (!qi->collapse_slot_group.ensure(n_slots)) return DINT_ERR_HIP;
+    const doc_facets_view f = fa->facets->view();
+    hipLaunchKernelGGL(collapse_best_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, qi->slot_score.p, n_slots,
+                       d_page_query, q0, f, ca->d_best, qi->collapse_slot_group.p);
+    hipLaunchKernelGGL(collapse_keep_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, qi->slot_score.p,
+                       qi->collapse_slot_group.p, n_slots, d_page_query, q0, f.n_groups, ca->d_best, ca->d_collapsed);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// collapse_hits_kernel behind ranked_topk, over the keys it selected for the n_ids queries from q0 on (qi->topk_out)
+static int collapse_hits_launch(const dint_query_index* qi, const collapse_args* ca, const facet_args* fa, size_t n_ids, uint32_t q0,
+                                hipStream_t s) {
+    const uint64_t n_out = uint64_t(n_ids) * ca->k;
+    hipLaunchKernelGGL(collapse_hits_kernel, dim3(uint32_t((n_out + 255) / 256)), dim3(256), 0, s, qi->topk_out.p, uint32_t(n_ids), ca->k, q0,
+                       fa->facets->view(), fa->d_rows, ca->d_hit_groups, ca->d_hit_group_matches);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// ... and the counters' and the hits' way back, on the stream, in front of the call's last wait
+static int collapse_back(collapse_args* ca, size_t n_queries, hipStream_t s) {
+    const size_t n_hits = n_queries * ca->k;
+    HIP_TRY(hipMemcpyAsync(ca->h_collapsed.data(), ca->d_collapsed, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ca->h_hit_groups, ca->d_hit_groups, n_hits * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ca->h_hit_group_matches, ca->d_hit_group_matches, n_hits * 4, hipMemcpyDeviceToHost, s));
     return DINT_OK;
 }
 

@@ -69,6 +69,10 @@ struct dint_query_index {
     device_buffer<uint32_t> q_ranges;
     // the faceted ranked calls (hip_api_facets.inc): per query of the call a row of n_groups counters
     device_buffer<uint32_t> facet_rows;
+    // the collapsed ranked calls (hip_api_collapse.inc): per (query, group) of the call the best key and behind them per
+    // query the kept documents; per slot of a pass its group; per (query, i) the hit's group, then its group's matches
+    device_buffer<unsigned long long> collapse_best;
+    device_buffer<uint32_t> collapse_slot_group, collapse_hits;
     // dint_check_index (hip_api_check.inc): every block of a list but its last holds 256 postings (the in-index layout:
     // block j of a list is its positions [256 j, 256 j + n)); two pinned staging buffers of a pass's expected postings
     // and their device copies, alternating

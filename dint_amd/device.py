@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "dint_doc_filter_create", "dint_doc_filter_info_get", "dint_doc_filter_destroy", "dint_ranked_or_filtered_queries", "dint_ranked_and_filtered_queries",
     "dint_doc_facets_create", "dint_doc_facets_info_get", "dint_doc_facets_group_sizes", "dint_doc_facets_destroy",
     "dint_ranked_or_faceted_queries", "dint_ranked_and_faceted_queries",
+    "dint_ranked_or_collapsed_queries", "dint_ranked_and_collapsed_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_check_index", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -177,6 +178,8 @@ def _load():
     lib.dint_doc_facets_destroy.restype = None
     lib.dint_ranked_or_faceted_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_and_faceted_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_or_collapsed_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_collapsed_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
@@ -808,6 +811,46 @@ class QueryIndex:
         """ranked_and_filtered_queries with the matches counted per document group (dint_ranked_and_faceted_queries):
         arguments and outputs as ranked_or_faceted_queries, over the intersection."""
         return self._ranked_faceted("dint_ranked_and_faceted_queries", freqs_dict, wand, queries, facets, filter, k, with_stats)
+
+    def _ranked_collapsed(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, facets, doc_filter, k: int, with_stats: bool,
+                          with_rows: bool):
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        collapsed = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        hit_groups = np.zeros((n, k), dtype=np.uint32)
+        hit_group_matches = np.zeros((n, k), dtype=np.uint32)
+        rows = np.zeros((n, facets.n_groups), dtype=np.uint32) if with_rows else None
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 doc_filter._h if doc_filter is not None else None, facets._h, n, counts.ctypes.data,
+                                 matches.ctypes.data, collapsed.ctypes.data, scores.ctypes.data, docids.ctypes.data,
+                                 hit_groups.ctypes.data, hit_group_matches.ctypes.data, rows.ctypes.data if with_rows else None,
+                                 C.byref(blocks), self._stream()), fn)
+        out = (counts, scores, docids, matches, blocks.value) if with_stats else (counts, scores, docids)
+        out += (collapsed, hit_groups, hit_group_matches)
+        return out + (rows,) if with_rows else out
+
+    def ranked_or_collapsed_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, facets: "DocFacets", filter=None,
+                                    k: int = 10, with_stats: bool = False, with_rows: bool = False):
+        """ranked_or_faceted_queries with at most one hit per document group (dint_ranked_or_collapsed_queries, DESIGN.md
+        4d-collapse): of every group a query matches only the match with the best key (higher score, then smaller docID) is
+        kept, a match in no group stands for itself, and the top k of the kept documents are returned. Arguments as the
+        faceted method takes them -> (counts, scores, docids) — with_stats: (counts, scores, docids, matches, blocks_decoded),
+        matches and blocks_decoded the faceted call's — and behind them collapsed u64[n] (the kept documents: groups with a
+        match plus ungrouped matches; counts = min(collapsed, k)), hit_groups u32[n, k] (FACET_NONE for an ungrouped hit and
+        past the count), hit_group_matches u32[n, k] (the query's matches in the hit's group, 1 for an ungrouped hit, 0 past
+        the count); with_rows: the faceted call's rows u32[n, n_groups] last."""
+        return self._ranked_collapsed("dint_ranked_or_collapsed_queries", freqs_dict, wand, queries, facets, filter, k, with_stats, with_rows)
+
+    def ranked_and_collapsed_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, facets: "DocFacets", filter=None,
+                                     k: int = 10, with_stats: bool = False, with_rows: bool = False):
+        """ranked_and_faceted_queries with at most one hit per document group (dint_ranked_and_collapsed_queries): arguments
+        and outputs as ranked_or_collapsed_queries, over the intersection."""
+        return self._ranked_collapsed("dint_ranked_and_collapsed_queries", freqs_dict, wand, queries, facets, filter, k, with_stats, with_rows)
 
     def ranked_or_maxscore_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10):
         """ranked_or_queries' answer, bit for bit, with MaxScore's pruning: the blocks of low-weight

@@ -701,7 +701,8 @@ int dint_ranked_and_filtered_queries(dint_query_index* qi, const dint_dict* freq
  * workspace of the query index (4 bytes * n_queries * n_groups, grow-only), cleared once per call. Terms, query_offsets,
  * the handle's lock and the stream are as for the filtered calls; besides their launches a call runs one counting launch
  * per OR pass / per AND call, which reads the candidate slots once more. Facets on the other query
- * forms, several maps per call, score sums and the best document per group are out of scope. */
+ * forms, several maps per call and score sums are out of scope; the best document per group: the collapsed
+ * calls below. */
 #define DINT_FACET_NONE 0xFFFFFFFFu   /* a document in no group */
 #define DINT_FACETS_MAX_GROUPS 65536u
 typedef struct dint_doc_facets dint_doc_facets;
@@ -722,6 +723,46 @@ int dint_ranked_and_faceted_queries(dint_query_index* qi, const dint_dict* freqs
                                     const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
                                     const dint_doc_facets* facets, size_t n_queries, uint64_t* counts, uint64_t* matches, float* scores,
                                     uint32_t* docids, uint32_t* facet_counts, uint64_t* blocks_decoded, void* stream);
+
+/* ---- collapsed ranked queries (the best document of every document group) ------------------------------------------
+ * Adds: what a cursor engine computes with a collapsing collector in place of its top-k collector (ranked_or_query /
+ * ranked_and_query, include/ds2i/queries.hpp:309-457, have none) — at most one hit per group of documents (a site, a
+ * product, a thread): the k best GROUPS of every query, each shown by its best document, for a batch of queries, in the call
+ * that ranks them. One filtered call per group answers the same and decodes and scores everything once per group; fetching
+ * more than k hits and collapsing on the host is wrong as soon as one group holds more than the over-fetch.
+ * A document's key is the one the selection sorts by: the score's bits, then the inverted docID — a higher score wins, equal
+ * scores go to the smaller docID. A query's KEPT documents are, for every group with at least one match, the match of that
+ * group with the largest key, and every match that is in no group (DINT_FACET_NONE, or a docID at or past the map's
+ * num_docs): such a document stands for itself. Arguments as the faceted calls take them; the outputs (HOST):
+ *   counts, scores, docids  the top k of the kept documents in key order, filled as the other ranked calls fill them
+ *                           (0.0f / 0xFFFFFFFF past the count); every kept hit carries exactly the score the unfiltered
+ *                           call gives that document
+ *   matches[q]              (nullable) every match, exactly as the faceted call reports it
+ *   collapsed[q]            the kept documents: groups with a match plus ungrouped matches; counts[q] = min(collapsed[q], k)
+ *   hit_groups[q * k + i]   the group of hit i, DINT_FACET_NONE for an ungrouped hit and past the count
+ *   hit_group_matches[q * k + i]  the matches of query q in that group (the faceted row's entry), 1 for an ungrouped hit,
+ *                           0 past the count
+ *   facet_counts            (nullable, n_queries * n_groups words) the faceted call's rows, bit for bit; the rows are counted
+ *                           on the device either way and copied only when asked for
+ *   *blocks_decoded         (nullable) the filtered / faceted call's value
+ * The reduction is a 64-bit maximum per (query, group): order-independent, so the answer is exact and the same from run to
+ * run (a float sum per group would not be: score sums stay out).
+ * DINT_ERR_ARG, before anything is written or launched: whatever the faceted calls refuse except a null facet_counts; a null
+ * collapsed, hit_groups or hit_group_matches; n_queries * n_groups > 2^27 — the per-call table of best keys is 8 BYTES PER
+ * (QUERY, GROUP), a grow-only workspace of the query index cleared once per call, so this is 1 GiB; the caller batches.
+ * Besides the faceted call's launches a call runs two launches over the candidate slots in front of the selection and one
+ * over the selected keys behind it, per OR pass / per AND call. Several hits per group, collapsing
+ * on the boolean and pruned forms and search_after paging are out of scope. */
+int dint_ranked_or_collapsed_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                     const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                     const dint_doc_facets* facets, size_t n_queries, uint64_t* counts, uint64_t* matches,
+                                     uint64_t* collapsed, float* scores, uint32_t* docids, uint32_t* hit_groups,
+                                     uint32_t* hit_group_matches, uint32_t* facet_counts, uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_collapsed_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                      const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                      const dint_doc_facets* facets, size_t n_queries, uint64_t* counts, uint64_t* matches,
+                                      uint64_t* collapsed, float* scores, uint32_t* docids, uint32_t* hit_groups,
+                                      uint32_t* hit_group_matches, uint32_t* facet_counts, uint64_t* blocks_decoded, void* stream);
 
 /* ---- the wand data's BM25 maxima from the index, on the device; block maxima for the pruned call --------------
  * Replaces: the max_term_weight half of wand_data's constructor (include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp),

@@ -4,7 +4,7 @@
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
 //   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
 //               ranked_or_bool | ranked_or_range | ranked_and_range | ranked_or_filtered | ranked_and_filtered |
-//               ranked_or_faceted | ranked_and_faceted, several separated by ':'
+//               ranked_or_faceted | ranked_and_faceted | ranked_or_collapsed | ranked_and_collapsed, several separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
@@ -37,6 +37,12 @@
 //               faceted type without --facets is a usage error; also only with a wand file; the query lines, output and
 //               keys are ranked_or's, and the JSON line carries besides "matches" (every match of the log),
 //               "n_groups" and "facet_totals" (per group, the matches of the log's queries in it);
+//               ranked_or_collapsed / ranked_and_collapsed (dint_ranked_or_collapsed_queries, dint_ranked_and_collapsed_queries:
+//               of every document group a query matches only its best document is ranked) take
+//               --facets FILE and --filter FILE as the faceted types do, and each must be the only type of its run; the
+//               result counts are the hits (at most 10 groups a query), and the JSON line carries besides "matches" (every
+//               match of the log), "collapsed" (the kept documents of the log's queries: groups with a match plus
+//               ungrouped matches) and "n_groups";
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -117,20 +123,22 @@ int main(int argc, char** argv) {
             std::cerr << query_type << " needs --filter FILE (every line a docID d or an interval lo:hi)" << std::endl;
             return 1;
         }
+        const bool is_collapsed = query_type == "ranked_or_collapsed" || query_type == "ranked_and_collapsed";
         const bool is_faceted = query_type == "ranked_or_faceted" || query_type == "ranked_and_faceted";
-        for (const char* faceted : {"ranked_or_faceted", "ranked_and_faceted"})
-            if (!is_faceted && (":" + query_type + ":").find(std::string(":") + faceted + ":") != std::string::npos)
+        const bool needs_facets = is_faceted || is_collapsed;  // the types that answer under the map of --facets
+        for (const char* faceted : {"ranked_or_faceted", "ranked_and_faceted", "ranked_or_collapsed", "ranked_and_collapsed"})
+            if (!needs_facets && (":" + query_type + ":").find(std::string(":") + faceted + ":") != std::string::npos)
                 throw std::runtime_error(std::string(faceted) + " answers its whole log under --facets: it must be the only query type of a run");
-        if (is_faceted && !facets_filename) {
+        if (needs_facets && !facets_filename) {
             std::cerr << query_type << " needs --facets FILE (every line `d g` or `lo:hi g`: document d, or every document of [lo, hi), is in group g)"
                       << std::endl;
             return 1;
         }
-        if (!is_faceted && facets_filename) throw std::runtime_error("--facets goes with ranked_or_faceted or ranked_and_faceted only");
-        if (!is_filtered && !is_faceted && filter_filename)
-            throw std::runtime_error("--filter goes with ranked_or_filtered, ranked_and_filtered, ranked_or_faceted or ranked_and_faceted only");
+        if (!needs_facets && facets_filename) throw std::runtime_error("--facets goes with the ranked_*_faceted and ranked_*_collapsed types only");
+        if (!is_filtered && !needs_facets && filter_filename)
+            throw std::runtime_error("--filter goes with the ranked_*_filtered, ranked_*_faceted and ranked_*_collapsed types only");
         tool::doc_facets_map facets_map;
-        if (is_faceted) {
+        if (needs_facets) {
             std::ifstream ff(facets_filename);
             if (!ff) throw std::runtime_error(std::string("could not open the facets file ") + facets_filename);
             facets_map = tool::parse_doc_facets(ff);
@@ -257,11 +265,15 @@ int main(int argc, char** argv) {
         dint_doc_filter* doc_filter = nullptr;  // ranked_*_filtered: the run's filter
         if (filter_filename) dint_ok(dint_doc_filter_create(qi, filter_bits.words.data(), filter_bits.num_docs, &doc_filter), "dint_doc_filter_create");
         dint_doc_facets* doc_facets = nullptr;  // ranked_*_faceted: the run's map, and a call's rows and matches
-        if (is_faceted)
+        if (needs_facets)
             dint_ok(dint_doc_facets_create(0, facets_map.group_of.data(), facets_map.num_docs, facets_map.n_groups, &doc_facets), "dint_doc_facets_create");
         const size_t n_groups = facets_map.n_groups;
         std::vector<uint32_t> facet_rows;
         std::vector<uint64_t> facet_matches;
+        // ranked_*_collapsed: a call's kept documents; its hits' groups and group matches are outputs the ABI requires, and
+        // the tool, which prints totals, does not read them
+        std::vector<uint64_t> collapsed_counts;
+        std::vector<uint32_t> hit_groups, hit_group_matches;
         constexpr uint32_t kTopK = 10;  // ranked_and_query(wdata, 10), src/queries.cpp:106-108
         std::vector<float> top_scores;
 
@@ -281,8 +293,10 @@ int main(int argc, char** argv) {
             const bool is_or_range = t == "ranked_or_range" && wand, is_and_range = t == "ranked_and_range" && wand;
             const bool is_or_filtered = t == "ranked_or_filtered" && wand, is_and_filtered = t == "ranked_and_filtered" && wand;
             const bool is_or_faceted = t == "ranked_or_faceted" && wand, is_and_faceted = t == "ranked_and_faceted" && wand;
+            const bool is_or_collapsed = t == "ranked_or_collapsed" && wand, is_and_collapsed = t == "ranked_and_collapsed" && wand;
             const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
-                                   is_or_range || is_and_range || is_or_filtered || is_and_filtered || is_or_faceted || is_and_faceted;
+                                   is_or_range || is_and_range || is_or_filtered || is_and_filtered || is_or_faceted || is_and_faceted ||
+                                   is_or_collapsed || is_and_collapsed;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
                 std::cerr << "Unsupported query type: " << t << std::endl;  // src/queries.cpp:108-110
                 continue;
@@ -335,6 +349,22 @@ int main(int argc, char** argv) {
                         dint_ok(dint_ranked_and_faceted_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_facets, n, q_counts,
                                                                 facet_matches.data(), top_scores.data(), nullptr, facet_rows.data(), nullptr, nullptr),
                                 "dint_ranked_and_faceted_queries");
+                } else if (is_or_collapsed || is_and_collapsed) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    facet_matches.resize(n);
+                    collapsed_counts.resize(n);
+                    hit_groups.resize(n * kTopK);
+                    hit_group_matches.resize(n * kTopK);
+                    if (is_or_collapsed)
+                        dint_ok(dint_ranked_or_collapsed_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_facets, n, q_counts,
+                                                                 facet_matches.data(), collapsed_counts.data(), top_scores.data(), nullptr,
+                                                                 hit_groups.data(), hit_group_matches.data(), nullptr, nullptr, nullptr),
+                                "dint_ranked_or_collapsed_queries");
+                    else
+                        dint_ok(dint_ranked_and_collapsed_queries(qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_facets, n, q_counts,
+                                                                  facet_matches.data(), collapsed_counts.data(), top_scores.data(), nullptr,
+                                                                  hit_groups.data(), hit_group_matches.data(), nullptr, nullptr, nullptr),
+                                "dint_ranked_and_collapsed_queries");
                 } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
@@ -361,7 +391,7 @@ int main(int argc, char** argv) {
             uint64_t total = 0, total_one_run = 0;
             // a faceted type: per group the matches of the log's queries in it, and every match of the log (the first run's)
             std::vector<uint64_t> facet_totals(is_faceted ? n_groups : 0, 0);
-            uint64_t all_matches = 0;
+            uint64_t all_matches = 0, all_collapsed = 0;  // (a collapsed type: every kept document of the log besides)
             for (size_t run = 0; run != runs; ++run) {  // op_perftest
                 for (size_t i = 0; i != queries.size(); ++i) {
                     auto const& q = queries[i];
@@ -371,9 +401,10 @@ int main(int argc, char** argv) {
                     run_queries(q.data(), offs, 1, &results, &fsum, i);
                     total += results;
                     if (run == 0) total_one_run += results;
-                    if (run == 0 && is_faceted) {
+                    if (run == 0 && needs_facets) {
                         all_matches += facet_matches[0];
-                        for (size_t g = 0; g != n_groups; ++g) facet_totals[g] += facet_rows[g];
+                        if (is_collapsed) all_collapsed += collapsed_counts[0];
+                        for (size_t g = 0; g != facet_totals.size(); ++g) facet_totals[g] += facet_rows[g];
                     }
                     if (run != 0) query_times.push_back(now_us() - tick);  // first run is not timed
                 }
@@ -400,7 +431,12 @@ int main(int argc, char** argv) {
                 if (batch_total != total_one_run)
                     throw std::runtime_error("the batch call counted " + std::to_string(batch_total) + " results, the one-query calls " +
                                              std::to_string(total_one_run));
-                if (is_faceted) {  // ... and count the same matches per group
+                if (is_collapsed) {  // ... and keep the same documents
+                    uint64_t batch_matches = 0, batch_collapsed = 0;
+                    for (size_t q = 0; q != queries.size(); ++q) batch_matches += facet_matches[q], batch_collapsed += collapsed_counts[q];
+                    if (batch_matches != all_matches || batch_collapsed != all_collapsed)
+                        throw std::runtime_error("the batch call and the one-query calls counted other matches or kept other documents");
+                } else if (is_faceted) {  // ... and count the same matches per group
                     std::vector<uint64_t> batch_totals(n_groups, 0);
                     for (size_t q = 0; q != queries.size(); ++q)
                         for (size_t g = 0; g != n_groups; ++g) batch_totals[g] += facet_rows[q * n_groups + g];
@@ -415,7 +451,9 @@ int main(int argc, char** argv) {
             std::cout << "{\"type\": \"" << type << "\", \"query\": \"" << t << "\", \"avg\": " << avg << ", \"q50\": " << q50
                       << ", \"q90\": " << q90 << ", \"q95\": " << q95;
             if (batch_us >= 0) std::cout << ", \"batch_us_per_query\": " << batch_us;
-            if (is_faceted) {
+            if (is_collapsed) {
+                std::cout << ", \"matches\": " << all_matches << ", \"collapsed\": " << all_collapsed << ", \"n_groups\": " << n_groups;
+            } else if (is_faceted) {
                 std::cout << ", \"matches\": " << all_matches << ", \"n_groups\": " << n_groups << ", \"facet_totals\": [";
                 for (size_t g = 0; g != n_groups; ++g) std::cout << (g ? ", " : "") << facet_totals[g];
                 std::cout << "]";
