@@ -18,7 +18,8 @@ struct bool_steps {
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split = true,
                             const ranked_args* rk = nullptr, bool_steps* extra = nullptr, range_args* rg = nullptr,
-                            filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr);
+                            filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr,
+                            page_args* pg = nullptr);
 
 // One AND call: what its stages share.
 struct and_call {
@@ -30,6 +31,7 @@ struct and_call {
     filter_args* fl = nullptr;              // a filtered call: candidates from the rarest list's live blocks, the others killed
     facet_args* fa = nullptr;               // a faceted call (ranked): the survivors' groups counted in front of the selection
     collapse_args* ca = nullptr;            // a collapsed call (with fa): of every group only the best survivor is selected from
+    page_args* pg = nullptr;                // a paged call (ranked): only the survivors after every query's cursor are selected from
     size_t n_queries = 0;
     uint64_t* counts = nullptr;
     hipStream_t s = nullptr;
@@ -510,7 +512,9 @@ static int and_batch_rounds(and_call& c, bool searched0, unsigned long long* hos
 // c.fa (with rk): the facet rows cleared, then facet_count_kernel over the survivors in cand directly in front of
 // ranked_topk; the rows travel to the host with the sums.
 // c.ca (with c.fa): its workspaces cleared, collapse_best_kernel and collapse_keep_kernel behind facet_count_kernel — the
-// call is one pass, so every query's slots are complete — and collapse_hits_kernel behind ranked_topk. ----
+// call is one pass, so every query's slots are complete — and collapse_hits_kernel behind ranked_topk.
+// c.pg (with rk): its keys sent and its counters cleared, then page_after_kernel directly in front of ranked_topk, behind the
+// collapse launches where there are any; the counters travel to the host with the sums. ----
 static int and_freqs_pass(and_call& c) {
     dint_query_index* qi = c.qi;
     const size_t n_queries = c.n_queries, n_terms = c.rounds + 1;
@@ -577,6 +581,11 @@ static int and_freqs_pass(and_call& c) {
         if (st == DINT_OK) st = collapse_launch(qi, c.ca, c.fa, c.n_pages, c.d_page_query, 0u, c.s);
         if (st != DINT_OK) return c.failed(st);
     }
+    if (rk && c.pg) {
+        int st = page_begin_device(qi, c.pg, n_queries, c.s);
+        if (st == DINT_OK) st = page_after_launch(qi, c.pg, c.n_pages, c.d_page_query, 0u, c.s);
+        if (st != DINT_OK) return c.failed(st);
+    }
     if (rk) {
         const int st = ranked_topk(qi, *rk, c.page_query, n_queries, c.s);
         if (st != DINT_OK) return c.failed(st);
@@ -587,6 +596,7 @@ static int and_freqs_pass(and_call& c) {
         if (st != DINT_OK) return c.failed(st);
     }
     if (rk && c.fa && facet_rows_back(c.fa, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
+    if (rk && c.pg && page_back(c.pg, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
     c.h_sums.resize(n_queries);
     HIP_TRY(hipMemcpyAsync(c.h_sums.data(), qi->freq_sums.p, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.s));
     c.h_freq_counts.resize(n_terms);
@@ -617,7 +627,7 @@ static int and_copy_back(and_call& c, uint64_t* freq_sums, uint64_t* freq_blocks
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split,
                             const ranked_args* rk, bool_steps* extra, range_args* rg, filter_args* fl, facet_args* fa,
-                            collapse_args* ca) {
+                            collapse_args* ca, page_args* pg) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -631,6 +641,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     c.fl = fl;
     c.fa = fa;
     c.ca = ca;
+    c.pg = pg;
     c.n_queries = n_queries;
     c.counts = counts;
     c.s = static_cast<hipStream_t>(stream);
@@ -641,6 +652,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     if (fl) fl->blocks = c.n_pages;
     facet_rows_begin(fa, n_queries);
     collapse_begin(ca, n_queries);
+    page_begin(pg, n_queries);
     if (c.n_pages == 0) return DINT_OK;
     bool mixed = false;
     const int split = may_split ? and_mixed_split(c, stream, &mixed) : DINT_OK;

@@ -224,6 +224,45 @@ static int collapse_back(collapse_args* ca, size_t n_queries, hipStream_t s) {
     return DINT_OK;
 }
 
+// A paged call (hip_api_paging.inc): per query of the call a cursor key — the selection's key (collapse_key) of the last hit
+// the caller has seen, kPageFromStart for a query read from the start, 0 where nothing lies after the cursor — and what the
+// call reports besides its answer: per query the matches (a collapsed call: the kept documents) that are NOT after the
+// cursor. The keys and the counters are a grow-only workspace of the query index, n_queries words each, uploaded and
+// cleared once per call under the lock (page_begin_device); page_after_kernel runs directly in front of ranked_topk, behind
+// the collapse launches where there are any. Where a call takes a null one nothing is planned or launched differently.
+struct page_args {
+    std::vector<unsigned long long> keys;       // per query: the cursor's key
+    std::vector<unsigned long long> h_skipped;  // out: per query (a query the call did not run: 0)
+    unsigned long long *d_keys = nullptr, *d_skipped = nullptr;  // (set by page_begin_device)
+};
+// the call is planned and has refused nothing: no query has skipped a match until a pass says otherwise
+static void page_begin(page_args* pg, size_t n_queries) {
+    if (pg) pg->h_skipped.assign(n_queries, 0ull);
+}
+// under the index's lock, once per call, in front of its first page_after_kernel launch: the keys go up, the counters clear
+static int page_begin_device(dint_query_index* qi, page_args* pg, size_t n_queries, hipStream_t s) {
+    if (!qi->page_keys.ensure(2 * n_queries)) return DINT_ERR_HIP;
+    pg->d_keys = qi->page_keys.p;
+    pg->d_skipped = pg->d_keys + n_queries;
+    // (pageable host memory: the copy has left pg->keys when the call returns, and the call waits on the stream before it does)
+    HIP_TRY(hipMemcpyAsync(pg->d_keys, pg->keys.data(), n_queries * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(pg->d_skipped, 0, n_queries * sizeof(unsigned long long), s));
+    return DINT_OK;
+}
+// page_after_kernel over the n_pages pages of qi->cand, directly in front of ranked_topk; d_page_query[page] + q0: the
+// page's query of the call
+static int page_after_launch(const dint_query_index* qi, const page_args* pg, uint64_t n_pages, const uint32_t* d_page_query, uint32_t q0,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(page_after_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, qi->slot_score.p, n_pages * kPageSlots,
+                       d_page_query, q0, pg->d_keys, pg->d_skipped);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// ... and the counters' way back, on the stream, in front of the call's last wait
+static int page_back(page_args* pg, size_t n_queries, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(pg->h_skipped.data(), pg->d_skipped, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    return DINT_OK;
+}
+
 // the *_queries_freqs entries: a freqs dictionary of the index's device and kind, and somewhere for the sums
 static bool freqs_args_ok(const dint_query_index* qi, const dint_dict* freqs_dict, const uint64_t* freq_sums) {
     return freqs_dict && freq_sums && (!qi || (freqs_dict->device == qi->docs->device && freqs_dict->kind == qi->docs->kind));

@@ -73,6 +73,9 @@ struct dint_query_index {
     // query the kept documents; per slot of a pass its group; per (query, i) the hit's group, then its group's matches
     device_buffer<unsigned long long> collapse_best;
     device_buffer<uint32_t> collapse_slot_group, collapse_hits;
+    // the paged ranked calls (hip_api_paging.inc): per query of the call the cursor's key and behind them per query the
+    // matches that are not after it
+    device_buffer<unsigned long long> page_keys;
     // dint_check_index (hip_api_check.inc): every block of a list but its last holds 256 postings (the in-index layout:
     // block j of a list is its positions [256 j, 256 j + n)); two pinned staging buffers of a pass's expected postings
     // and their device copies, alternating

@@ -42,6 +42,8 @@ ABI_SYMBOLS = (
     "dint_doc_facets_create", "dint_doc_facets_info_get", "dint_doc_facets_group_sizes", "dint_doc_facets_destroy",
     "dint_ranked_or_faceted_queries", "dint_ranked_and_faceted_queries",
     "dint_ranked_or_collapsed_queries", "dint_ranked_and_collapsed_queries",
+    "dint_ranked_or_paged_queries", "dint_ranked_and_paged_queries",
+    "dint_ranked_or_collapsed_paged_queries", "dint_ranked_and_collapsed_paged_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_check_index", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -180,6 +182,10 @@ def _load():
     lib.dint_ranked_and_faceted_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_or_collapsed_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_and_collapsed_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_or_paged_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_paged_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_or_collapsed_paged_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_collapsed_paged_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
@@ -852,6 +858,117 @@ class QueryIndex:
         and outputs as ranked_or_collapsed_queries, over the intersection."""
         return self._ranked_collapsed("dint_ranked_and_collapsed_queries", freqs_dict, wand, queries, facets, filter, k, with_stats, with_rows)
 
+    def _ranked_paged(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, after, doc_filter, k: int, with_stats: bool):
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        cursors = _pack_cursors(after, n)
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        skipped = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 doc_filter._h if doc_filter is not None else None, cursors.ctypes.data if cursors is not None else None, n,
+                                 counts.ctypes.data, matches.ctypes.data, skipped.ctypes.data, scores.ctypes.data, docids.ctypes.data,
+                                 C.byref(blocks), self._stream()), fn)
+        return (counts, scores, docids, matches, blocks.value, skipped) if with_stats else (counts, scores, docids, skipped)
+
+    def ranked_or_paged_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, after=None, filter=None, k: int = 10,
+                                with_stats: bool = False):
+        """ranked_or_filtered_queries behind a cursor per query (dint_ranked_or_paged_queries): after is
+        None (every query from the start) or a list of n entries, each None (from the start) or (score, docid) — the last hit
+        the caller has seen; it need not be a match. A match (s, d) lies after (cs, cd) iff s < cs, or s == cs and d > cd,
+        compared on the float's bits; a score <= 0 leaves nothing after it, a NaN is refused. filter: a DocFilter of this
+        index or None -> what ranked_or_filtered_queries returns for (queries, filter, k, with_stats) — counts =
+        min(k, matches - skipped), scores and docids the best k AFTER the cursor, matches and blocks_decoded unchanged by it —
+        and behind it skipped u64[n]: the matches not after the cursor, i.e. the rank of the page's first hit. Every page
+        decodes and scores the whole query again."""
+        return self._ranked_paged("dint_ranked_or_paged_queries", freqs_dict, wand, queries, after, filter, k, with_stats)
+
+    def ranked_and_paged_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, after=None, filter=None, k: int = 10,
+                                 with_stats: bool = False):
+        """ranked_and_filtered_queries behind a cursor per query (dint_ranked_and_paged_queries): arguments and outputs as
+        ranked_or_paged_queries, over the intersection."""
+        return self._ranked_paged("dint_ranked_and_paged_queries", freqs_dict, wand, queries, after, filter, k, with_stats)
+
+    def _ranked_collapsed_paged(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, facets, after, doc_filter, k: int,
+                                with_stats: bool, with_rows: bool):
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        cursors = _pack_cursors(after, n)
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        collapsed = np.zeros(n, dtype=np.uint64)
+        skipped = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        hit_groups = np.zeros((n, k), dtype=np.uint32)
+        hit_group_matches = np.zeros((n, k), dtype=np.uint32)
+        rows = np.zeros((n, facets.n_groups), dtype=np.uint32) if with_rows else None
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 doc_filter._h if doc_filter is not None else None, facets._h,
+                                 cursors.ctypes.data if cursors is not None else None, n, counts.ctypes.data, matches.ctypes.data,
+                                 collapsed.ctypes.data, skipped.ctypes.data, scores.ctypes.data, docids.ctypes.data,
+                                 hit_groups.ctypes.data, hit_group_matches.ctypes.data, rows.ctypes.data if with_rows else None,
+                                 C.byref(blocks), self._stream()), fn)
+        out = (counts, scores, docids, matches, blocks.value) if with_stats else (counts, scores, docids)
+        out += (collapsed, hit_groups, hit_group_matches)
+        return (out + (rows,) if with_rows else out) + (skipped,)
+
+    def ranked_or_collapsed_paged_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, facets: "DocFacets", after=None,
+                                          filter=None, k: int = 10, with_stats: bool = False, with_rows: bool = False):
+        """ranked_or_collapsed_queries behind a cursor per query (dint_ranked_or_collapsed_paged_queries):
+        after as ranked_or_paged_queries takes it. The cursor applies to the kept documents, after the best of every group is
+        taken, so the pages of a walk show every group once -> what ranked_or_collapsed_queries returns for the same
+        arguments — counts = min(k, collapsed - skipped), the hits those after the cursor, collapsed, matches, the rows and
+        blocks_decoded unchanged by it — and last skipped u64[n]: the kept documents not after the cursor."""
+        return self._ranked_collapsed_paged("dint_ranked_or_collapsed_paged_queries", freqs_dict, wand, queries, facets, after, filter, k,
+                                            with_stats, with_rows)
+
+    def ranked_and_collapsed_paged_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, facets: "DocFacets", after=None,
+                                           filter=None, k: int = 10, with_stats: bool = False, with_rows: bool = False):
+        """ranked_and_collapsed_queries behind a cursor per query (dint_ranked_and_collapsed_paged_queries): arguments and
+        outputs as ranked_or_collapsed_paged_queries, over the intersection."""
+        return self._ranked_collapsed_paged("dint_ranked_and_collapsed_paged_queries", freqs_dict, wand, queries, facets, after, filter, k,
+                                            with_stats, with_rows)
+
+    def ranked_pages(self, entry: str, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10, filter=None, facets=None,
+                     after=None, max_pages=None):
+        """Walks a batch page by page: entry is "or", "and", "or_collapsed" or "and_collapsed" (the
+        collapsed ones need facets). The first page starts at `after` (None: from the start); each query's next cursor is its
+        last hit, and a query drops out of the batch when a page comes back short (fewer than k hits: nothing lies behind it).
+        Yields per page (query ids — indices into `queries` of the queries still in the batch —, counts, scores, docids,
+        skipped), a row per query id; stops after max_pages pages or when no query is left. Every page is a call of its own
+        and decodes and scores its queries again."""
+        calls = {"or": self.ranked_or_paged_queries, "and": self.ranked_and_paged_queries,
+                 "or_collapsed": self.ranked_or_collapsed_paged_queries, "and_collapsed": self.ranked_and_collapsed_paged_queries}
+        if entry not in calls:
+            raise ValueError(f"ranked_pages: entry must be one of {sorted(calls)}, not {entry!r}")
+        collapsed = entry.endswith("_collapsed")
+        if collapsed and facets is None:
+            raise ValueError("ranked_pages: a collapsed entry needs facets")
+        ids = np.arange(len(queries), dtype=np.int64)
+        cursors = list(after) if after is not None else [None] * len(queries)
+        if len(cursors) != len(queries):
+            raise ValueError(f"ranked_pages: {len(cursors)} cursors for {len(queries)} queries")
+        page = 0
+        while len(ids) and (max_pages is None or page < max_pages):
+            batch = [queries[i] for i in ids]
+            batch_after = [cursors[i] for i in ids]
+            if collapsed:
+                out = calls[entry](freqs_dict, wand, batch, facets, after=batch_after, filter=filter, k=k)
+            else:
+                out = calls[entry](freqs_dict, wand, batch, after=batch_after, filter=filter, k=k)
+            counts, scores, docids, skipped = out[0], out[1], out[2], out[-1]
+            yield ids.copy(), counts, scores, docids, skipped
+            for j, i in enumerate(ids):
+                if counts[j]:
+                    cursors[i] = (scores[j, int(counts[j]) - 1], int(docids[j, int(counts[j]) - 1]))
+            ids = ids[counts == k]
+            page += 1
+
     def ranked_or_maxscore_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10):
         """ranked_or_queries' answer, bit for bit, with MaxScore's pruning: the blocks of low-weight
         lists that no candidate able to reach the top k falls in are not decoded. `wand` must carry max_term_weight ->
@@ -1077,6 +1194,29 @@ class WandData:
             _lib.dint_wand_data_destroy(h)
 
     __del__ = close
+
+
+# dint_rank_cursor {float score; uint32_t docid;}
+_CURSOR = np.dtype([("score", np.float32), ("docid", np.uint32)])
+
+
+def _pack_cursors(after, n: int):
+    """after (None, or n entries each None or (score, docid)) as an array of dint_rank_cursor, or None: a missing entry is
+    score +inf (from the start); the score goes in as the binary32 it is or rounds to."""
+    if after is None:
+        return None
+    if len(after) != n:
+        raise ValueError(f"{len(after)} cursors for {n} queries")
+    out = np.zeros(n, dtype=_CURSOR)
+    for i, c in enumerate(after):
+        if c is None:
+            out[i] = (np.float32(np.inf), 0)
+            continue
+        score, docid = c
+        if not 0 <= int(docid) <= 0xFFFFFFFF:
+            raise ValueError(f"cursor {i}: the docID {docid} is not a u32")
+        out[i] = (np.float32(score), int(docid))
+    return out
 
 
 def _pack_queries(queries):

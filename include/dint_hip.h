@@ -751,8 +751,8 @@ int dint_ranked_and_faceted_queries(dint_query_index* qi, const dint_dict* freqs
  * collapsed, hit_groups or hit_group_matches; n_queries * n_groups > 2^27 — the per-call table of best keys is 8 BYTES PER
  * (QUERY, GROUP), a grow-only workspace of the query index cleared once per call, so this is 1 GiB; the caller batches.
  * Besides the faceted call's launches a call runs two launches over the candidate slots in front of the selection and one
- * over the selected keys behind it, per OR pass / per AND call. Several hits per group, collapsing
- * on the boolean and pruned forms and search_after paging are out of scope. */
+ * over the selected keys behind it, per OR pass / per AND call. Several hits per group and collapsing
+ * on the boolean and pruned forms are out of scope; the hits behind the first k: the paged calls below. */
 int dint_ranked_or_collapsed_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
                                      const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
                                      const dint_doc_facets* facets, size_t n_queries, uint64_t* counts, uint64_t* matches,
@@ -763,6 +763,65 @@ int dint_ranked_and_collapsed_queries(dint_query_index* qi, const dint_dict* fre
                                       const dint_doc_facets* facets, size_t n_queries, uint64_t* counts, uint64_t* matches,
                                       uint64_t* collapsed, float* scores, uint32_t* docids, uint32_t* hit_groups,
                                       uint32_t* hit_group_matches, uint32_t* facet_counts, uint64_t* blocks_decoded, void* stream);
+
+/* ---- search_after paging of the ranked queries (the hits behind a cursor) ------------------------------------------
+ * Adds: what a front end needs for page 2 of a result list and a cursor engine's top-k queue cannot give (ranked_or_query /
+ * ranked_and_query, include/ds2i/queries.hpp:309-457, return one queue of k) — the best k matches BEHIND a position of the
+ * ranking, for a batch of queries with a position each. Asking with a larger k ends at DINT_RANKED_MAX_K; the range calls page
+ * the docID order, not the ranking.
+ * A cursor is a position in the order the selection sorts by: the score's bits, then the inverted docID. A match (s, d) of
+ * query q lies AFTER after[q] = (cs, cd) iff s < cs, or s == cs and d > cd: its key bits(s) << 32 | (0xFFFFFFFF - d) is
+ * strictly below the cursor's. The comparison is on bits and takes no tolerance. The last hit of one page is the cursor of
+ * the next; the cursor need not be a match — any docID and any finite score give a well-defined cut. Special values:
+ *   after == NULL, or score == +inf   from the start: the query's outputs are the un-paged call's, bit for bit, skipped 0
+ *   score <= 0 (-0.0f, -inf)          nothing lies after it (every score is > 0): count 0, skipped = every match
+ *   score NaN                         DINT_ERR_ARG
+ * dint_ranked_or_paged_queries / dint_ranked_and_paged_queries take the arguments of the filtered calls (filter nullable:
+ * unrestricted) and after (HOST, nullable, n_queries entries); the outputs (HOST):
+ *   matches[q]       (nullable) every match, as the filtered call reports it: the cursor does not change it
+ *   skipped[q]       (nullable) the matches that are NOT after the cursor: the rank of the page's first hit
+ *   counts[q]        min(k, matches[q] - skipped[q])
+ *   scores, docids   the best k of the matches after the cursor; order and filler are the other ranked calls'
+ *   *blocks_decoded  (nullable) the filtered call's value: the plan does not depend on the cursor
+ * dint_ranked_or_collapsed_paged_queries / dint_ranked_and_collapsed_paged_queries take the collapsed calls' arguments, after
+ * and skipped. The cursor applies to the KEPT documents, after the best of every group is taken — a group's best does not
+ * depend on the page, so walking the pages shows every group once. collapsed[q] is the collapsed call's; skipped[q] counts the
+ * kept documents not after the cursor; counts[q] = min(k, collapsed[q] - skipped[q]); hit_groups, hit_group_matches, the rows
+ * and matches are defined as the collapsed call defines them.
+ * What a page costs: the whole query. Nothing is kept on the device between pages; every page decodes and scores again, and
+ * one launch over the candidate slots in front of the selection (per OR pass / per AND call) kills and counts what is not
+ * after the cursor — the selection then sees fewer live slots. The cursor keys and the counters are a grow-only workspace of
+ * the query index (16 bytes per query), sent and cleared once per call. The counts are integer sums: exact and the same from
+ * run to run.
+ * A match whose score has underflowed to 0.0f (a norm_len so large that every addend rounds to zero) cannot be paged past: a
+ * cursor at such a hit has score <= 0 and ends the walk.
+ * DINT_ERR_ARG, before anything is written or launched: exactly what the filtered / collapsed calls refuse, and a NaN cursor
+ * score. A scroll that keeps scored slots on the device between pages, paging on the boolean and pruned forms and backwards
+ * paging are out of scope. */
+typedef struct dint_rank_cursor {
+    float score;
+    uint32_t docid;
+} dint_rank_cursor;
+int dint_ranked_or_paged_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                 const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                 const dint_rank_cursor* after, size_t n_queries, uint64_t* counts, uint64_t* matches, uint64_t* skipped,
+                                 float* scores, uint32_t* docids, uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_paged_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                  const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                  const dint_rank_cursor* after, size_t n_queries, uint64_t* counts, uint64_t* matches, uint64_t* skipped,
+                                  float* scores, uint32_t* docids, uint64_t* blocks_decoded, void* stream);
+int dint_ranked_or_collapsed_paged_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                           const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                           const dint_doc_facets* facets, const dint_rank_cursor* after, size_t n_queries, uint64_t* counts,
+                                           uint64_t* matches, uint64_t* collapsed, uint64_t* skipped, float* scores, uint32_t* docids,
+                                           uint32_t* hit_groups, uint32_t* hit_group_matches, uint32_t* facet_counts,
+                                           uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_collapsed_paged_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                            const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                            const dint_doc_facets* facets, const dint_rank_cursor* after, size_t n_queries, uint64_t* counts,
+                                            uint64_t* matches, uint64_t* collapsed, uint64_t* skipped, float* scores, uint32_t* docids,
+                                            uint32_t* hit_groups, uint32_t* hit_group_matches, uint32_t* facet_counts,
+                                            uint64_t* blocks_decoded, void* stream);
 
 /* ---- the wand data's BM25 maxima from the index, on the device; block maxima for the pruned call --------------
  * Replaces: the max_term_weight half of wand_data's constructor (include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp),

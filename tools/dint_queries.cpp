@@ -4,7 +4,8 @@
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
 //   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
 //               ranked_or_bool | ranked_or_range | ranked_and_range | ranked_or_filtered | ranked_and_filtered |
-//               ranked_or_faceted | ranked_and_faceted | ranked_or_collapsed | ranked_and_collapsed, several separated by ':'
+//               ranked_or_faceted | ranked_and_faceted | ranked_or_collapsed | ranked_and_collapsed | ranked_or_paged |
+//               ranked_and_paged, several separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
@@ -43,6 +44,13 @@
 //               result counts are the hits (at most 10 groups a query), and the JSON line carries besides "matches" (every
 //               match of the log), "collapsed" (the kept documents of the log's queries: groups with a match plus
 //               ungrouped matches) and "n_groups";
+//               ranked_or_paged / ranked_and_paged (dint_ranked_or_paged_queries, dint_ranked_and_paged_queries: search_after
+//               paging) walk --pages N pages (default 2) of 10 hits per query, each page behind the last
+//               hit of the one before; a query whose page comes back short is finished. --filter FILE is optional, and
+//               --facets FILE selects the collapsed paged entries (pages of kept documents, one per group); each must be
+//               the only type of its run; the result counts are the hits summed over the pages, and the JSON line carries
+//               besides "pages", "hits" (the hits of the log's queries over their pages) and "matches" (every match of
+//               the log; with --facets also "collapsed" and "n_groups"); --pages 1 answers what ranked_*_filtered answers;
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -56,6 +64,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -79,7 +88,7 @@ static double now_us() {
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] < query_log"
+        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N] < query_log"
                   << std::endl;
         return 1;
     }
@@ -91,12 +100,14 @@ int main(int argc, char** argv) {
         const char* facets_filename = nullptr;
         bool batch = false;
         size_t runs = 10 + 1;  // src/queries.cpp:13
+        size_t pages = 0;      // ranked_*_paged: the pages walked per query (0: not given)
         for (int i = 4; i < argc; ++i) {
             std::string a = argv[i];
             if (a == "--batch") batch = true;
             else if (a == "--runs" && i + 1 < argc) runs = size_t(std::max(2, std::atoi(argv[++i])));
             else if (a == "--filter" && i + 1 < argc) filter_filename = argv[++i];
             else if (a == "--facets" && i + 1 < argc) facets_filename = argv[++i];
+            else if (a == "--pages" && i + 1 < argc) pages = size_t(std::max(1, std::atoi(argv[++i])));
             else if (!wand_filename && a.rfind("--", 0) != 0) wand_filename = argv[i];
             else throw std::runtime_error("unknown parameter");
         }
@@ -134,11 +145,19 @@ int main(int argc, char** argv) {
                       << std::endl;
             return 1;
         }
-        if (!needs_facets && facets_filename) throw std::runtime_error("--facets goes with the ranked_*_faceted and ranked_*_collapsed types only");
-        if (!is_filtered && !needs_facets && filter_filename)
-            throw std::runtime_error("--filter goes with the ranked_*_filtered, ranked_*_faceted and ranked_*_collapsed types only");
+        const bool is_paged = query_type == "ranked_or_paged" || query_type == "ranked_and_paged";
+        for (const char* paged : {"ranked_or_paged", "ranked_and_paged"})
+            if (!is_paged && (":" + query_type + ":").find(std::string(":") + paged + ":") != std::string::npos)
+                throw std::runtime_error(std::string(paged) + " walks its whole log page by page: it must be the only query type of a run");
+        if (!is_paged && pages) throw std::runtime_error("--pages goes with ranked_or_paged and ranked_and_paged only");
+        if (is_paged && !pages) pages = 2;
+        if (!needs_facets && !is_paged && facets_filename)
+            throw std::runtime_error("--facets goes with the ranked_*_faceted, ranked_*_collapsed and ranked_*_paged types only");
+        if (!is_filtered && !needs_facets && !is_paged && filter_filename)
+            throw std::runtime_error("--filter goes with the ranked_*_filtered, ranked_*_faceted, ranked_*_collapsed and ranked_*_paged types only");
+        const bool uses_facets = needs_facets || (is_paged && facets_filename);  // (a paged type: the collapsed paged entry)
         tool::doc_facets_map facets_map;
-        if (needs_facets) {
+        if (uses_facets) {
             std::ifstream ff(facets_filename);
             if (!ff) throw std::runtime_error(std::string("could not open the facets file ") + facets_filename);
             facets_map = tool::parse_doc_facets(ff);
@@ -265,7 +284,7 @@ int main(int argc, char** argv) {
         dint_doc_filter* doc_filter = nullptr;  // ranked_*_filtered: the run's filter
         if (filter_filename) dint_ok(dint_doc_filter_create(qi, filter_bits.words.data(), filter_bits.num_docs, &doc_filter), "dint_doc_filter_create");
         dint_doc_facets* doc_facets = nullptr;  // ranked_*_faceted: the run's map, and a call's rows and matches
-        if (needs_facets)
+        if (uses_facets)
             dint_ok(dint_doc_facets_create(0, facets_map.group_of.data(), facets_map.num_docs, facets_map.n_groups, &doc_facets), "dint_doc_facets_create");
         const size_t n_groups = facets_map.n_groups;
         std::vector<uint32_t> facet_rows;
@@ -276,6 +295,10 @@ int main(int argc, char** argv) {
         std::vector<uint32_t> hit_groups, hit_group_matches;
         constexpr uint32_t kTopK = 10;  // ranked_and_query(wdata, 10), src/queries.cpp:106-108
         std::vector<float> top_scores;
+        // ranked_*_paged: a page's docIDs and counts, and every query's cursor — the last hit of its page before
+        std::vector<uint32_t> top_docids;
+        std::vector<uint64_t> page_counts;
+        std::vector<dint_rank_cursor> cursors;
 
         std::vector<std::string> types;
         for (size_t a = 0; a <= query_type.size();) {
@@ -294,7 +317,8 @@ int main(int argc, char** argv) {
             const bool is_or_filtered = t == "ranked_or_filtered" && wand, is_and_filtered = t == "ranked_and_filtered" && wand;
             const bool is_or_faceted = t == "ranked_or_faceted" && wand, is_and_faceted = t == "ranked_and_faceted" && wand;
             const bool is_or_collapsed = t == "ranked_or_collapsed" && wand, is_and_collapsed = t == "ranked_and_collapsed" && wand;
-            const bool is_ranked = (t == "ranked_and" && wand) || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
+            const bool is_or_paged = t == "ranked_or_paged" && wand, is_and_paged = t == "ranked_and_paged" && wand;
+            const bool is_ranked = (t == "ranked_and" && wand) || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
                                    is_or_range || is_and_range || is_or_filtered || is_and_filtered || is_or_faceted || is_and_faceted ||
                                    is_or_collapsed || is_and_collapsed;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
@@ -365,6 +389,44 @@ int main(int argc, char** argv) {
                                                                   facet_matches.data(), collapsed_counts.data(), top_scores.data(), nullptr,
                                                                   hit_groups.data(), hit_group_matches.data(), nullptr, nullptr, nullptr),
                                 "dint_ranked_and_collapsed_queries");
+                } else if (is_or_paged || is_and_paged) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    top_docids.resize(n * kTopK);
+                    page_counts.resize(n);
+                    facet_matches.resize(n);
+                    cursors.assign(n, dint_rank_cursor{INFINITY, 0u});  // (from the start)
+                    std::fill(q_counts, q_counts + n, uint64_t(0));
+                    if (doc_facets) {
+                        collapsed_counts.resize(n);
+                        hit_groups.resize(n * kTopK);
+                        hit_group_matches.resize(n * kTopK);
+                    }
+                    for (size_t page = 0; page != pages; ++page) {
+                        if (doc_facets)
+                            dint_ok((is_or_paged ? dint_ranked_or_collapsed_paged_queries : dint_ranked_and_collapsed_paged_queries)(
+                                        qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_facets, cursors.data(), n, page_counts.data(),
+                                        facet_matches.data(), collapsed_counts.data(), nullptr, top_scores.data(), top_docids.data(),
+                                        hit_groups.data(), hit_group_matches.data(), nullptr, nullptr, nullptr),
+                                    "dint_ranked_*_collapsed_paged_queries");
+                        else
+                            dint_ok((is_or_paged ? dint_ranked_or_paged_queries : dint_ranked_and_paged_queries)(
+                                        qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, cursors.data(), n, page_counts.data(),
+                                        facet_matches.data(), nullptr, top_scores.data(), top_docids.data(), nullptr, nullptr),
+                                    "dint_ranked_*_paged_queries");
+                        bool more = false;
+                        for (size_t q = 0; q != n; ++q) {
+                            q_counts[q] += page_counts[q];
+                            // a full page: the next one begins behind its last hit; a short one: the query is finished, and a
+                            // cursor of score 0 leaves nothing after it
+                            if (page_counts[q] == kTopK) {
+                                cursors[q] = dint_rank_cursor{top_scores[q * kTopK + kTopK - 1], top_docids[q * kTopK + kTopK - 1]};
+                                more = true;
+                            } else {
+                                cursors[q] = dint_rank_cursor{0.0f, 0u};
+                            }
+                        }
+                        if (!more) break;
+                    }
                 } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
@@ -401,9 +463,9 @@ int main(int argc, char** argv) {
                     run_queries(q.data(), offs, 1, &results, &fsum, i);
                     total += results;
                     if (run == 0) total_one_run += results;
-                    if (run == 0 && needs_facets) {
+                    if (run == 0 && (needs_facets || is_paged)) {
                         all_matches += facet_matches[0];
-                        if (is_collapsed) all_collapsed += collapsed_counts[0];
+                        if (is_collapsed || (is_paged && doc_facets)) all_collapsed += collapsed_counts[0];
                         for (size_t g = 0; g != facet_totals.size(); ++g) facet_totals[g] += facet_rows[g];
                     }
                     if (run != 0) query_times.push_back(now_us() - tick);  // first run is not timed
@@ -431,9 +493,10 @@ int main(int argc, char** argv) {
                 if (batch_total != total_one_run)
                     throw std::runtime_error("the batch call counted " + std::to_string(batch_total) + " results, the one-query calls " +
                                              std::to_string(total_one_run));
-                if (is_collapsed) {  // ... and keep the same documents
+                if (is_collapsed || is_paged) {  // ... and keep the same documents
                     uint64_t batch_matches = 0, batch_collapsed = 0;
-                    for (size_t q = 0; q != queries.size(); ++q) batch_matches += facet_matches[q], batch_collapsed += collapsed_counts[q];
+                    for (size_t q = 0; q != queries.size(); ++q)
+                        batch_matches += facet_matches[q], batch_collapsed += is_collapsed || doc_facets ? collapsed_counts[q] : 0;
                     if (batch_matches != all_matches || batch_collapsed != all_collapsed)
                         throw std::runtime_error("the batch call and the one-query calls counted other matches or kept other documents");
                 } else if (is_faceted) {  // ... and count the same matches per group
@@ -451,7 +514,10 @@ int main(int argc, char** argv) {
             std::cout << "{\"type\": \"" << type << "\", \"query\": \"" << t << "\", \"avg\": " << avg << ", \"q50\": " << q50
                       << ", \"q90\": " << q90 << ", \"q95\": " << q95;
             if (batch_us >= 0) std::cout << ", \"batch_us_per_query\": " << batch_us;
-            if (is_collapsed) {
+            if (is_paged) {
+                std::cout << ", \"pages\": " << pages << ", \"hits\": " << total_one_run << ", \"matches\": " << all_matches;
+                if (doc_facets) std::cout << ", \"collapsed\": " << all_collapsed << ", \"n_groups\": " << n_groups;
+            } else if (is_collapsed) {
                 std::cout << ", \"matches\": " << all_matches << ", \"collapsed\": " << all_collapsed << ", \"n_groups\": " << n_groups;
             } else if (is_faceted) {
                 std::cout << ", \"matches\": " << all_matches << ", \"n_groups\": " << n_groups << ", \"facet_totals\": [";
