@@ -29,9 +29,12 @@ void scan_finish(uint32_t* out, uint64_t n, uint32_t* partials, hipStream_t s) {
 }
 }  // namespace
 
-int dint_doc_filter_create(dint_query_index* qi, const uint64_t* bits, uint64_t num_docs, dint_doc_filter** out) {
-    if (!qi || !out || (num_docs && !bits) || num_docs > 0xFFFFFFFFull) return DINT_ERR_ARG;
-    *out = nullptr;
+// A filter handle of num_docs documents for qi, shared by its two creations (dint_doc_filter_create and, hip_api_doc_values.inc,
+// dint_doc_filter_create_from_values): fill(d_bits, n_words) puts the bitmap into the handle's own words on the device, masked
+// at num_docs — an upload or a kernel on the null stream, under the index's lock — and the same rank-directory, liveness and
+// scan launches follow.
+static int doc_filter_build(dint_query_index* qi, uint64_t num_docs, const std::function<bool(uint64_t*, uint64_t)>& fill,
+                            dint_doc_filter** out) {
     auto* f = new (std::nothrow) dint_doc_filter();
     if (!f) return DINT_ERR_NOMEM;
     f->qi = qi;
@@ -46,8 +49,6 @@ int dint_doc_filter_create(dint_query_index* qi, const uint64_t* bits, uint64_t 
         delete f;
         return DINT_ERR_NOMEM;
     }
-    // the handle's own copy is the device's: the caller's words go there as they are, and the last word again, masked at num_docs
-    const uint64_t last_word = n_words ? (num_docs & 63u ? bits[n_words - 1] & ((1ull << (num_docs & 63u)) - 1ull) : bits[n_words - 1]) : 0ull;
 
     std::lock_guard<std::mutex> lock(qi->mutex);
     // the creation's own memory: the rank directory (an entry per word and the total), the partials of either scan, the flags
@@ -60,8 +61,7 @@ int dint_doc_filter_create(dint_query_index* qi, const uint64_t* bits, uint64_t 
               hip_ok(counted_malloc(&d_rank, (n_words + 1) * 4), "counted_malloc(filter rank)") &&
               hip_ok(counted_malloc(&d_partials, n_partials * 4), "counted_malloc(filter partials)") &&
               hip_ok(counted_malloc(&d_live, std::max<uint64_t>(1, n_blocks)), "counted_malloc(filter live)") &&
-              (n_words == 0 || (hip_ok(hipMemcpy(f->d_bits, bits, n_words * 8, hipMemcpyHostToDevice), "hipMemcpy(filter bits)") &&
-                                hip_ok(hipMemcpy(f->d_bits + (n_words - 1), &last_word, 8, hipMemcpyHostToDevice), "hipMemcpy(filter last word)")));
+              (n_words == 0 || fill(f->d_bits, n_words));
     uint32_t n_set = 0;
     if (ok) {
         hipStream_t s = nullptr;
@@ -87,6 +87,17 @@ int dint_doc_filter_create(dint_query_index* qi, const uint64_t* bits, uint64_t 
     f->n_set = n_set;
     *out = f;
     return DINT_OK;
+}
+
+int dint_doc_filter_create(dint_query_index* qi, const uint64_t* bits, uint64_t num_docs, dint_doc_filter** out) {
+    if (!qi || !out || (num_docs && !bits) || num_docs > 0xFFFFFFFFull) return DINT_ERR_ARG;
+    *out = nullptr;
+    // the handle's own copy is the device's: the caller's words go there as they are, and the last word again, masked at num_docs
+    return doc_filter_build(qi, num_docs, [&](uint64_t* d_bits, uint64_t n_words) {
+        const uint64_t last_word = num_docs & 63u ? bits[n_words - 1] & ((1ull << (num_docs & 63u)) - 1ull) : bits[n_words - 1];
+        return hip_ok(hipMemcpy(d_bits, bits, n_words * 8, hipMemcpyHostToDevice), "hipMemcpy(filter bits)") &&
+               hip_ok(hipMemcpy(d_bits + (n_words - 1), &last_word, 8, hipMemcpyHostToDevice), "hipMemcpy(filter last word)");
+    }, out);
 }
 
 int dint_doc_filter_info_get(const dint_doc_filter* f, dint_doc_filter_info* info) {

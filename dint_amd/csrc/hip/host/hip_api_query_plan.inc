@@ -72,8 +72,10 @@ static float bm25_query_term_weight(uint32_t qf, uint64_t df, uint64_t num_docs)
     const float epsilon_score = 1.0E-6f;
     return f * std::max(epsilon_score, idf) * (1.0f + kBm25K1);
 }
+// (sv, a sorted call's sort_args below: stage 1 of the selection orders by the column's value instead of the score)
+struct sort_args;
 static int ranked_topk(dint_query_index* qi, const ranked_args& rk, const std::vector<uint32_t>& page_query, size_t n_queries,
-                       hipStream_t s);
+                       hipStream_t s, const sort_args* sv = nullptr);
 
 // A ranged call (hip_api_ranked_range.inc): every query's docID range, and what the call reports besides its answer. Where
 // a call takes a null one there is no range: nothing is planned or launched differently.
@@ -126,6 +128,14 @@ struct dint_doc_facets {
     uint32_t* d_group_of = nullptr;  // max(1, num_docs) words
     std::vector<uint32_t> sizes;     // n_groups: the documents of every group
     doc_facets_view view() const { return doc_facets_view{d_group_of, uint32_t(num_docs), n_groups}; }
+};
+// A document-values handle (dint_doc_values_create, hip_api_doc_values.inc): docID -> value, a word per document on the
+// device. Like the facets handle it belongs to a device, not to a query index. Immutable once created.
+struct dint_doc_values {
+    int device = 0;
+    uint64_t num_docs = 0;
+    uint32_t* d_values = nullptr;  // max(1, num_docs) words
+    doc_values_view view() const { return doc_values_view{d_values, uint32_t(num_docs)}; }
 };
 // A faceted call (hip_api_facets.inc): the handle, the call's rows on the device — n_queries * n_groups counters in the
 // query index's facet_rows workspace, cleared once per call, added to by every pass — and where they go on the host. Where a
@@ -260,6 +270,73 @@ static int page_after_launch(const dint_query_index* qi, const page_args* pg, ui
 // ... and the counters' way back, on the stream, in front of the call's last wait
 static int page_back(page_args* pg, size_t n_queries, hipStream_t s) {
     HIP_TRY(hipMemcpyAsync(pg->h_skipped.data(), pg->d_skipped, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    return DINT_OK;
+}
+
+// A sorted call (hip_api_doc_values.inc): the column and the order its hits come in, per query of the call the cursor's key
+// K (dint_doc_values_kernels.hpp) and whether it has a cursor at all — every 64-bit pattern is a key, so the flag travels
+// beside it — and what the call reports besides its answer: per query the matches NOT after the cursor, per (query, i) the
+// BM25 score of hit i (a key has no room for it: sorted_hits_kernel recovers it behind the selection). The keys and the
+// counters, the flags and the hit scores are two grow-only workspaces of the query index, sent and cleared once per call
+// under the lock (sort_begin_device). Per OR pass / per AND call: scoring -> value_after_kernel -> ranked_topk by value ->
+// sorted_hits_kernel. Where a call takes a null one nothing is planned or launched differently.
+struct sort_args {
+    const dint_doc_values* values = nullptr;
+    uint32_t order = 0, k = 0;
+    bool any_set = false;      // some query has a cursor: value_after_kernel runs
+    bool want_scores = false;  // the caller takes the scores: sorted_hits_kernel runs
+    std::vector<unsigned long long> keys;       // per query: the cursor's key
+    std::vector<uint32_t> set;                  // per query: 0: from the start
+    std::vector<unsigned long long> h_skipped;  // out: per query (a query the call did not run: 0)
+    std::vector<float> h_hit_scores;            // out: n_queries * k (past a query's count: 0.0f)
+    unsigned long long *d_keys = nullptr, *d_skipped = nullptr;  // (set by sort_begin_device)
+    uint32_t* d_set = nullptr;
+    float* d_hit_scores = nullptr;
+};
+// the call is planned and has refused nothing: no query has skipped a match or has a hit until a pass says otherwise
+static void sort_begin(sort_args* sv, size_t n_queries) {
+    if (!sv) return;
+    sv->h_skipped.assign(n_queries, 0ull);
+    sv->h_hit_scores.assign(n_queries * sv->k, 0.0f);
+}
+// under the index's lock, once per call, in front of its first launch: the keys and the flags go up, the counters and the
+// hit scores clear
+static int sort_begin_device(dint_query_index* qi, sort_args* sv, size_t n_queries, hipStream_t s) {
+    const size_t n_hits = n_queries * sv->k;
+    if (!qi->sort_keys.ensure(2 * n_queries) || !qi->sort_words.ensure(n_queries + n_hits)) return DINT_ERR_HIP;
+    sv->d_keys = qi->sort_keys.p;
+    sv->d_skipped = sv->d_keys + n_queries;
+    sv->d_set = qi->sort_words.p;
+    sv->d_hit_scores = reinterpret_cast<float*>(qi->sort_words.p + n_queries);
+    // (pageable host memory: the copies have left sv when the call returns, and the call waits on the stream before it does)
+    HIP_TRY(hipMemcpyAsync(sv->d_keys, sv->keys.data(), n_queries * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(sv->d_set, sv->set.data(), n_queries * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(sv->d_skipped, 0, n_queries * sizeof(unsigned long long), s));
+    HIP_TRY(hipMemsetAsync(sv->d_hit_scores, 0, n_hits * 4, s));
+    return DINT_OK;
+}
+// value_after_kernel over the n_pages pages of qi->cand, directly in front of ranked_topk; d_page_query[page] + q0: the
+// page's query of the call. A call without a cursor launches nothing.
+static int value_after_launch(const dint_query_index* qi, const sort_args* sv, uint64_t n_pages, const uint32_t* d_page_query, uint32_t q0,
+                              hipStream_t s) {
+    if (!sv->any_set) return DINT_OK;
+    hipLaunchKernelGGL(value_after_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, n_pages * kPageSlots, d_page_query, q0,
+                       sv->values->view(), sv->order, sv->d_keys, sv->d_set, sv->d_skipped);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// sorted_hits_kernel behind ranked_topk, over the same pages and the keys it selected for the pass's queries (qi->topk_out)
+static int sorted_hits_launch(const dint_query_index* qi, const sort_args* sv, uint64_t n_pages, const uint32_t* d_page_query, uint32_t q0,
+                              hipStream_t s) {
+    if (!sv->want_scores) return DINT_OK;
+    hipLaunchKernelGGL(sorted_hits_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, qi->slot_score.p, n_pages * kPageSlots,
+                       d_page_query, q0, sv->values->view(), sv->order, qi->topk_out.p, sv->k, sv->d_hit_scores);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// ... and the counters' and the hit scores' way back, on the stream, in front of the call's last wait
+static int sort_back(sort_args* sv, size_t n_queries, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(sv->h_skipped.data(), sv->d_skipped, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (sv->want_scores)
+        HIP_TRY(hipMemcpyAsync(sv->h_hit_scores.data(), sv->d_hit_scores, n_queries * sv->k * 4, hipMemcpyDeviceToHost, s));
     return DINT_OK;
 }
 

@@ -73,9 +73,10 @@ int dint_wand_data_create_with_max_weights(int device, const float* norm_lens, u
 // The selection of and_queries_impl's ranked form, on its stream, behind the freqs pass: query q's candidate pages are the
 // pages p with page_query[p] == q (consecutive). Its slots are cut into runs of R keys, every run sorted, then the runs
 // merged pairwise, pass after pass (a pass serves every query of the call), until run 0 of every query holds its best R.
-// rk.keys <- the first k of them (copied on the stream: the caller synchronises).
+// rk.keys <- the first k of them (copied on the stream: the caller synchronises). sv (a sorted call): the runs are sorted by
+// the key of the column's value (topk_sort_runs_by_value_kernel); the merges and the output order whatever keys they get.
 static int ranked_topk(dint_query_index* qi, const ranked_args& rk, const std::vector<uint32_t>& page_query, size_t n_queries,
-                       hipStream_t s) {
+                       hipStream_t s, const sort_args* sv) {
     uint32_t R = kPageSlots;
     while (R < rk.k) R <<= 1;
     std::vector<uint32_t> q_page_first(n_queries, 0), q_pages(n_queries, 0);
@@ -125,7 +126,10 @@ static int ranked_topk(dint_query_index* qi, const ranked_args& rk, const std::v
     for (size_t p = 0; p + 1 < pass_first.size(); ++p) {
         const size_t n_tasks = pass_first[p + 1] - pass_first[p];
         if (n_tasks == 0) continue;
-        if (p == 0)
+        if (p == 0 && sv)
+            hipLaunchKernelGGL(topk_sort_runs_by_value_kernel, dim3(uint32_t(n_tasks)), dim3(tb), R * sizeof(unsigned long long), s, d_tasks,
+                               d_page_first, d_pages, d_base, qi->cand.p, sv->values->view(), sv->order, R, qi->topk_keys.p);
+        else if (p == 0)
             hipLaunchKernelGGL(topk_sort_runs_kernel, dim3(uint32_t(n_tasks)), dim3(tb), R * sizeof(unsigned long long), s, d_tasks,
                                d_page_first, d_pages, d_base, qi->cand.p, qi->slot_score.p, R, qi->topk_keys.p);
         else

@@ -76,6 +76,10 @@ struct dint_query_index {
     // the paged ranked calls (hip_api_paging.inc): per query of the call the cursor's key and behind them per query the
     // matches that are not after it
     device_buffer<unsigned long long> page_keys;
+    // the sorted ranked calls (hip_api_doc_values.inc): per query of the call the cursor's key and behind them per query the
+    // matches that are not after it; per query whether it has a cursor and behind them per (query, i) the hit's score
+    device_buffer<unsigned long long> sort_keys;
+    device_buffer<uint32_t> sort_words;
     // dint_check_index (hip_api_check.inc): every block of a list but its last holds 256 postings (the in-index layout:
     // block j of a list is its positions [256 j, 256 j + n)); two pinned staging buffers of a pass's expected postings
     // and their device copies, alternating

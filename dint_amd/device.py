@@ -44,6 +44,8 @@ ABI_SYMBOLS = (
     "dint_ranked_or_collapsed_queries", "dint_ranked_and_collapsed_queries",
     "dint_ranked_or_paged_queries", "dint_ranked_and_paged_queries",
     "dint_ranked_or_collapsed_paged_queries", "dint_ranked_and_collapsed_paged_queries",
+    "dint_doc_values_create", "dint_doc_values_info_get", "dint_doc_values_destroy", "dint_doc_filter_create_from_values",
+    "dint_ranked_or_sorted_queries", "dint_ranked_and_sorted_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_check_index", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -85,6 +87,10 @@ class DocFilterInfo(C.Structure):  # dint_doc_filter_info
 
 class DocFacetsInfo(C.Structure):  # dint_doc_facets_info
     _fields_ = [(k, C.c_uint64) for k in ("num_docs", "n_groups", "n_grouped")]
+
+
+class DocValuesInfo(C.Structure):  # dint_doc_values_info
+    _fields_ = [("num_docs", C.c_uint64)]
 
 
 class IndexMismatch(C.Structure):  # dint_index_mismatch
@@ -186,6 +192,13 @@ def _load():
     lib.dint_ranked_and_paged_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_or_collapsed_paged_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_and_collapsed_paged_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_doc_values_create.argtypes = [C.c_int, vp, u64, C.POINTER(vp)]
+    lib.dint_doc_values_info_get.argtypes = [vp, C.POINTER(DocValuesInfo)]
+    lib.dint_doc_values_destroy.argtypes = [vp]
+    lib.dint_doc_values_destroy.restype = None
+    lib.dint_doc_filter_create_from_values.argtypes = [vp, vp, u32, u32, C.POINTER(vp)]
+    lib.dint_ranked_or_sorted_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_sorted_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
@@ -934,21 +947,88 @@ class QueryIndex:
         return self._ranked_collapsed_paged("dint_ranked_and_collapsed_paged_queries", freqs_dict, wand, queries, facets, after, filter, k,
                                             with_stats, with_rows)
 
+    def doc_filter_from_values(self, values: "DocValues", lo: int, hi: int) -> "DocFilter":
+        """The filter of the documents d < values.num_docs with lo <= v(d) <= hi (closed; lo > hi: the empty filter), built
+        on the device from the column (dint_doc_filter_create_from_values): in its info and under every
+        filtered call it equals doc_filter of the same bitmap. Close it before the index."""
+        return DocFilter.from_values(self, values, lo, hi)
+
+    def _ranked_sorted(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, values, descending, after, doc_filter, k: int,
+                       with_stats: bool):
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        cursors = _pack_value_cursors(after, n)
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        skipped = np.zeros(n, dtype=np.uint64)
+        hit_values = np.zeros((n, k), dtype=np.uint32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        scores = np.zeros((n, k), dtype=np.float32)
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 doc_filter._h if doc_filter is not None else None, values._h, SORT_DESC if descending else SORT_ASC,
+                                 cursors.ctypes.data if cursors is not None else None, n, counts.ctypes.data, matches.ctypes.data,
+                                 skipped.ctypes.data, hit_values.ctypes.data, docids.ctypes.data, scores.ctypes.data, C.byref(blocks),
+                                 self._stream()), fn)
+        if with_stats:
+            return counts, hit_values, docids, scores, matches, blocks.value, skipped
+        return counts, hit_values, docids, scores, skipped
+
+    def ranked_or_sorted_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, values: "DocValues", descending: bool = True,
+                                 after=None, filter=None, k: int = 10, with_stats: bool = False):
+        """ranked_or_filtered_queries' matches ordered by a column instead of the score (dint_ranked_or_sorted_queries, DESIGN.md
+        4d-values): values is a DocValues on this index's device; descending: the larger value first, else the smaller; equal
+        values go by ascending docID in both orders. after is None (every query from the start) or a list of n entries, each
+        None or (value, docid) — the last hit the caller has seen; it need not be a match. filter: a DocFilter of this index or
+        None -> (counts u64[n] = min(k, matches - skipped), hit_values u32[n, k], docids u32[n, k], scores f32[n, k] — every
+        hit's score exactly the filtered call's —, skipped u64[n]: the matches not after the cursor); with_stats: (counts,
+        hit_values, docids, scores, matches, blocks_decoded, skipped), matches and blocks_decoded the filtered call's. Past
+        the count: 0, 0xFFFFFFFF, 0.0."""
+        return self._ranked_sorted("dint_ranked_or_sorted_queries", freqs_dict, wand, queries, values, descending, after, filter, k, with_stats)
+
+    def ranked_and_sorted_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, values: "DocValues", descending: bool = True,
+                                  after=None, filter=None, k: int = 10, with_stats: bool = False):
+        """ranked_and_filtered_queries' matches ordered by a column (dint_ranked_and_sorted_queries): arguments and outputs as
+        ranked_or_sorted_queries, over the intersection."""
+        return self._ranked_sorted("dint_ranked_and_sorted_queries", freqs_dict, wand, queries, values, descending, after, filter, k, with_stats)
+
     def ranked_pages(self, entry: str, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10, filter=None, facets=None,
-                     after=None, max_pages=None):
+                     after=None, max_pages=None, values=None, descending: bool = True):
         """Walks a batch page by page: entry is "or", "and", "or_collapsed" or "and_collapsed" (the
-        collapsed ones need facets). The first page starts at `after` (None: from the start); each query's next cursor is its
+        collapsed ones need facets), or "or_sorted" / "and_sorted" (they need values, a DocValues, and
+        take descending). The first page starts at `after` (None: from the start); each query's next cursor is its
         last hit, and a query drops out of the batch when a page comes back short (fewer than k hits: nothing lies behind it).
         Yields per page (query ids — indices into `queries` of the queries still in the batch —, counts, scores, docids,
-        skipped), a row per query id; stops after max_pages pages or when no query is left. Every page is a call of its own
-        and decodes and scores its queries again."""
+        skipped), a row per query id — a sorted entry: (query ids, counts, hit_values, docids, scores, skipped), and the next
+        cursor is (hit_value, docid) of a page's last hit; stops after max_pages pages or when no query is left. Every page is
+        a call of its own and decodes and scores its queries again."""
         calls = {"or": self.ranked_or_paged_queries, "and": self.ranked_and_paged_queries,
-                 "or_collapsed": self.ranked_or_collapsed_paged_queries, "and_collapsed": self.ranked_and_collapsed_paged_queries}
+                 "or_collapsed": self.ranked_or_collapsed_paged_queries, "and_collapsed": self.ranked_and_collapsed_paged_queries,
+                 "or_sorted": self.ranked_or_sorted_queries, "and_sorted": self.ranked_and_sorted_queries}
         if entry not in calls:
             raise ValueError(f"ranked_pages: entry must be one of {sorted(calls)}, not {entry!r}")
         collapsed = entry.endswith("_collapsed")
         if collapsed and facets is None:
             raise ValueError("ranked_pages: a collapsed entry needs facets")
+        if entry.endswith("_sorted"):
+            if values is None:
+                raise ValueError("ranked_pages: a sorted entry needs values")
+            ids = np.arange(len(queries), dtype=np.int64)
+            cursors = list(after) if after is not None else [None] * len(queries)
+            if len(cursors) != len(queries):
+                raise ValueError(f"ranked_pages: {len(cursors)} cursors for {len(queries)} queries")
+            page = 0
+            while len(ids) and (max_pages is None or page < max_pages):
+                counts, hit_values, docids, scores, skipped = calls[entry](
+                    freqs_dict, wand, [queries[i] for i in ids], values, descending=descending, after=[cursors[i] for i in ids],
+                    filter=filter, k=k)
+                yield ids.copy(), counts, hit_values, docids, scores, skipped
+                for j, i in enumerate(ids):
+                    if counts[j]:
+                        cursors[i] = (int(hit_values[j, int(counts[j]) - 1]), int(docids[j, int(counts[j]) - 1]))
+                ids = ids[counts == k]
+                page += 1
+            return
         ids = np.arange(len(queries), dtype=np.int64)
         cursors = list(after) if after is not None else [None] * len(queries)
         if len(cursors) != len(queries):
@@ -1090,6 +1170,18 @@ class DocFilter:
         _check(_lib.dint_doc_filter_info_get(self._h, C.byref(out)), "dint_doc_filter_info_get")
         return out
 
+    @classmethod
+    def from_values(cls, index: "QueryIndex", values: "DocValues", lo: int, hi: int) -> "DocFilter":
+        """QueryIndex.doc_filter_from_values: the documents of the column with lo <= v(d) <= hi, found on the device"""
+        if not (0 <= int(lo) <= 0xFFFFFFFF and 0 <= int(hi) <= 0xFFFFFFFF):
+            raise ValueError("lo and hi are u32")
+        self = cls.__new__(cls)
+        self.index = index
+        self._h = C.c_void_p()
+        _check(_lib.dint_doc_filter_create_from_values(index._h, values._h, int(lo), int(hi), C.byref(self._h)),
+               "dint_doc_filter_create_from_values")
+        return self
+
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None:  # (None at interpreter shutdown)
@@ -1158,6 +1250,58 @@ class DocFacets:
     __del__ = close
 
 
+SORT_DESC, SORT_ASC = 0, 1    # DINT_SORT_DESC, DINT_SORT_ASC (include/dint_hip.h)
+
+
+class DocValues:
+    """A document -> u32 value column on a device (dint_doc_values): values[d] is document d's value,
+    every 32-bit value is legal, and a document at or past len(values) sorts as value 0. It belongs to no index, holds 4
+    bytes per document on the device, is immutable and serves any number of ranked_*_sorted_queries and
+    doc_filter_from_values calls, from several threads."""
+
+    def __init__(self, device: int, values):
+        a = np.asarray(values)
+        if a.size and a.dtype.kind not in "iu":
+            raise TypeError("values holds integers (floats: DocValues.from_float32)")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError("a value does not fit u32")
+        v = np.ascontiguousarray(a.reshape(-1), dtype=np.uint32)
+        self.device = device
+        self._h = C.c_void_p()
+        _check(_lib.dint_doc_values_create(device, v.ctypes.data if v.size else None, v.size, C.byref(self._h)), "dint_doc_values_create")
+        info = DocValuesInfo()
+        _check(_lib.dint_doc_values_info_get(self._h, C.byref(info)), "dint_doc_values_info_get")
+        self.num_docs = int(info.num_docs)
+
+    @staticmethod
+    def float32_keys(x) -> np.ndarray:
+        """binary32 -> order-preserving u32: bits with the sign bit set are inverted, all others get the sign bit set, so
+        -0.0 sorts directly below +0.0. A NaN raises."""
+        f = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        if np.isnan(f).any():
+            raise ValueError("a NaN has no place in the order")
+        bits = f.view(np.uint32)
+        return np.where(bits >> 31 != 0, ~bits, bits | np.uint32(0x80000000)).astype(np.uint32)
+
+    @classmethod
+    def from_float32(cls, device: int, x) -> "DocValues":
+        """A column of binary32 numbers, mapped by float32_keys: sorting by the column sorts by the numbers."""
+        return cls(device, cls.float32_keys(x))
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:  # (None at interpreter shutdown)
+            _lib.dint_doc_values_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = close
+
+
 class WandData:
     """The wand data's document lengths on the device (dint_wand_data_create): norm_lens f32[num_docs], as
     host.wand_data / host.read_wand_data give them; with max_term_weight f32[n_lists] (the same functions' second array)
@@ -1216,6 +1360,28 @@ def _pack_cursors(after, n: int):
         if not 0 <= int(docid) <= 0xFFFFFFFF:
             raise ValueError(f"cursor {i}: the docID {docid} is not a u32")
         out[i] = (np.float32(score), int(docid))
+    return out
+
+
+# dint_value_cursor {uint32_t value; uint32_t docid; uint32_t set;}
+_VALUE_CURSOR = np.dtype([("value", np.uint32), ("docid", np.uint32), ("set", np.uint32)])
+
+
+def _pack_value_cursors(after, n: int):
+    """after (None, or n entries each None or (value, docid)) as an array of dint_value_cursor, or None: a missing entry has
+    set == 0 (from the start)."""
+    if after is None:
+        return None
+    if len(after) != n:
+        raise ValueError(f"{len(after)} cursors for {n} queries")
+    out = np.zeros(n, dtype=_VALUE_CURSOR)
+    for i, c in enumerate(after):
+        if c is None:
+            continue
+        value, docid = c
+        if not (0 <= int(value) <= 0xFFFFFFFF and 0 <= int(docid) <= 0xFFFFFFFF):
+            raise ValueError(f"cursor {i}: ({value}, {docid}) are not u32")
+        out[i] = (int(value), int(docid), 1)
     return out
 
 

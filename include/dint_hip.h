@@ -823,6 +823,70 @@ int dint_ranked_and_collapsed_paged_queries(dint_query_index* qi, const dint_dic
                                             uint32_t* hit_groups, uint32_t* hit_group_matches, uint32_t* facet_counts,
                                             uint64_t* blocks_decoded, void* stream);
 
+/* ---- document values: ranked hits sorted by a per-document number, value-range filters ------------------------------
+ * Adds: what a cursor engine computes with a field-sort collector in place of its top-k queue (ranked_or_query /
+ * ranked_and_query, include/ds2i/queries.hpp:309-457, order by score only) — "the matches of this query, newest first" (or
+ * cheapest first, or by any per-document number) — and the filter "only the documents whose value lies in [lo, hi]". A ranked
+ * call with a large k, re-sorted by the caller, ends at DINT_RANKED_MAX_K and is wrong as soon as a query has more matches.
+ * A values handle (dint_doc_values_create): values is a HOST array of num_docs words, one u32 per document, every 32-bit
+ * value legal (signed, 64-bit or float columns: the caller maps them to order-preserving u32). The handle takes its device as
+ * dint_doc_facets_create does and belongs to no query index. It keeps its own copy on the device, 4 BYTES PER DOCUMENT (values
+ * may be released at once), is immutable and usable from several host threads at once. num_docs == 0 is legal. A document at
+ * or past num_docs has value 0 wherever a value is read for sorting. DINT_ERR_ARG (no handle): num_docs > 0xFFFFFFFF, a null
+ * out, a null array with num_docs > 0. dint_doc_values_info_get: num_docs as given.
+ * dint_ranked_or_sorted_queries / dint_ranked_and_sorted_queries take the arguments of the filtered calls (filter nullable:
+ * unrestricted), the column, order (DINT_SORT_DESC: larger value first; DINT_SORT_ASC) and after (HOST, nullable, n_queries
+ * entries; set == 0: from the start). The matches are the filtered call's match set; the plan depends neither on the column,
+ * nor on the order, nor on the cursor. The order is by value; EQUAL VALUES GO BY ASCENDING docID IN BOTH ORDERS. As a key,
+ * sorted descending: K(d) = (order == ASC ? ~v(d) : v(d)) << 32 | (0xFFFFFFFF - d). A match lies AFTER a set cursor (cv, cd)
+ * iff K(d) < (ASC ? ~cv : cv) << 32 | (0xFFFFFFFF - cd), compared as integers; the cursor need not be a match. The last hit
+ * of one page, as (hit_value, docid), is the cursor of the next. The outputs (HOST):
+ *   matches[q]       (nullable) every match, as the filtered call reports it: bit for bit
+ *   skipped[q]       (nullable) the matches that are NOT after the cursor: the rank of the page's first hit
+ *   counts[q]        min(k, matches[q] - skipped[q])
+ *   docids, hit_values[q * k + i]  the i-th match after the cursor in the order above, and its value (hit_values nullable)
+ *   scores[q * k + i]  (nullable) EXACTLY the BM25 score the filtered call gives that document
+ *   past the count   0xFFFFFFFF, 0 and 0.0f
+ *   *blocks_decoded  (nullable) the filtered call's value
+ * What a page costs: the whole query, as a paged call's, and besides the filtered call's launches, per OR pass / per AND call,
+ * one launch over the candidate slots that cuts at the cursor (only if some query has one), the selection's first stage with
+ * one gathered word per live slot, and one launch over the slots behind the selection that finds the hits' scores (only if
+ * scores are asked for). The cursor keys, flags, counters and hit scores are grow-only workspaces of the query index
+ * (20 + 4 k bytes per query), sent and cleared once per call. Integer comparisons throughout: exact, the same from run to run.
+ * DINT_ERR_ARG, before anything is written or launched: whatever the filtered calls refuse (scores may be null here, docids may
+ * not), a null values or one on another device than the index, order > 1.
+ * dint_doc_filter_create_from_values: the filter of the documents d < the column's num_docs with lo <= v(d) <= hi (closed;
+ * lo > hi: the empty filter), built on the device — the bitmap never exists on the host. In its info and under every filtered
+ * call it equals what dint_doc_filter_create makes of the same bitmap with num_docs the column's. DINT_ERR_ARG: a null qi,
+ * values or out, a column on another device than the index.
+ * Sorting the collapsed, faceted, boolean and pruned forms, several sort keys, an order per query, a value range combined
+ * with a bitmap in one handle, backwards paging and narrower columns are out of scope. */
+#define DINT_SORT_DESC 0u
+#define DINT_SORT_ASC 1u
+typedef struct dint_doc_values dint_doc_values;
+typedef struct dint_doc_values_info {
+    uint64_t num_docs; /* as given to dint_doc_values_create */
+} dint_doc_values_info;
+typedef struct dint_value_cursor {
+    uint32_t value;
+    uint32_t docid;
+    uint32_t set; /* 0: from the start */
+} dint_value_cursor;
+int dint_doc_values_create(int device, const uint32_t* values, uint64_t num_docs, dint_doc_values** out);
+int dint_doc_values_info_get(const dint_doc_values* v, dint_doc_values_info* info);
+void dint_doc_values_destroy(dint_doc_values* v);
+int dint_doc_filter_create_from_values(dint_query_index* qi, const dint_doc_values* values, uint32_t lo, uint32_t hi, dint_doc_filter** out);
+int dint_ranked_or_sorted_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                  const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                  const dint_doc_values* values, uint32_t order, const dint_value_cursor* after, size_t n_queries,
+                                  uint64_t* counts, uint64_t* matches, uint64_t* skipped, uint32_t* hit_values, uint32_t* docids, float* scores,
+                                  uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_sorted_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                   const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                   const dint_doc_values* values, uint32_t order, const dint_value_cursor* after, size_t n_queries,
+                                   uint64_t* counts, uint64_t* matches, uint64_t* skipped, uint32_t* hit_values, uint32_t* docids, float* scores,
+                                   uint64_t* blocks_decoded, void* stream);
+
 /* ---- the wand data's BM25 maxima from the index, on the device; block maxima for the pruned call --------------
  * Replaces: the max_term_weight half of wand_data's constructor (include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp),
  * which walks the uncompressed collection posting by posting, by one decode of the INDEX: a caller that has only what this

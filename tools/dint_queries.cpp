@@ -1,11 +1,12 @@
 // dint_queries — the reference's `queries` tool (src/queries.cpp:15-153) for the DINT index types, on the device path.
 //
-//   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] [--filter FILE] [--facets FILE] < query_log
+//   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N]
+//                [--values FILE] [--order asc|desc] [--value-range lo:hi] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
 //   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
 //               ranked_or_bool | ranked_or_range | ranked_and_range | ranked_or_filtered | ranked_and_filtered |
 //               ranked_or_faceted | ranked_and_faceted | ranked_or_collapsed | ranked_and_collapsed | ranked_or_paged |
-//               ranked_and_paged, several separated by ':'
+//               ranked_and_paged | ranked_or_sorted | ranked_and_sorted, several separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
@@ -51,6 +52,14 @@
 //               the only type of its run; the result counts are the hits summed over the pages, and the JSON line carries
 //               besides "pages", "hits" (the hits of the log's queries over their pages) and "matches" (every match of
 //               the log; with --facets also "collapsed" and "n_groups"); --pages 1 answers what ranked_*_filtered answers;
+//               ranked_or_sorted / ranked_and_sorted (dint_ranked_or_sorted_queries, dint_ranked_and_sorted_queries: the matches
+//               ordered by a per-document value) need --values FILE — every line `d v` or `lo:hi v`,
+//               later lines win, a document no line names has value 0 (doc_values_file.hpp) — and take --order asc|desc
+//               (default desc), --pages N (default 1: pages of 10 hits, each behind the last hit of the one before) and
+//               either --filter FILE or --value-range lo:hi (the documents of the column whose value lies in the closed
+//               interval, found on the device: dint_doc_filter_create_from_values), not both; each must be the only type
+//               of its run; the result counts are the hits summed over the pages, and the JSON line carries besides
+//               "pages", "hits", "matches" and "order";
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -77,6 +86,7 @@
 #include "dint_hip.h"
 #include "doc_facets_file.hpp"
 #include "doc_filter_file.hpp"
+#include "doc_values_file.hpp"
 #include "tool_common.hpp"
 
 static void dint_ok(int st, const char* what) {
@@ -88,7 +98,7 @@ static double now_us() {
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N] < query_log"
+        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N] [--values FILE] [--order asc|desc] [--value-range lo:hi] < query_log"
                   << std::endl;
         return 1;
     }
@@ -98,6 +108,9 @@ int main(int argc, char** argv) {
         const char* wand_filename = nullptr;
         const char* filter_filename = nullptr;
         const char* facets_filename = nullptr;
+        const char* values_filename = nullptr;
+        const char* value_range = nullptr;  // ranked_*_sorted: lo:hi, the run's filter from the column
+        std::string order_name;             // ranked_*_sorted: asc | desc ("": not given)
         bool batch = false;
         size_t runs = 10 + 1;  // src/queries.cpp:13
         size_t pages = 0;      // ranked_*_paged: the pages walked per query (0: not given)
@@ -107,6 +120,9 @@ int main(int argc, char** argv) {
             else if (a == "--runs" && i + 1 < argc) runs = size_t(std::max(2, std::atoi(argv[++i])));
             else if (a == "--filter" && i + 1 < argc) filter_filename = argv[++i];
             else if (a == "--facets" && i + 1 < argc) facets_filename = argv[++i];
+            else if (a == "--values" && i + 1 < argc) values_filename = argv[++i];
+            else if (a == "--order" && i + 1 < argc) order_name = argv[++i];
+            else if (a == "--value-range" && i + 1 < argc) value_range = argv[++i];
             else if (a == "--pages" && i + 1 < argc) pages = size_t(std::max(1, std::atoi(argv[++i])));
             else if (!wand_filename && a.rfind("--", 0) != 0) wand_filename = argv[i];
             else throw std::runtime_error("unknown parameter");
@@ -149,12 +165,36 @@ int main(int argc, char** argv) {
         for (const char* paged : {"ranked_or_paged", "ranked_and_paged"})
             if (!is_paged && (":" + query_type + ":").find(std::string(":") + paged + ":") != std::string::npos)
                 throw std::runtime_error(std::string(paged) + " walks its whole log page by page: it must be the only query type of a run");
-        if (!is_paged && pages) throw std::runtime_error("--pages goes with ranked_or_paged and ranked_and_paged only");
+        const bool is_sorted = query_type == "ranked_or_sorted" || query_type == "ranked_and_sorted";
+        for (const char* sorted : {"ranked_or_sorted", "ranked_and_sorted"})
+            if (!is_sorted && (":" + query_type + ":").find(std::string(":") + sorted + ":") != std::string::npos)
+                throw std::runtime_error(std::string(sorted) + " walks its whole log page by page under --values: it must be the only query type of a run");
+        if (!is_paged && !is_sorted && pages) throw std::runtime_error("--pages goes with ranked_or_paged, ranked_and_paged, ranked_or_sorted and ranked_and_sorted only");
         if (is_paged && !pages) pages = 2;
+        if (is_sorted && !pages) pages = 1;
+        if (!is_sorted && (values_filename || value_range || !order_name.empty()))
+            throw std::runtime_error("--values, --order and --value-range go with ranked_or_sorted and ranked_and_sorted only");
+        if (is_sorted && !values_filename) {
+            std::cerr << query_type << " needs --values FILE (every line `d v` or `lo:hi v`: document d, or every document of [lo, hi), has value v)"
+                      << std::endl;
+            return 1;
+        }
+        if (!order_name.empty() && order_name != "asc" && order_name != "desc") throw std::runtime_error("--order is asc or desc");
+        const uint32_t sort_order = order_name == "asc" ? DINT_SORT_ASC : DINT_SORT_DESC;
+        if (value_range && filter_filename) throw std::runtime_error("--value-range and --filter exclude each other: a run has one filter");
+        if (is_sorted && facets_filename) throw std::runtime_error("--facets does not go with the ranked_*_sorted types");
+        uint32_t range_lo = 0, range_hi = 0;
+        if (value_range) tool::parse_value_range(value_range, range_lo, range_hi);
+        tool::doc_values_column values_column;
+        if (is_sorted) {
+            std::ifstream vf(values_filename);
+            if (!vf) throw std::runtime_error(std::string("could not open the values file ") + values_filename);
+            values_column = tool::parse_doc_values(vf);
+        }
         if (!needs_facets && !is_paged && facets_filename)
             throw std::runtime_error("--facets goes with the ranked_*_faceted, ranked_*_collapsed and ranked_*_paged types only");
-        if (!is_filtered && !needs_facets && !is_paged && filter_filename)
-            throw std::runtime_error("--filter goes with the ranked_*_filtered, ranked_*_faceted, ranked_*_collapsed and ranked_*_paged types only");
+        if (!is_filtered && !needs_facets && !is_paged && !is_sorted && filter_filename)
+            throw std::runtime_error("--filter goes with the ranked_*_filtered, ranked_*_faceted, ranked_*_collapsed, ranked_*_paged and ranked_*_sorted types only");
         const bool uses_facets = needs_facets || (is_paged && facets_filename);  // (a paged type: the collapsed paged entry)
         tool::doc_facets_map facets_map;
         if (uses_facets) {
@@ -283,6 +323,11 @@ int main(int argc, char** argv) {
         }
         dint_doc_filter* doc_filter = nullptr;  // ranked_*_filtered: the run's filter
         if (filter_filename) dint_ok(dint_doc_filter_create(qi, filter_bits.words.data(), filter_bits.num_docs, &doc_filter), "dint_doc_filter_create");
+        dint_doc_values* doc_values = nullptr;  // ranked_*_sorted: the run's column, and with --value-range the filter from it
+        if (is_sorted) {
+            dint_ok(dint_doc_values_create(0, values_column.values.data(), values_column.num_docs, &doc_values), "dint_doc_values_create");
+            if (value_range) dint_ok(dint_doc_filter_create_from_values(qi, doc_values, range_lo, range_hi, &doc_filter), "dint_doc_filter_create_from_values");
+        }
         dint_doc_facets* doc_facets = nullptr;  // ranked_*_faceted: the run's map, and a call's rows and matches
         if (uses_facets)
             dint_ok(dint_doc_facets_create(0, facets_map.group_of.data(), facets_map.num_docs, facets_map.n_groups, &doc_facets), "dint_doc_facets_create");
@@ -299,6 +344,9 @@ int main(int argc, char** argv) {
         std::vector<uint32_t> top_docids;
         std::vector<uint64_t> page_counts;
         std::vector<dint_rank_cursor> cursors;
+        // ranked_*_sorted: a page's values beside them, and every query's cursor — (value, docid) of its last hit
+        std::vector<uint32_t> top_values;
+        std::vector<dint_value_cursor> value_cursors;
 
         std::vector<std::string> types;
         for (size_t a = 0; a <= query_type.size();) {
@@ -318,7 +366,8 @@ int main(int argc, char** argv) {
             const bool is_or_faceted = t == "ranked_or_faceted" && wand, is_and_faceted = t == "ranked_and_faceted" && wand;
             const bool is_or_collapsed = t == "ranked_or_collapsed" && wand, is_and_collapsed = t == "ranked_and_collapsed" && wand;
             const bool is_or_paged = t == "ranked_or_paged" && wand, is_and_paged = t == "ranked_and_paged" && wand;
-            const bool is_ranked = (t == "ranked_and" && wand) || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
+            const bool is_or_sorted = t == "ranked_or_sorted" && wand, is_and_sorted = t == "ranked_and_sorted" && wand;
+            const bool is_ranked = (t == "ranked_and" && wand) || is_or_sorted || is_and_sorted || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
                                    is_or_range || is_and_range || is_or_filtered || is_and_filtered || is_or_faceted || is_and_faceted ||
                                    is_or_collapsed || is_and_collapsed;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
@@ -427,6 +476,33 @@ int main(int argc, char** argv) {
                         }
                         if (!more) break;
                     }
+                } else if (is_or_sorted || is_and_sorted) {
+                    top_values.resize(n * kTopK);
+                    top_docids.resize(n * kTopK);
+                    page_counts.resize(n);
+                    facet_matches.resize(n);
+                    value_cursors.assign(n, dint_value_cursor{0u, 0u, 0u});  // (from the start)
+                    std::fill(q_counts, q_counts + n, uint64_t(0));
+                    std::vector<char> finished(n, 0);
+                    for (size_t page = 0; page != pages; ++page) {
+                        dint_ok((is_or_sorted ? dint_ranked_or_sorted_queries : dint_ranked_and_sorted_queries)(
+                                    qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_values, sort_order, value_cursors.data(), n,
+                                    page_counts.data(), facet_matches.data(), nullptr, top_values.data(), top_docids.data(), nullptr, nullptr,
+                                    nullptr),
+                                "dint_ranked_*_sorted_queries");
+                        bool more = false;
+                        for (size_t q = 0; q != n; ++q) {
+                            if (finished[q]) continue;  // (a short page ended the query: what later calls return for it is not counted)
+                            q_counts[q] += page_counts[q];
+                            if (page_counts[q] == kTopK) {
+                                value_cursors[q] = dint_value_cursor{top_values[q * kTopK + kTopK - 1], top_docids[q * kTopK + kTopK - 1], 1u};
+                                more = true;
+                            } else {
+                                finished[q] = 1;
+                            }
+                        }
+                        if (!more) break;
+                    }
                 } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
@@ -463,7 +539,7 @@ int main(int argc, char** argv) {
                     run_queries(q.data(), offs, 1, &results, &fsum, i);
                     total += results;
                     if (run == 0) total_one_run += results;
-                    if (run == 0 && (needs_facets || is_paged)) {
+                    if (run == 0 && (needs_facets || is_paged || is_sorted)) {
                         all_matches += facet_matches[0];
                         if (is_collapsed || (is_paged && doc_facets)) all_collapsed += collapsed_counts[0];
                         for (size_t g = 0; g != facet_totals.size(); ++g) facet_totals[g] += facet_rows[g];
@@ -493,7 +569,7 @@ int main(int argc, char** argv) {
                 if (batch_total != total_one_run)
                     throw std::runtime_error("the batch call counted " + std::to_string(batch_total) + " results, the one-query calls " +
                                              std::to_string(total_one_run));
-                if (is_collapsed || is_paged) {  // ... and keep the same documents
+                if (is_collapsed || is_paged || is_sorted) {  // ... and keep the same documents
                     uint64_t batch_matches = 0, batch_collapsed = 0;
                     for (size_t q = 0; q != queries.size(); ++q)
                         batch_matches += facet_matches[q], batch_collapsed += is_collapsed || doc_facets ? collapsed_counts[q] : 0;
@@ -514,7 +590,10 @@ int main(int argc, char** argv) {
             std::cout << "{\"type\": \"" << type << "\", \"query\": \"" << t << "\", \"avg\": " << avg << ", \"q50\": " << q50
                       << ", \"q90\": " << q90 << ", \"q95\": " << q95;
             if (batch_us >= 0) std::cout << ", \"batch_us_per_query\": " << batch_us;
-            if (is_paged) {
+            if (is_sorted) {
+                std::cout << ", \"pages\": " << pages << ", \"hits\": " << total_one_run << ", \"matches\": " << all_matches << ", \"order\": \""
+                          << (sort_order == DINT_SORT_ASC ? "asc" : "desc") << "\"";
+            } else if (is_paged) {
                 std::cout << ", \"pages\": " << pages << ", \"hits\": " << total_one_run << ", \"matches\": " << all_matches;
                 if (doc_facets) std::cout << ", \"collapsed\": " << all_collapsed << ", \"n_groups\": " << n_groups;
             } else if (is_collapsed) {
@@ -528,6 +607,7 @@ int main(int argc, char** argv) {
         }
         dint_doc_facets_destroy(doc_facets);
         dint_doc_filter_destroy(doc_filter);
+        dint_doc_values_destroy(doc_values);
         dint_wand_data_destroy(wand);
         dint_wand_data_destroy(wand_blockmax);
         dint_query_index_destroy(qi);
