@@ -35,7 +35,12 @@
 //  * WAITS: gfx950 counts loads and stores in one in-order counter, so a tile has exactly one
 //    wait point — before its expansion — where everything prefetched is consumed (read-write
 //    asm barriers, so that the compiler never adds a wait behind the stores, which would be a
-//    wait for their acknowledgements).
+//    wait for their acknowledgements). With loads AND stores pending the compiler's s_waitcnt is
+//    always vmcnt(0): a wait is a wait for everything requested before it;
+//  * the STREAM is read 8 bytes a lane, a tile (512 bytes) a request, three tiles ahead. The single-dictionary
+//    segments ask for two consecutive tiles back to back at the top of every second tile (DINT_SLOT_BURST), behind the
+//    tile-top wait for the tile's metadata and not in front of it: 1 KB of consecutive stream per request point,
+//    the line two tiles share fetched once, and the tile's front end for the pair to land (kernels/segment.inc).
 //
 // LDS (160 KB/CU, one 1024-thread workgroup per CU):
 //   [ 256 u16 zeros | hot meta | hot payloads (u16) ]  <= kHotImageWords, shared by 16 waves
@@ -64,6 +69,19 @@ namespace dint_dev {
 #endif
 #ifndef DINT_MAX_STRAGGLERS
 #define DINT_MAX_STRAGGLERS 4096
+#endif
+// Tiles of slots the single-dictionary segments request per request point (kernels/segment.inc, kPaired): 2 = two
+// consecutive tiles back to back at the top of every second tile — 1 KB of consecutive stream per trip to HBM, and
+// the line two tiles share fetched once; 1 = one tile at the top of every tile (the A/B baseline).
+#ifndef DINT_SLOT_BURST
+#define DINT_SLOT_BURST 2
+#endif
+static_assert(DINT_SLOT_BURST == 1 || DINT_SLOT_BURST == 2, "DINT_SLOT_BURST: 1 or 2");
+#ifndef DINT_SLOT_GLOBAL
+#define DINT_SLOT_GLOBAL (DINT_SLOT_BURST == 2)  // those loads as global loads (load_lane_slots<true>); 0: flat loads, as before the bursts
+#endif
+#ifndef DINT_SLOT_LATE
+#define DINT_SLOT_LATE 0  // A/B only, with DINT_SLOT_BURST 1: the one-tile request behind the tile-top wait, where the pairs go
 #endif
 #ifndef DINT_GATHER_AUX
 #define DINT_GATHER_AUX 0  // cache policy of the metadata / row gathers (L2-resident tables, no reuse in L1)

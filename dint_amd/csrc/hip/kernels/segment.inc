@@ -27,9 +27,22 @@ __device__ __forceinline__ uint64_t decode_segment(const decode_args& a, const w
 
     // pipeline: tile t in `cur` (slots + metadata; the rows of its cold slots on their way into `rr`), tile
     // t+1's slots in `nxt` (its metadata requested half-way through tile t, its rows at the end of tile t),
-    // tile t+2's slots in raw2, tile t+3's requested at the top of tile t
+    // tile t+2's slots in raw2, tile t+3's requested at the top of tile t.
+    // kPaired (the single-dictionary segments, DINT_SLOT_BURST 2): the slots are requested two tiles at a time — tiles
+    // t+2 and t+3 back to back at the top of every ODD tile t, nothing at the top of the even ones (the prologue has
+    // asked for tiles 0, 1 and 2). The 128-byte line that two neighbouring tiles share is then asked for twice within
+    // a few cycles, not a tile-time (about 10 k cycles of other traffic through the L2) apart: it comes from HBM once,
+    // and HBM sees 1 KB per request point, half as many of them. An odd tile holds t+1 (nxt_raw) and the pair, an
+    // even one t+1 and t+2 (raw2, and a raw3 nobody reads): six registers of slots at the most, as before.
+    constexpr bool kPaired = DINT_SLOT_BURST == 2 && W == 16 && CHAINED_T == 0;
+    // ... and their loads are global loads (load_lane_slots<true>), not flat ones: vector memory's counter alone.
+    constexpr bool kGlobalSlots = DINT_SLOT_GLOBAL != 0 && W == 16 && CHAINED_T == 0;
+    constexpr bool kLateSlots = DINT_SLOT_LATE != 0 && W == 16 && CHAINED_T == 0;  // DINT_SLOT_BURST 1 only: see the loop top
     const uint64_t in_off_u = uniform64(in_off);
     uint64_t slot_byte = in_off_u;  // first byte of the tile whose slots are loaded next (wave-uniform)
+    // kPaired: the stream's bytes from the unit's first on, saturated to 32 bits (wave-uniform)
+    uint32_t room = 0;
+    if (kPaired && in_off_u <= a.enc_bytes) room = uniform(a.enc_bytes - in_off_u < 0xFFFFFFFFull ? uint32_t(a.enc_bytes - in_off_u) : 0xFFFFFFFFu);
     tile_regs cur;
     uint64_t nxt_raw;  // tile t+1's slots, packed as they were loaded: unpacked where they are used (two registers instead of four
                        // across the front end of tile t, where the register file is fullest)
@@ -42,11 +55,11 @@ __device__ __forceinline__ uint64_t decode_segment(const decode_args& a, const w
         slot_byte += kTileBytes;  // the pipeline is one tile shorter: tile t+2's slots are requested in tile t
     } else {
         // (all three requested before the first is looked at: one trip to memory, not two)
-        uint64_t raw0 = load_lane_slots(narrow, a.enc, slot_byte, lane, a.enc_bytes);
+        uint64_t raw0 = load_lane_slots<kGlobalSlots>(narrow, a.enc, slot_byte, lane, a.enc_bytes);
         slot_byte += kTileBytes;
-        raw1 = load_lane_slots(narrow, a.enc, slot_byte, lane, a.enc_bytes);
+        raw1 = load_lane_slots<kGlobalSlots>(narrow, a.enc, slot_byte, lane, a.enc_bytes);
         slot_byte += kTileBytes;
-        raw2 = load_lane_slots(narrow, a.enc, slot_byte, lane, a.enc_bytes);
+        raw2 = load_lane_slots<kGlobalSlots>(narrow, a.enc, slot_byte, lane, a.enc_bytes);
         asm volatile("" : "+v"(raw0), "+v"(raw1), "+v"(raw2));
         unpack_slots(narrow, raw0, cur);
     }
@@ -103,12 +116,47 @@ __device__ __forceinline__ uint64_t decode_segment(const decode_args& a, const w
         // be back before this tile's expansion (every wait is a wait for everything), so it gets the whole
         // front end. (Requested at the wait point instead, as the youngest load in flight there, it would have
         // a whole tile; measured: no gain — the kernel waits for the vector-memory front end, not for HBM.)
-        slot_byte += kTileBytes;
-        const uint64_t raw3 = load_lane_slots(narrow, a.enc, slot_byte, lane, a.enc_bytes);
+        // (Not so where the loop is kPaired, see below: in the assembly THIS request sits in front of the s_waitcnt
+        // vmcnt(0) that take_metas' barriers make the compiler write, and is waited for there, a few cycles after it went out.)
+        uint64_t raw3;
+        if (!kPaired && !kLateSlots) {
+            slot_byte += kTileBytes;
+            raw3 = load_lane_slots<kGlobalSlots>(narrow, a.enc, slot_byte, lane, a.enc_bytes);
+        }
 
         SECTION(pf, 1, "1_classify");
         // this tile's metadata: requested before the previous tile's stores (so this is no wait for them)
         take_metas(hot_k, mr, hr, cur);
+        // kPaired: the pair t+2, t+3 at the top of the odd tiles — BEHIND the wait for this tile's metadata. With stores
+        // in flight the compiler's wait is a wait for everything (loads and stores share one counter, and it counts
+        // nothing once both kinds are pending): a load requested before it is waited for on the spot, at HBM latency.
+        // Requested behind it, the pair has the tile's front end, up to the wait point, to land (the one-tile request moved
+        // here on its own, DINT_SLOT_LATE: -2.9 to -4.0 % at 10^9 postings; the pairs: -6.7 to -7.1 %). Where the pair's 1 KB
+        // does not lie inside the buffer, each load takes load_lane_slots' end-of-buffer path on its own, so the second of
+        // a pair never reads past the stream either.
+        // (t+2's slots go straight into raw2, which an odd tile finds dead — handed on to nxt_raw a tile ago —, t+3's into
+        // raw3: the rotation at the tile's end is the same for both parities, and an even tile hands on a raw3 nobody reads.
+        // The parity needs no state: an odd tile finds the last request one tile ahead of it, an even one two.)
+        if (!kPaired && kLateSlots) {  // (the A/B build that moves the one-tile request behind the wait and changes nothing else)
+            slot_byte += kTileBytes;
+            raw3 = load_lane_slots<kGlobalSlots>(narrow, a.enc, slot_byte, lane, a.enc_bytes);
+        }
+        if (kPaired) {
+            if (uint32_t(slot_byte - tile_base) == kTileBytes) {
+                const uint64_t pair_byte = slot_byte + kTileBytes;
+                slot_byte += 2 * kTileBytes;
+                // (one 32-bit test for the pair, everywhere but at the stream's end: offsets inside a unit fit 32 bits)
+                if (uint32_t(slot_byte - in_off_u) + kTileBytes <= room) {
+                    raw2 = load_lane_slots<kGlobalSlots, true>(narrow, a.enc, pair_byte, lane, a.enc_bytes);
+                    raw3 = load_lane_slots<kGlobalSlots, true>(narrow, a.enc, slot_byte, lane, a.enc_bytes);
+                } else {
+                    raw2 = load_lane_slots<kGlobalSlots>(narrow, a.enc, pair_byte, lane, a.enc_bytes);
+                    raw3 = load_lane_slots<kGlobalSlots>(narrow, a.enc, slot_byte, lane, a.enc_bytes);
+                }
+            } else {
+                asm volatile("" : "=v"(raw3));  // (no instruction: the even tiles' raw3 is whatever the registers hold)
+            }
+        }
         // ---- 1. classification: done a tile ago (kc) ----
         const bool special = kc.special;
         const uint32_t row = kc.row;
@@ -256,6 +304,7 @@ __device__ __forceinline__ uint64_t decode_segment(const decode_args& a, const w
         SECTION(pf, 8, "8_wait");
         uint64_t raw3w = raw3;
         asm volatile("" : "+v"(raw3w));
+        if (kPaired) asm volatile("" : "+v"(raw2));  // (an odd tile: the pair's first half)
         if (CHAINED) asm volatile("" : "+v"(ch.sel), "+v"(ch.data.x), "+v"(ch.data.y), "+v"(ch.data.z), "+v"(ch.data.w));
         // the heads of this tile's cold codewords into their cells (the integers start 4 bytes in); the tails
         // of the large ones requested: integers 6..13 into the same registers, 14 and 15 into one more each

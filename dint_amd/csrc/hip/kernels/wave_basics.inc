@@ -132,6 +132,20 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// How load_lane_slots addresses the stream: a generic pointer (flat loads), or one in the global address space.
+template <bool GLOBAL>
+struct slot_stream_ptr {
+    typedef const uint8_t* type;
+    typedef const u32x2_a1* x2;
+    typedef const u32_a1* x1;
+};
+template <>
+struct slot_stream_ptr<true> {
+    typedef const __attribute__((address_space(1))) uint8_t* type;
+    typedef const __attribute__((address_space(1))) u32x2_a1* x2;
+    typedef const __attribute__((address_space(1))) u32_a1* x1;
+};
+
 // kSPL consecutive slots of one lane (16-bit slots: 8 bytes; `narrow`, 8-bit slots: 4 bytes) from an
 // arbitrary byte address (SURVEY H4). `tile_byte` is the (wave-uniform) offset of the tile's
 // first slot: when the whole tile lies inside the buffer — every tile but the stream's last —
@@ -139,26 +153,39 @@ __device__ __forceinline__ void wave_lds_fence() {
 // later. Otherwise it never reads past the buffer: the tail lanes load the final bytes and
 // shift (bytes past the end read as zero), which waits for the data on the spot.
 // (`narrow` is a compile-time constant in the single-dictionary kernel and wave-uniform in the multi one.)
-__device__ __forceinline__ uint64_t load_lane_slots(bool narrow, const uint8_t* enc, uint64_t tile_byte, uint32_t lane,
+// GLOBAL: the load is a global_load, not a flat_load (`enc` reaches the kernel inside a struct, so the compiler takes it for
+// a generic pointer): a flat load in flight counts on the LDS counter as well as on vector memory's, and the compiler waits
+// for it on both.
+// INSIDE: the caller has checked that the whole tile lies inside the buffer.
+template <bool GLOBAL = false, bool INSIDE = false>
+__device__ __forceinline__ uint64_t load_lane_slots(bool narrow, const uint8_t* enc_generic, uint64_t tile_byte, uint32_t lane,
                                                     uint64_t enc_bytes) {
+    typedef typename slot_stream_ptr<GLOBAL>::type byte_ptr;
+    typedef typename slot_stream_ptr<GLOBAL>::x2 x2_ptr;
+    typedef typename slot_stream_ptr<GLOBAL>::x1 x1_ptr;
+    const byte_ptr enc = (byte_ptr)enc_generic;
     const uint32_t kBytes = narrow ? 4u : 8u;
     const uint64_t byte_off = tile_byte + uint64_t(kBytes) * lane;
-    if (tile_byte <= enc_bytes && enc_bytes - tile_byte >= uint64_t(kBytes) * kWave) {  // wave-uniform
-        if (!narrow) {
-            const u32x2 r = reinterpret_cast<const u32x2_a1*>(enc + byte_off)->v;
+    if (INSIDE || (tile_byte <= enc_bytes && enc_bytes - tile_byte >= uint64_t(kBytes) * kWave)) {  // wave-uniform
+        if (GLOBAL && !narrow) {  // (the wave-uniform part of the address first, then the lane's 32-bit offset)
+            const u32x2 r = ((x2_ptr)((enc + tile_byte) + kBytes * lane))->v;
             return (uint64_t(r.y) << 32) | r.x;
         }
-        return reinterpret_cast<const u32_a1*>(enc + byte_off)->v;
+        if (!narrow) {
+            const u32x2 r = ((x2_ptr)(enc + byte_off))->v;
+            return (uint64_t(r.y) << 32) | r.x;
+        }
+        return ((x1_ptr)(enc + byte_off))->v;
     }
     const uint64_t last_valid = enc_bytes - kBytes;  // enc_bytes >= 8 is checked by the host
     const uint64_t o = byte_off < last_valid ? byte_off : last_valid;
     const uint64_t over = byte_off - o;  // 0 for all but the tail lanes
     uint64_t q;
     if (!narrow) {
-        const u32x2 r = reinterpret_cast<const u32x2_a1*>(enc + o)->v;
+        const u32x2 r = ((x2_ptr)(enc + o))->v;
         q = (uint64_t(r.y) << 32) | r.x;
     } else {
-        q = reinterpret_cast<const u32_a1*>(enc + o)->v;
+        q = ((x1_ptr)(enc + o))->v;
     }
     return over < kBytes ? q >> (8 * uint32_t(over)) : 0ull;
 }
