@@ -34,6 +34,10 @@
 // sorted_hits_kernel behind it, both over the pass's slots at the pass's query offset; the cursor keys and flags go up and the
 // counters and hit scores are cleared once per call, and come back with the last pass. Without sv nothing is planned or
 // launched differently.
+// vs (dint_ranked_or_value_stats_queries, hip_api_value_stats.inc), with rk and with rg or fl: the pass's page -> query table is
+// staged as for fa, and value_stats_kernel runs between the scoring launch and ranked_topk, over the pass's slots at the pass's
+// query offset, hit_values_kernel behind the selection over the pass's keys; the records and the edges go up and the rows and
+// hit values are cleared once per call, and come back with the last pass. Without vs nothing is planned or launched differently.
 
 // What a ranked OR call with a minimum and exclusions adds to its passes, and what it gets back.
 struct or_bool_args {
@@ -97,10 +101,13 @@ struct or_pass_query {
 // pg (with rk; its keys up and its counters cleared): or_facet_layout staged as for fa, page_after_kernel in front of the selection.
 // sv (with rk; its keys up, its counters and hit scores cleared): or_facet_layout staged as for fa, value_after_kernel in front of
 // the selection, which runs by value, sorted_hits_kernel behind it.
+// vs (with rk; its records and edges up, its rows and hit values cleared): or_facet_layout staged as for fa, value_stats_kernel
+// behind the scoring launch, hit_values_kernel behind the selection.
 static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const ranked_args* rk, const std::vector<or_pass_query>& qs,
                        size_t min_stage, unsigned long long* d_counts, size_t n_counts, uint32_t id0, size_t n_ids, hipStream_t s,
                        or_bool_args* xb = nullptr, bool ranged = false, const filter_args* fl = nullptr, const facet_args* fa = nullptr,
-                       const collapse_args* ca = nullptr, const page_args* pg = nullptr, const sort_args* sv = nullptr) {
+                       const collapse_args* ca = nullptr, const page_args* pg = nullptr, const sort_args* sv = nullptr,
+                       const value_stats_args* vs = nullptr) {
     uint64_t n_pages = 0, n_terms = 0;
     for (const or_pass_query& q : qs) {
         n_terms += q.n;
@@ -113,8 +120,8 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
             if (q.n) n_steps = std::max<size_t>(n_steps, xb->not_at[q.id + 1] - xb->not_at[q.id]);
     const or_bool_layout B(L.words, xb ? n_pages : 0, xb ? n_terms : 0, n_steps * n_ids, n_steps);
     const or_range_layout R(B.words, ranged ? n_terms : 0);
-    const or_facet_layout F(R.words, fa || pg || sv ? n_pages : 0);
-    const size_t up_words = F.words;  // (without xb, fa, pg and sv and not ranged: L.words)
+    const or_facet_layout F(R.words, fa || pg || sv || vs ? n_pages : 0);
+    const size_t up_words = F.words;  // (without xb, fa, pg, sv and vs and not ranged: L.words)
     if (qi->stage(std::max<size_t>(up_words * 4, min_stage)) != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     uint32_t *page_block = qi->h(L.page_block), *page_term = qi->h(L.page_term), *term_order = qi->h(L.term_order);
     std::vector<uint32_t> page_query(rk ? n_pages : 0);  // (ranked_topk's: the pass's queries, from 0)
@@ -145,7 +152,7 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
             }
         }
     }
-    if ((fa || pg || sv) && n_pages) std::memcpy(qi->h(F.page_query), page_query.data(), n_pages * 4);
+    if ((fa || pg || sv || vs) && n_pages) std::memcpy(qi->h(F.page_query), page_query.data(), n_pages * 4);
     if (xb) {
         if (n_pages) std::memcpy(qi->h(B.page_query), page_query.data(), n_pages * 4);
         std::memset(qi->h(B.not_first), 0, (B.words - B.not_first) * 4);
@@ -233,6 +240,7 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
         if (hipGetLastError() != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     }
     if (fa && facet_count_launch(qi, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
+    if (vs && value_stats_launch(qi, vs, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (ca && collapse_launch(qi, ca, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (pg && page_after_launch(qi, pg, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (sv && value_after_launch(qi, sv, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
@@ -240,6 +248,7 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
     if (rst != DINT_OK) return stream_failed(s, rst);
     if (ca && collapse_hits_launch(qi, ca, fa, n_ids, id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (sv && sorted_hits_launch(qi, sv, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
+    if (vs && hit_values_launch(qi, vs, n_ids, id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     return DINT_OK;
 }
 
@@ -247,7 +256,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream,
                            const ranked_args* rk = nullptr, or_bool_args* xb = nullptr, range_args* rg = nullptr,
                            filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr, page_args* pg = nullptr,
-                           sort_args* sv = nullptr) {
+                           sort_args* sv = nullptr, value_stats_args* vs = nullptr) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -273,6 +282,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     collapse_begin(ca, n_queries);
     page_begin(pg, n_queries);
     sort_begin(sv, n_queries);
+    value_stats_begin(vs, n_queries);
     if (op.all == 0) return DINT_OK;
 
     std::lock_guard<std::mutex> lock(qi->mutex);
@@ -293,6 +303,10 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     if (sv) {
         const int begun = sort_begin_device(qi, sv, n_queries, s);
         if (begun != DINT_OK) return begun;
+    }
+    if (vs) {
+        const int cleared = value_stats_clear(qi, vs, n_queries, s);
+        if (cleared != DINT_OK) return cleared;
     }
     // the call's counters: counts[n_queries] then freq sums[n_queries], cleared once, added to by every pass
     if (!qi->freq_sums.ensure(2 * n_queries)) return DINT_ERR_HIP;
@@ -319,13 +333,14 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         ranked_args pass_rk = rk ? *rk : ranked_args{};
         if (rk) pass_rk.keys += uint64_t(q0) * rk->k;  // (the keys of the pass's queries at their own offset)
         const int st = or_run_pass(qi, freqs_dict, rk ? &pass_rk : nullptr, qs, 2 * n_queries * sizeof(unsigned long long), d_counts,
-                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl, fa, ca, pg, sv);
+                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl, fa, ca, pg, sv, vs);
         if (st != DINT_OK) return st;
     }
     if (fa && facet_rows_back(fa, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (ca && collapse_back(ca, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (pg && page_back(pg, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (sv && sort_back(sv, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
+    if (vs && value_stats_back(vs, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (fl) HIP_TRY(hipMemcpyAsync(fl->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (rg) HIP_TRY(hipMemcpyAsync(rg->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (xb) HIP_TRY(hipMemcpyAsync(xb->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));

@@ -340,6 +340,75 @@ static int sort_back(sort_args* sv, size_t n_queries, hipStream_t s) {
     return DINT_OK;
 }
 
+// A value-stats call (hip_api_value_stats.inc): the column and the bucket boundaries, where the call's records, rows and hit
+// values go on the host, and where they live on the device — two grow-only workspaces of the query index: the records, 24
+// bytes per query, and behind one another the edges, the rows (n_queries * (n_edges + 1) counters) and the hit values
+// (n_queries * k words). The records go up as the empty record, the edges go up and the rest is cleared once per call under
+// the lock (value_stats_clear), every pass adds, and everything comes back once. Where a call takes a null one nothing is
+// planned or launched differently.
+struct value_stats_args {
+    const dint_doc_values* values = nullptr;
+    const uint32_t* edges = nullptr;  // host, n_edges words, strictly ascending (checked by the entry)
+    uint32_t n_edges = 0, k = 0;
+    dint_value_stats* h_stats = nullptr;  // the caller's, n_queries
+    uint32_t* h_rows = nullptr;           // the caller's bucket_counts (n_edges == 0: not touched)
+    uint32_t* h_hit_values = nullptr;     // the caller's, n_queries * k, or null: hit_values_kernel does not run
+    value_stats_rec* d_stats = nullptr;   // (set by value_stats_clear)
+    uint32_t *d_edges = nullptr, *d_rows = nullptr, *d_hit_values = nullptr;
+    size_t row_words(size_t n_queries) const { return n_edges ? n_queries * (size_t(n_edges) + 1) : 0; }
+    size_t hit_words(size_t n_queries) const { return h_hit_values ? n_queries * k : 0; }
+};
+static_assert(sizeof(dint_value_stats) == sizeof(value_stats_rec) && offsetof(dint_value_stats, min) == offsetof(value_stats_rec, min),
+              "the records travel as the caller's struct");
+// the call is planned and has refused nothing: every record is empty, every row and hit value zero until a pass says otherwise
+static void value_stats_begin(const value_stats_args* vs, size_t n_queries) {
+    if (!vs) return;
+    std::fill(vs->h_stats, vs->h_stats + n_queries, dint_value_stats{0, 0, 0xFFFFFFFFu, 0});
+    if (vs->n_edges) std::fill(vs->h_rows, vs->h_rows + vs->row_words(n_queries), 0u);
+    if (vs->h_hit_values) std::fill(vs->h_hit_values, vs->h_hit_values + vs->hit_words(n_queries), 0u);
+}
+// under the index's lock, once per call, in front of its first launch: the empty records (the caller's own, as
+// value_stats_begin left them) and the edges go up, the rows and the hit values clear
+static int value_stats_clear(dint_query_index* qi, value_stats_args* vs, size_t n_queries, hipStream_t s) {
+    const size_t n_rows = vs->row_words(n_queries), n_hits = vs->hit_words(n_queries);
+    if (!qi->value_stats_recs.ensure(3 * n_queries) || !qi->value_stats_words.ensure(vs->n_edges + n_rows + n_hits)) return DINT_ERR_HIP;
+    vs->d_stats = reinterpret_cast<value_stats_rec*>(qi->value_stats_recs.p);
+    vs->d_edges = qi->value_stats_words.p;
+    vs->d_rows = vs->d_edges + vs->n_edges;
+    vs->d_hit_values = vs->d_rows + n_rows;
+    // (pageable host memory: the copies have left the caller's arrays when the call returns, and the call waits on the stream
+    // before it does)
+    HIP_TRY(hipMemcpyAsync(vs->d_stats, vs->h_stats, n_queries * sizeof(value_stats_rec), hipMemcpyHostToDevice, s));
+    if (vs->n_edges) HIP_TRY(hipMemcpyAsync(vs->d_edges, vs->edges, size_t(vs->n_edges) * 4, hipMemcpyHostToDevice, s));
+    if (n_rows + n_hits) HIP_TRY(hipMemsetAsync(vs->d_rows, 0, (n_rows + n_hits) * 4, s));
+    return DINT_OK;
+}
+// value_stats_kernel over the n_pages pages of qi->cand, in front of ranked_topk; d_page_query[page] + q0: the page's query of
+// the call
+static int value_stats_launch(const dint_query_index* qi, const value_stats_args* vs, uint64_t n_pages, const uint32_t* d_page_query,
+                              uint32_t q0, hipStream_t s) {
+    hipLaunchKernelGGL(value_stats_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, n_pages * kPageSlots, d_page_query, q0,
+                       vs->values->view(), vs->d_edges, vs->n_edges, vs->d_stats, vs->d_rows);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// hit_values_kernel behind ranked_topk, over the keys it selected for the n_ids queries from q0 on (qi->topk_out). A call that
+// asks for no hit values launches nothing.
+static int hit_values_launch(const dint_query_index* qi, const value_stats_args* vs, size_t n_ids, uint32_t q0, hipStream_t s) {
+    if (!vs->h_hit_values) return DINT_OK;
+    const uint64_t n_out = uint64_t(n_ids) * vs->k;
+    hipLaunchKernelGGL(hit_values_kernel, dim3(uint32_t((n_out + 255) / 256)), dim3(256), 0, s, qi->topk_out.p, uint32_t(n_ids), vs->k, q0,
+                       vs->values->view(), vs->d_hit_values);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// ... and the records', the rows' and the hit values' way back, on the stream, in front of the call's last wait
+static int value_stats_back(const value_stats_args* vs, size_t n_queries, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(vs->h_stats, vs->d_stats, n_queries * sizeof(value_stats_rec), hipMemcpyDeviceToHost, s));
+    if (vs->n_edges) HIP_TRY(hipMemcpyAsync(vs->h_rows, vs->d_rows, vs->row_words(n_queries) * 4, hipMemcpyDeviceToHost, s));
+    if (vs->h_hit_values)
+        HIP_TRY(hipMemcpyAsync(vs->h_hit_values, vs->d_hit_values, vs->hit_words(n_queries) * 4, hipMemcpyDeviceToHost, s));
+    return DINT_OK;
+}
+
 // the *_queries_freqs entries: a freqs dictionary of the index's device and kind, and somewhere for the sums
 static bool freqs_args_ok(const dint_query_index* qi, const dint_dict* freqs_dict, const uint64_t* freq_sums) {
     return freqs_dict && freq_sums && (!qi || (freqs_dict->device == qi->docs->device && freqs_dict->kind == qi->docs->kind));

@@ -80,6 +80,10 @@ struct dint_query_index {
     // matches that are not after it; per query whether it has a cursor and behind them per (query, i) the hit's score
     device_buffer<unsigned long long> sort_keys;
     device_buffer<uint32_t> sort_words;
+    // the value-stats ranked calls (hip_api_value_stats.inc): per query of the call its record, three 64-bit words; the
+    // call's edges and behind them per query a row of n_edges + 1 counters, then per (query, i) the hit's value
+    device_buffer<unsigned long long> value_stats_recs;
+    device_buffer<uint32_t> value_stats_words;
     // dint_check_index (hip_api_check.inc): every block of a list but its last holds 256 postings (the in-index layout:
     // block j of a list is its positions [256 j, 256 j + n)); two pinned staging buffers of a pass's expected postings
     // and their device copies, alternating

@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "dint_ranked_or_collapsed_paged_queries", "dint_ranked_and_collapsed_paged_queries",
     "dint_doc_values_create", "dint_doc_values_info_get", "dint_doc_values_destroy", "dint_doc_filter_create_from_values",
     "dint_ranked_or_sorted_queries", "dint_ranked_and_sorted_queries",
+    "dint_ranked_or_value_stats_queries", "dint_ranked_and_value_stats_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_check_index", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -199,6 +200,10 @@ def _load():
     lib.dint_doc_filter_create_from_values.argtypes = [vp, vp, u32, u32, C.POINTER(vp)]
     lib.dint_ranked_or_sorted_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_and_sorted_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    # (qi, freqs, wand, k, terms, offsets, filter, values, edges, n_edges, n_queries, counts, matches, scores, docids, stats,
+    # bucket_counts, hit_values, blocks_decoded, stream)
+    lib.dint_ranked_or_value_stats_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_value_stats_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
@@ -992,6 +997,45 @@ class QueryIndex:
         ranked_or_sorted_queries, over the intersection."""
         return self._ranked_sorted("dint_ranked_and_sorted_queries", freqs_dict, wand, queries, values, descending, after, filter, k, with_stats)
 
+    def _ranked_value_stats(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, values, edges, doc_filter, k: int,
+                            with_stats: bool):
+        edges = _pack_value_edges(edges)
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        stats = np.zeros(n, dtype=_VALUE_STATS)
+        buckets = np.zeros((n, edges.size + 1), dtype=np.uint32) if edges.size else None
+        hit_values = np.zeros((n, k), dtype=np.uint32)
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 doc_filter._h if doc_filter is not None else None, values._h, edges.ctypes.data if edges.size else None,
+                                 edges.size, n, counts.ctypes.data, matches.ctypes.data, scores.ctypes.data, docids.ctypes.data,
+                                 stats.ctypes.data, buckets.ctypes.data if buckets is not None else None, hit_values.ctypes.data,
+                                 C.byref(blocks), self._stream()), fn)
+        head = (counts, scores, docids, matches, blocks.value) if with_stats else (counts, scores, docids)
+        return head + (stats, buckets, hit_values)
+
+    def ranked_or_value_stats_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, values: "DocValues", edges=None,
+                                      filter=None, k: int = 10, with_stats: bool = False):
+        """ranked_or_filtered_queries with a column reduced over every match (dint_ranked_or_value_stats_queries, DESIGN.md
+        4d-stats): values is a DocValues on this index's device, edges None or up to 1023 strictly ascending u32 bucket
+        boundaries (ValueError otherwise, before the call), filter a DocFilter of this index or None (unrestricted) -> what
+        ranked_or_filtered_queries returns for (queries, filter, k, with_stats), bit for bit, and behind it stats (a structured
+        array of n records with the fields n, sum, min, max over the matches d < values.num_docs — matches at or past the
+        column have no value; no valued match: (0, 0, 0xFFFFFFFF, 0)), buckets u32[n, n_edges + 1] (None without edges):
+        buckets[q, b] = the valued matches of q with b edges <= their value, and hit_values u32[n, k]: the values of the
+        hits (0 past the count and for a hit past the column)."""
+        return self._ranked_value_stats("dint_ranked_or_value_stats_queries", freqs_dict, wand, queries, values, edges, filter, k, with_stats)
+
+    def ranked_and_value_stats_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, values: "DocValues", edges=None,
+                                       filter=None, k: int = 10, with_stats: bool = False):
+        """ranked_and_filtered_queries with a column reduced over every match (dint_ranked_and_value_stats_queries): arguments
+        and outputs as ranked_or_value_stats_queries, over the intersection."""
+        return self._ranked_value_stats("dint_ranked_and_value_stats_queries", freqs_dict, wand, queries, values, edges, filter, k, with_stats)
+
     def ranked_pages(self, entry: str, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10, filter=None, facets=None,
                      after=None, max_pages=None, values=None, descending: bool = True):
         """Walks a batch page by page: entry is "or", "and", "or_collapsed" or "and_collapsed" (the
@@ -1383,6 +1427,26 @@ def _pack_value_cursors(after, n: int):
             raise ValueError(f"cursor {i}: ({value}, {docid}) are not u32")
         out[i] = (int(value), int(docid), 1)
     return out
+
+
+#: dint_value_stats (include/dint_hip.h): 24 bytes
+_VALUE_STATS = np.dtype([("n", np.uint64), ("sum", np.uint64), ("min", np.uint32), ("max", np.uint32)])
+VALUE_STATS_MAX_EDGES = 1023
+
+
+def _pack_value_edges(edges):
+    """-> the bucket boundaries as a contiguous u32 array (None: none). ValueError for more than VALUE_STATS_MAX_EDGES, for a
+    value outside 0 .. 2^32 - 1 and for edges that are not strictly ascending."""
+    if edges is None:
+        return np.zeros(0, dtype=np.uint32)
+    e = [int(x) for x in np.asarray(edges).reshape(-1).tolist()]
+    if len(e) > VALUE_STATS_MAX_EDGES:
+        raise ValueError(f"value edges: at most {VALUE_STATS_MAX_EDGES}, not {len(e)}")
+    if any(x < 0 or x > 0xFFFFFFFF for x in e):
+        raise ValueError("value edges: every edge must lie in 0 .. 2^32 - 1")
+    if any(a >= b for a, b in zip(e, e[1:])):
+        raise ValueError("value edges: must be strictly ascending")
+    return np.array(e, dtype=np.uint32)
 
 
 def _pack_queries(queries):

@@ -887,6 +887,61 @@ int dint_ranked_and_sorted_queries(dint_query_index* qi, const dint_dict* freqs_
                                    uint64_t* counts, uint64_t* matches, uint64_t* skipped, uint32_t* hit_values, uint32_t* docids, float* scores,
                                    uint64_t* blocks_decoded, void* stream);
 
+/* ---- value statistics and range histograms of the ranked queries (how the matches are distributed over a column) ----
+ * Adds: what a cursor engine computes with a stats / range-aggregation collector beside its top-k collector (ranked_or_query /
+ * ranked_and_query, include/ds2i/queries.hpp:309-457, have none) — per query the number, the sum, the minimum and the maximum
+ * of a column's values over the query's matches and how many of them fall between caller-given bucket boundaries ("under 10,
+ * 10-50, 50-200, above", a date histogram, the newest and the oldest match), for a batch of queries, in the call that ranks
+ * them. Quantising the column into a facets map costs a 4-byte-per-document map per choice of boundaries and gives no min, max
+ * or sum; aggregating fetched hits on the host is wrong as soon as a query has more than DINT_RANKED_MAX_K matches.
+ * dint_ranked_or_value_stats_queries / dint_ranked_and_value_stats_queries take the arguments of the filtered calls (filter
+ * nullable: unrestricted), the column (a dint_doc_values), edges (HOST, n_edges strictly ascending bucket boundaries;
+ * n_edges == 0: no histogram, edges and bucket_counts are ignored and may be null) and the outputs (HOST):
+ *   counts, matches, scores, docids, *blocks_decoded   bit for bit what dint_ranked_or_filtered_queries /
+ *                    dint_ranked_and_filtered_queries return for the same arguments (filter null: the unfiltered answer with
+ *                    the matches counted); the plan depends neither on the column nor on the edges; docids is nullable
+ *   stats[q]         over EVERY match of query q that has a value, not over the top k. A match d HAS A VALUE iff d < the
+ *                    column's num_docs, and the value is v(d); a match at or past the column has none and enters neither the
+ *                    statistics nor any bucket — UNLIKE the sorted calls above, which give such a document the value 0 because
+ *                    they must order it. So matches[q] - stats[q].n is the number of matches without a value. The sum is
+ *                    64-bit and cannot overflow (fewer than 2^32 matches, each value below 2^32). An empty query, or one
+ *                    without a valued match: {0, 0, 0xFFFFFFFF, 0}
+ *   bucket_counts[q * (n_edges + 1) + b]  the valued matches of q in bucket b, bucket(v) = the number of edges e with e <= v:
+ *                    bucket b holds edges[b - 1] <= v < edges[b], bucket 0 the values below edges[0], bucket n_edges the values
+ *                    at or above the last edge. The row's sum equals stats[q].n
+ *   hit_values[q * k + i]  (nullable) v(docids[q * k + i]) for i < counts[q] where that document has a value; 0 past the count
+ *                    and for a hit at or past the column. Gathered on the device behind the selection; docids may be null
+ *                    while hit_values is not
+ * Every quantity is an integer sum, minimum or maximum: exact, order-independent and the same from run to run.
+ * DINT_ERR_ARG, before anything is written or launched: whatever the filtered calls refuse; a null values or one on another
+ * device than the index; a null stats; n_edges > DINT_VALUE_STATS_MAX_EDGES; n_edges > 0 with a null edges or bucket_counts;
+ * edges that are not strictly ascending; n_queries * (n_edges + 1) > 2^28 (the caller batches). Terms, query_offsets, the
+ * handle's lock and the stream are as for the filtered calls. The records (24 bytes per query, initialised to the empty
+ * record), and the edges, the rows and the hit values (4 bytes * (n_edges + n_queries * (n_edges + 1 + k))) are grow-only
+ * workspaces of the query index, sent and cleared once per call and copied back once. Besides the filtered call's launches a
+ * call runs one launch over the candidate slots in front of the selection per OR pass / per AND call, which gathers one word
+ * of the column per live slot and reduces in LDS — at most one global add per bucket present in a page and four atomics on the
+ * query's record — and, if hit_values is given, one over the selected keys behind it.
+ * Percentiles, sums or means of scores (float sums are not order-independent), statistics per facet group, several columns per
+ * call and the boolean, pruned, collapsed and paged forms are out of scope. */
+#define DINT_VALUE_STATS_MAX_EDGES 1023u
+typedef struct dint_value_stats { /* 24 bytes: offsets 0, 8, 16, 20 */
+    uint64_t n;   /* matches that have a value */
+    uint64_t sum; /* the sum of their values   */
+    uint32_t min; /* 0xFFFFFFFF if n == 0      */
+    uint32_t max; /* 0 if n == 0               */
+} dint_value_stats;
+int dint_ranked_or_value_stats_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                       const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                       const dint_doc_values* values, const uint32_t* edges, uint32_t n_edges, size_t n_queries,
+                                       uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids, dint_value_stats* stats,
+                                       uint32_t* bucket_counts, uint32_t* hit_values, uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_value_stats_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                        const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                        const dint_doc_values* values, const uint32_t* edges, uint32_t n_edges, size_t n_queries,
+                                        uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids, dint_value_stats* stats,
+                                        uint32_t* bucket_counts, uint32_t* hit_values, uint64_t* blocks_decoded, void* stream);
+
 /* ---- the wand data's BM25 maxima from the index, on the device; block maxima for the pruned call --------------
  * Replaces: the max_term_weight half of wand_data's constructor (include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp),
  * which walks the uncompressed collection posting by posting, by one decode of the INDEX: a caller that has only what this

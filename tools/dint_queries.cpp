@@ -1,12 +1,13 @@
 // dint_queries — the reference's `queries` tool (src/queries.cpp:15-153) for the DINT index types, on the device path.
 //
 //   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N]
-//                [--values FILE] [--order asc|desc] [--value-range lo:hi] < query_log
+//                [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
 //   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
 //               ranked_or_bool | ranked_or_range | ranked_and_range | ranked_or_filtered | ranked_and_filtered |
 //               ranked_or_faceted | ranked_and_faceted | ranked_or_collapsed | ranked_and_collapsed | ranked_or_paged |
-//               ranked_and_paged | ranked_or_sorted | ranked_and_sorted, several separated by ':'
+//               ranked_and_paged | ranked_or_sorted | ranked_and_sorted | ranked_or_value_stats | ranked_and_value_stats, several
+//               separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
@@ -60,6 +61,13 @@
 //               interval, found on the device: dint_doc_filter_create_from_values), not both; each must be the only type
 //               of its run; the result counts are the hits summed over the pages, and the JSON line carries besides
 //               "pages", "hits", "matches" and "order";
+//               ranked_or_value_stats / ranked_and_value_stats (dint_ranked_or_value_stats_queries,
+//               dint_ranked_and_value_stats_queries: ranked_or / ranked_and with a column's values reduced over every match,
+//               DESIGN.md 4d-stats) need --values FILE as the sorted types do and take --edges e1,e2,... — up to 1023 strictly
+//               ascending decimal bucket boundaries (value_edges.hpp) — and either --filter FILE or --value-range lo:hi; each
+//               must be the only type of its run; the query lines, output and keys are ranked_or's, and the JSON line carries
+//               besides "matches", "value_n" and "value_sum" (totals over the log), "value_min" and "value_max" (over the
+//               log; 4294967295 and 0 if no match has a value) and "buckets" (per bucket the log's total; [] without --edges);
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -88,6 +96,7 @@
 #include "doc_filter_file.hpp"
 #include "doc_values_file.hpp"
 #include "tool_common.hpp"
+#include "value_edges.hpp"
 
 static void dint_ok(int st, const char* what) {
     if (st != DINT_OK) throw std::runtime_error(std::string(what) + ": " + dint_strerror(st) + " " + dint_last_hip_error());
@@ -98,7 +107,7 @@ static double now_us() {
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N] [--values FILE] [--order asc|desc] [--value-range lo:hi] < query_log"
+        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N] [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] < query_log"
                   << std::endl;
         return 1;
     }
@@ -111,6 +120,7 @@ int main(int argc, char** argv) {
         const char* values_filename = nullptr;
         const char* value_range = nullptr;  // ranked_*_sorted: lo:hi, the run's filter from the column
         std::string order_name;             // ranked_*_sorted: asc | desc ("": not given)
+        const char* edges_text = nullptr;   // ranked_*_value_stats: the bucket boundaries
         bool batch = false;
         size_t runs = 10 + 1;  // src/queries.cpp:13
         size_t pages = 0;      // ranked_*_paged: the pages walked per query (0: not given)
@@ -123,6 +133,7 @@ int main(int argc, char** argv) {
             else if (a == "--values" && i + 1 < argc) values_filename = argv[++i];
             else if (a == "--order" && i + 1 < argc) order_name = argv[++i];
             else if (a == "--value-range" && i + 1 < argc) value_range = argv[++i];
+            else if (a == "--edges" && i + 1 < argc) edges_text = argv[++i];
             else if (a == "--pages" && i + 1 < argc) pages = size_t(std::max(1, std::atoi(argv[++i])));
             else if (!wand_filename && a.rfind("--", 0) != 0) wand_filename = argv[i];
             else throw std::runtime_error("unknown parameter");
@@ -169,12 +180,18 @@ int main(int argc, char** argv) {
         for (const char* sorted : {"ranked_or_sorted", "ranked_and_sorted"})
             if (!is_sorted && (":" + query_type + ":").find(std::string(":") + sorted + ":") != std::string::npos)
                 throw std::runtime_error(std::string(sorted) + " walks its whole log page by page under --values: it must be the only query type of a run");
+        const bool is_vstats = query_type == "ranked_or_value_stats" || query_type == "ranked_and_value_stats";
+        for (const char* vstats : {"ranked_or_value_stats", "ranked_and_value_stats"})
+            if (!is_vstats && (":" + query_type + ":").find(std::string(":") + vstats + ":") != std::string::npos)
+                throw std::runtime_error(std::string(vstats) + " answers its whole log under --values: it must be the only query type of a run");
         if (!is_paged && !is_sorted && pages) throw std::runtime_error("--pages goes with ranked_or_paged, ranked_and_paged, ranked_or_sorted and ranked_and_sorted only");
         if (is_paged && !pages) pages = 2;
         if (is_sorted && !pages) pages = 1;
-        if (!is_sorted && (values_filename || value_range || !order_name.empty()))
+        if (!is_sorted && !is_vstats && (values_filename || value_range || !order_name.empty()))
             throw std::runtime_error("--values, --order and --value-range go with ranked_or_sorted and ranked_and_sorted only");
-        if (is_sorted && !values_filename) {
+        if (is_vstats && !order_name.empty()) throw std::runtime_error("--order goes with ranked_or_sorted and ranked_and_sorted only");
+        if (!is_vstats && edges_text) throw std::runtime_error("--edges goes with ranked_or_value_stats and ranked_and_value_stats only");
+        if ((is_sorted || is_vstats) && !values_filename) {
             std::cerr << query_type << " needs --values FILE (every line `d v` or `lo:hi v`: document d, or every document of [lo, hi), has value v)"
                       << std::endl;
             return 1;
@@ -183,17 +200,20 @@ int main(int argc, char** argv) {
         const uint32_t sort_order = order_name == "asc" ? DINT_SORT_ASC : DINT_SORT_DESC;
         if (value_range && filter_filename) throw std::runtime_error("--value-range and --filter exclude each other: a run has one filter");
         if (is_sorted && facets_filename) throw std::runtime_error("--facets does not go with the ranked_*_sorted types");
+        if (is_vstats && facets_filename) throw std::runtime_error("--facets does not go with the ranked_*_value_stats types");
+        std::vector<uint32_t> value_edges;
+        if (edges_text) value_edges = tool::parse_value_edges(edges_text);
         uint32_t range_lo = 0, range_hi = 0;
         if (value_range) tool::parse_value_range(value_range, range_lo, range_hi);
         tool::doc_values_column values_column;
-        if (is_sorted) {
+        if (is_sorted || is_vstats) {
             std::ifstream vf(values_filename);
             if (!vf) throw std::runtime_error(std::string("could not open the values file ") + values_filename);
             values_column = tool::parse_doc_values(vf);
         }
         if (!needs_facets && !is_paged && facets_filename)
             throw std::runtime_error("--facets goes with the ranked_*_faceted, ranked_*_collapsed and ranked_*_paged types only");
-        if (!is_filtered && !needs_facets && !is_paged && !is_sorted && filter_filename)
+        if (!is_filtered && !needs_facets && !is_paged && !is_sorted && !is_vstats && filter_filename)
             throw std::runtime_error("--filter goes with the ranked_*_filtered, ranked_*_faceted, ranked_*_collapsed, ranked_*_paged and ranked_*_sorted types only");
         const bool uses_facets = needs_facets || (is_paged && facets_filename);  // (a paged type: the collapsed paged entry)
         tool::doc_facets_map facets_map;
@@ -323,8 +343,8 @@ int main(int argc, char** argv) {
         }
         dint_doc_filter* doc_filter = nullptr;  // ranked_*_filtered: the run's filter
         if (filter_filename) dint_ok(dint_doc_filter_create(qi, filter_bits.words.data(), filter_bits.num_docs, &doc_filter), "dint_doc_filter_create");
-        dint_doc_values* doc_values = nullptr;  // ranked_*_sorted: the run's column, and with --value-range the filter from it
-        if (is_sorted) {
+        dint_doc_values* doc_values = nullptr;  // ranked_*_sorted, ranked_*_value_stats: the run's column, and with --value-range the filter from it
+        if (is_sorted || is_vstats) {
             dint_ok(dint_doc_values_create(0, values_column.values.data(), values_column.num_docs, &doc_values), "dint_doc_values_create");
             if (value_range) dint_ok(dint_doc_filter_create_from_values(qi, doc_values, range_lo, range_hi, &doc_filter), "dint_doc_filter_create_from_values");
         }
@@ -347,6 +367,10 @@ int main(int argc, char** argv) {
         // ranked_*_sorted: a page's values beside them, and every query's cursor — (value, docid) of its last hit
         std::vector<uint32_t> top_values;
         std::vector<dint_value_cursor> value_cursors;
+        // ranked_*_value_stats: a call's records and bucket rows
+        std::vector<dint_value_stats> value_stats;
+        std::vector<uint32_t> bucket_rows;
+        const size_t n_buckets = value_edges.empty() ? 0 : value_edges.size() + 1;
 
         std::vector<std::string> types;
         for (size_t a = 0; a <= query_type.size();) {
@@ -367,7 +391,8 @@ int main(int argc, char** argv) {
             const bool is_or_collapsed = t == "ranked_or_collapsed" && wand, is_and_collapsed = t == "ranked_and_collapsed" && wand;
             const bool is_or_paged = t == "ranked_or_paged" && wand, is_and_paged = t == "ranked_and_paged" && wand;
             const bool is_or_sorted = t == "ranked_or_sorted" && wand, is_and_sorted = t == "ranked_and_sorted" && wand;
-            const bool is_ranked = (t == "ranked_and" && wand) || is_or_sorted || is_and_sorted || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
+            const bool is_or_vstats = t == "ranked_or_value_stats" && wand, is_and_vstats = t == "ranked_and_value_stats" && wand;
+            const bool is_ranked = (t == "ranked_and" && wand) || is_or_vstats || is_and_vstats || is_or_sorted || is_and_sorted || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
                                    is_or_range || is_and_range || is_or_filtered || is_and_filtered || is_or_faceted || is_and_faceted ||
                                    is_or_collapsed || is_and_collapsed;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
@@ -503,6 +528,16 @@ int main(int argc, char** argv) {
                         }
                         if (!more) break;
                     }
+                } else if (is_or_vstats || is_and_vstats) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    facet_matches.resize(n);
+                    value_stats.resize(n);
+                    bucket_rows.resize(n * n_buckets);
+                    dint_ok((is_or_vstats ? dint_ranked_or_value_stats_queries : dint_ranked_and_value_stats_queries)(
+                                qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_values, value_edges.data(), uint32_t(value_edges.size()),
+                                n, q_counts, facet_matches.data(), top_scores.data(), nullptr, value_stats.data(), bucket_rows.data(), nullptr,
+                                nullptr, nullptr),
+                            "dint_ranked_*_value_stats_queries");
                 } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
@@ -530,6 +565,18 @@ int main(int argc, char** argv) {
             // a faceted type: per group the matches of the log's queries in it, and every match of the log (the first run's)
             std::vector<uint64_t> facet_totals(is_faceted ? n_groups : 0, 0);
             uint64_t all_matches = 0, all_collapsed = 0;  // (a collapsed type: every kept document of the log besides)
+            // a value-stats type: the log's records merged and per bucket the log's total (the first run's)
+            dint_value_stats log_stats{0, 0, 0xFFFFFFFFu, 0};
+            std::vector<uint64_t> bucket_totals(is_vstats ? n_buckets : 0, 0);
+            auto merge_stats = [&](dint_value_stats& into, std::vector<uint64_t>& buckets, size_t n) {
+                for (size_t q = 0; q != n; ++q) {
+                    into.n += value_stats[q].n;
+                    into.sum += value_stats[q].sum;
+                    into.min = std::min(into.min, value_stats[q].min);
+                    into.max = std::max(into.max, value_stats[q].max);
+                    for (size_t b = 0; b != n_buckets; ++b) buckets[b] += bucket_rows[q * n_buckets + b];
+                }
+            };
             for (size_t run = 0; run != runs; ++run) {  // op_perftest
                 for (size_t i = 0; i != queries.size(); ++i) {
                     auto const& q = queries[i];
@@ -539,7 +586,8 @@ int main(int argc, char** argv) {
                     run_queries(q.data(), offs, 1, &results, &fsum, i);
                     total += results;
                     if (run == 0) total_one_run += results;
-                    if (run == 0 && (needs_facets || is_paged || is_sorted)) {
+                    if (run == 0 && is_vstats && is_ranked) merge_stats(log_stats, bucket_totals, 1);
+                    if (run == 0 && (needs_facets || is_paged || is_sorted || is_vstats)) {
                         all_matches += facet_matches[0];
                         if (is_collapsed || (is_paged && doc_facets)) all_collapsed += collapsed_counts[0];
                         for (size_t g = 0; g != facet_totals.size(); ++g) facet_totals[g] += facet_rows[g];
@@ -575,6 +623,15 @@ int main(int argc, char** argv) {
                         batch_matches += facet_matches[q], batch_collapsed += is_collapsed || doc_facets ? collapsed_counts[q] : 0;
                     if (batch_matches != all_matches || batch_collapsed != all_collapsed)
                         throw std::runtime_error("the batch call and the one-query calls counted other matches or kept other documents");
+                } else if (is_vstats) {  // ... and reduce the same values
+                    dint_value_stats batch_stats{0, 0, 0xFFFFFFFFu, 0};
+                    std::vector<uint64_t> batch_buckets(n_buckets, 0);
+                    merge_stats(batch_stats, batch_buckets, queries.size());
+                    uint64_t batch_matches = 0;
+                    for (size_t q = 0; q != queries.size(); ++q) batch_matches += facet_matches[q];
+                    if (batch_matches != all_matches || batch_stats.n != log_stats.n || batch_stats.sum != log_stats.sum ||
+                        batch_stats.min != log_stats.min || batch_stats.max != log_stats.max || batch_buckets != bucket_totals)
+                        throw std::runtime_error("the batch call and the one-query calls reduced other values");
                 } else if (is_faceted) {  // ... and count the same matches per group
                     std::vector<uint64_t> batch_totals(n_groups, 0);
                     for (size_t q = 0; q != queries.size(); ++q)
@@ -590,7 +647,12 @@ int main(int argc, char** argv) {
             std::cout << "{\"type\": \"" << type << "\", \"query\": \"" << t << "\", \"avg\": " << avg << ", \"q50\": " << q50
                       << ", \"q90\": " << q90 << ", \"q95\": " << q95;
             if (batch_us >= 0) std::cout << ", \"batch_us_per_query\": " << batch_us;
-            if (is_sorted) {
+            if (is_vstats) {
+                std::cout << ", \"matches\": " << all_matches << ", \"value_n\": " << log_stats.n << ", \"value_sum\": " << log_stats.sum
+                          << ", \"value_min\": " << log_stats.min << ", \"value_max\": " << log_stats.max << ", \"buckets\": [";
+                for (size_t b = 0; b != n_buckets; ++b) std::cout << (b ? ", " : "") << bucket_totals[b];
+                std::cout << "]";
+            } else if (is_sorted) {
                 std::cout << ", \"pages\": " << pages << ", \"hits\": " << total_one_run << ", \"matches\": " << all_matches << ", \"order\": \""
                           << (sort_order == DINT_SORT_ASC ? "asc" : "desc") << "\"";
             } else if (is_paged) {
