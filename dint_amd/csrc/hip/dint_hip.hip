@@ -42,6 +42,7 @@
 #include "dint_paging_kernels.hpp"
 #include "dint_doc_values_kernels.hpp"
 #include "dint_value_stats_kernels.hpp"
+#include "dint_group_stats_kernels.hpp"
 #include "dint_score_documents_kernels.hpp"
 #include "dint_wand_kernels.hpp"
 #include "dint_check_kernels.hpp"
@@ -72,6 +73,7 @@
 #include "host/hip_api_paging.inc"
 #include "host/hip_api_doc_values.inc"
 #include "host/hip_api_value_stats.inc"
+#include "host/hip_api_group_stats.inc"
 #include "host/hip_api_score_documents.inc"
 #include "host/hip_api_wand.inc"
 #include "host/hip_api_check.inc"

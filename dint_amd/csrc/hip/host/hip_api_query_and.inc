@@ -19,7 +19,8 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split = true,
                             const ranked_args* rk = nullptr, bool_steps* extra = nullptr, range_args* rg = nullptr,
                             filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr,
-                            page_args* pg = nullptr, sort_args* sv = nullptr, value_stats_args* vs = nullptr);
+                            page_args* pg = nullptr, sort_args* sv = nullptr, value_stats_args* vs = nullptr,
+                            group_stats_args* gs = nullptr);
 
 // One AND call: what its stages share.
 struct and_call {
@@ -34,6 +35,7 @@ struct and_call {
     page_args* pg = nullptr;                // a paged call (ranked): only the survivors after every query's cursor are selected from
     sort_args* sv = nullptr;                // a sorted call (ranked): the survivors are selected by a column's value, after every query's cursor
     value_stats_args* vs = nullptr;         // a value-stats call (ranked): the survivors' values reduced in front of the selection
+    group_stats_args* gs = nullptr;         // a group-stats call (ranked): the survivors' values reduced per group in front of the selection
     size_t n_queries = 0;
     uint64_t* counts = nullptr;
     hipStream_t s = nullptr;
@@ -522,7 +524,9 @@ static int and_batch_rounds(and_call& c, bool searched0, unsigned long long* hos
 // travel to the host with the sums.
 // c.vs (with rk): its records and edges sent, its rows and hit values cleared, value_stats_kernel over the survivors directly
 // in front of ranked_topk and hit_values_kernel behind it; the records, the rows and the hit values travel to the host with
-// the sums. ----
+// the sums.
+// c.gs (with rk): its records sent empty, group_stats_kernel over the survivors directly in front of ranked_topk; the records
+// travel to the host with the sums. ----
 static int and_freqs_pass(and_call& c) {
     dint_query_index* qi = c.qi;
     const size_t n_queries = c.n_queries, n_terms = c.rounds + 1;
@@ -604,6 +608,11 @@ static int and_freqs_pass(and_call& c) {
         if (st == DINT_OK) st = value_stats_launch(qi, c.vs, c.n_pages, c.d_page_query, 0u, c.s);
         if (st != DINT_OK) return c.failed(st);
     }
+    if (rk && c.gs) {
+        int st = group_stats_clear(qi, c.gs, n_queries, c.s);
+        if (st == DINT_OK) st = group_stats_launch(qi, c.gs, c.n_pages, c.d_page_query, 0u, c.s);
+        if (st != DINT_OK) return c.failed(st);
+    }
     if (rk) {
         const int st = ranked_topk(qi, *rk, c.page_query, n_queries, c.s, c.sv);
         if (st != DINT_OK) return c.failed(st);
@@ -613,6 +622,7 @@ static int and_freqs_pass(and_call& c) {
         if (st == DINT_OK) st = value_stats_back(c.vs, n_queries, c.s);
         if (st != DINT_OK) return c.failed(st);
     }
+    if (rk && c.gs && group_stats_back(c.gs, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
     if (rk && c.sv) {
         int st = sorted_hits_launch(qi, c.sv, c.n_pages, c.d_page_query, 0u, c.s);
         if (st == DINT_OK) st = sort_back(c.sv, n_queries, c.s);
@@ -655,7 +665,7 @@ static int and_copy_back(and_call& c, uint64_t* freq_sums, uint64_t* freq_blocks
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split,
                             const ranked_args* rk, bool_steps* extra, range_args* rg, filter_args* fl, facet_args* fa,
-                            collapse_args* ca, page_args* pg, sort_args* sv, value_stats_args* vs) {
+                            collapse_args* ca, page_args* pg, sort_args* sv, value_stats_args* vs, group_stats_args* gs) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -672,6 +682,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     c.pg = pg;
     c.sv = sv;
     c.vs = vs;
+    c.gs = gs;
     c.n_queries = n_queries;
     c.counts = counts;
     c.s = static_cast<hipStream_t>(stream);
@@ -685,6 +696,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     page_begin(pg, n_queries);
     sort_begin(sv, n_queries);
     value_stats_begin(vs, n_queries);
+    group_stats_begin(gs, n_queries);
     if (c.n_pages == 0) return DINT_OK;
     bool mixed = false;
     const int split = may_split ? and_mixed_split(c, stream, &mixed) : DINT_OK;

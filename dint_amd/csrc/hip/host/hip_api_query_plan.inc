@@ -409,6 +409,46 @@ static int value_stats_back(const value_stats_args* vs, size_t n_queries, hipStr
     return DINT_OK;
 }
 
+// A group-stats call (hip_api_group_stats.inc): the map and the column, where the call's records go on the host —
+// n_queries * n_groups of them, query by query — and where they live on the device: a grow-only workspace of the query index
+// of its own, 24 bytes per (query, group). The records go up as the empty record once per call under the lock
+// (group_stats_clear), every pass adds, and they come back once. Where a call takes a null one nothing is planned or launched
+// differently.
+struct group_stats_args {
+    const dint_doc_facets* facets = nullptr;
+    const dint_doc_values* values = nullptr;
+    dint_value_stats* h_recs = nullptr;  // the caller's group_stats
+    value_stats_rec* d_recs = nullptr;   // (set by group_stats_clear)
+    size_t recs(size_t n_queries) const { return n_queries * size_t(facets->n_groups); }
+};
+// the call is planned and has refused nothing: every record is empty until a pass says otherwise
+static void group_stats_begin(const group_stats_args* gs, size_t n_queries) {
+    if (gs) std::fill(gs->h_recs, gs->h_recs + gs->recs(n_queries), dint_value_stats{0, 0, 0xFFFFFFFFu, 0});
+}
+// under the index's lock, once per call, in front of its first launch: the empty records (the caller's own, as
+// group_stats_begin left them) go up
+static int group_stats_clear(dint_query_index* qi, group_stats_args* gs, size_t n_queries, hipStream_t s) {
+    if (!qi->group_stats_recs.ensure(3 * gs->recs(n_queries))) return DINT_ERR_HIP;
+    gs->d_recs = reinterpret_cast<value_stats_rec*>(qi->group_stats_recs.p);
+    // (pageable host memory: the copy has left the caller's array when the call returns, and the call waits on the stream
+    // before it does)
+    HIP_TRY(hipMemcpyAsync(gs->d_recs, gs->h_recs, gs->recs(n_queries) * sizeof(value_stats_rec), hipMemcpyHostToDevice, s));
+    return DINT_OK;
+}
+// group_stats_kernel over the n_pages pages of qi->cand, in front of ranked_topk; d_page_query[page] + q0: the page's query of
+// the call
+static int group_stats_launch(const dint_query_index* qi, const group_stats_args* gs, uint64_t n_pages, const uint32_t* d_page_query,
+                              uint32_t q0, hipStream_t s) {
+    hipLaunchKernelGGL(group_stats_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, n_pages * kPageSlots, d_page_query, q0,
+                       gs->facets->view(), gs->values->view(), gs->d_recs);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// ... and the records' way back, on the stream, in front of the call's last wait
+static int group_stats_back(const group_stats_args* gs, size_t n_queries, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(gs->h_recs, gs->d_recs, gs->recs(n_queries) * sizeof(value_stats_rec), hipMemcpyDeviceToHost, s));
+    return DINT_OK;
+}
+
 // the *_queries_freqs entries: a freqs dictionary of the index's device and kind, and somewhere for the sums
 static bool freqs_args_ok(const dint_query_index* qi, const dint_dict* freqs_dict, const uint64_t* freq_sums) {
     return freqs_dict && freq_sums && (!qi || (freqs_dict->device == qi->docs->device && freqs_dict->kind == qi->docs->kind));

@@ -84,6 +84,8 @@ struct dint_query_index {
     // call's edges and behind them per query a row of n_edges + 1 counters, then per (query, i) the hit's value
     device_buffer<unsigned long long> value_stats_recs;
     device_buffer<uint32_t> value_stats_words;
+    // the group-stats ranked calls (hip_api_group_stats.inc): per (query, group) of the call its record, three 64-bit words
+    device_buffer<unsigned long long> group_stats_recs;
     // dint_check_index (hip_api_check.inc): every block of a list but its last holds 256 postings (the in-index layout:
     // block j of a list is its positions [256 j, 256 j + n)); two pinned staging buffers of a pass's expected postings
     // and their device copies, alternating

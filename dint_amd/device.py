@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "dint_doc_values_create", "dint_doc_values_info_get", "dint_doc_values_destroy", "dint_doc_filter_create_from_values",
     "dint_ranked_or_sorted_queries", "dint_ranked_and_sorted_queries",
     "dint_ranked_or_value_stats_queries", "dint_ranked_and_value_stats_queries",
+    "dint_ranked_or_group_stats_queries", "dint_ranked_and_group_stats_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_check_index", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -204,6 +205,8 @@ def _load():
     # bucket_counts, hit_values, blocks_decoded, stream)
     lib.dint_ranked_or_value_stats_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_and_value_stats_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_or_group_stats_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_group_stats_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
@@ -1035,6 +1038,43 @@ class QueryIndex:
         """ranked_and_filtered_queries with a column reduced over every match (dint_ranked_and_value_stats_queries): arguments
         and outputs as ranked_or_value_stats_queries, over the intersection."""
         return self._ranked_value_stats("dint_ranked_and_value_stats_queries", freqs_dict, wand, queries, values, edges, filter, k, with_stats)
+
+    def _ranked_group_stats(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, facets, values, doc_filter, k: int,
+                            with_facet_counts: bool):
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        group_stats = np.zeros((n, facets.n_groups), dtype=_VALUE_STATS)
+        rows = np.zeros((n, facets.n_groups), dtype=np.uint32) if with_facet_counts else None
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 doc_filter._h if doc_filter is not None else None, facets._h, values._h, n, counts.ctypes.data,
+                                 matches.ctypes.data, scores.ctypes.data, docids.ctypes.data, group_stats.ctypes.data,
+                                 rows.ctypes.data if with_facet_counts else None, C.byref(blocks), self._stream()), fn)
+        return counts, scores, docids, matches, blocks.value, group_stats, rows
+
+    def ranked_or_group_stats_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, facets: "DocFacets", values: "DocValues",
+                                      filter=None, k: int = 10, with_facet_counts: bool = False):
+        """ranked_or_filtered_queries with a column reduced over every match per document group
+        (dint_ranked_or_group_stats_queries): facets is a DocFacets and values a DocValues on this
+        index's device, filter a DocFilter of this index or None (unrestricted) -> (counts, scores, docids, matches,
+        blocks_decoded, group_stats, facet_counts): the first five what ranked_or_filtered_queries returns with with_stats for
+        (queries, filter, k), bit for bit; group_stats a structured array [n, n_groups] with the fields n, sum, min, max over the
+        matches d of the query with d < facets.num_docs, group_of[d] == g and d < values.num_docs (no such match:
+        (0, 0, 0xFFFFFFFF, 0)); facet_counts u32[n, n_groups], the faceted call's rows — every match per group, valued or not —
+        with with_facet_counts, else None."""
+        return self._ranked_group_stats("dint_ranked_or_group_stats_queries", freqs_dict, wand, queries, facets, values, filter, k,
+                                        with_facet_counts)
+
+    def ranked_and_group_stats_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, facets: "DocFacets", values: "DocValues",
+                                       filter=None, k: int = 10, with_facet_counts: bool = False):
+        """ranked_and_filtered_queries with a column reduced over every match per document group
+        (dint_ranked_and_group_stats_queries): arguments and outputs as ranked_or_group_stats_queries, over the intersection."""
+        return self._ranked_group_stats("dint_ranked_and_group_stats_queries", freqs_dict, wand, queries, facets, values, filter, k,
+                                        with_facet_counts)
 
     def ranked_pages(self, entry: str, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10, filter=None, facets=None,
                      after=None, max_pages=None, values=None, descending: bool = True):

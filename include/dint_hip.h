@@ -922,8 +922,8 @@ int dint_ranked_and_sorted_queries(dint_query_index* qi, const dint_dict* freqs_
  * call runs one launch over the candidate slots in front of the selection per OR pass / per AND call, which gathers one word
  * of the column per live slot and reduces in LDS — at most one global add per bucket present in a page and four atomics on the
  * query's record — and, if hit_values is given, one over the selected keys behind it.
- * Percentiles, sums or means of scores (float sums are not order-independent), statistics per facet group, several columns per
- * call and the boolean, pruned, collapsed and paged forms are out of scope. */
+ * Percentiles, sums or means of scores (float sums are not order-independent), several columns per call and the boolean,
+ * pruned, collapsed and paged forms are out of scope; statistics per facet group are the group-stats calls below. */
 #define DINT_VALUE_STATS_MAX_EDGES 1023u
 typedef struct dint_value_stats { /* 24 bytes: offsets 0, 8, 16, 20 */
     uint64_t n;   /* matches that have a value */
@@ -941,6 +941,45 @@ int dint_ranked_and_value_stats_queries(dint_query_index* qi, const dint_dict* f
                                         const dint_doc_values* values, const uint32_t* edges, uint32_t n_edges, size_t n_queries,
                                         uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids, dint_value_stats* stats,
                                         uint32_t* bucket_counts, uint32_t* hit_values, uint64_t* blocks_decoded, void* stream);
+
+/* ---- per-group value statistics of the ranked queries (facets x values: a column reduced per document group) --------
+ * Adds: what a cursor engine computes with a stats collector nested under a terms collector — the average price per brand of
+ * the results, the newest document per site, the revenue per tenant of what matched — for a batch of queries, in the call that
+ * ranks them. Without it a caller runs one filtered value-stats call per group, each of which decodes and scores the query again.
+ * dint_ranked_or_group_stats_queries / dint_ranked_and_group_stats_queries take the arguments of the filtered calls (filter
+ * nullable: unrestricted), a facets map and a column (both belong to a device, neither to the index, and their num_docs need
+ * not agree with each other or with the index) and the outputs (HOST):
+ *   counts, matches, scores, docids, *blocks_decoded   bit for bit what dint_ranked_or_filtered_queries /
+ *                    dint_ranked_and_filtered_queries return for the same arguments; the plan depends neither on the map nor on
+ *                    the column; matches, docids and blocks_decoded are nullable
+ *   group_stats[q * n_groups + g]   over EVERY match d of query q, not over the top k, that is in group g (d < the map's
+ *                    num_docs and group_of[d] == g) and has a value (d < the column's num_docs): their number, the 64-bit sum of
+ *                    their values, the minimum and the maximum. A match in no group contributes nowhere, and so does a match in
+ *                    a group but at or past the column. A (query, group) without such a match: {0, 0, 0xFFFFFFFF, 0}
+ *   facet_counts[q * n_groups + g]  (nullable) the faceted call's row, bit for bit: EVERY match of q in group g, valued or
+ *                    not; so group_stats[..].n <= facet_counts[..], with equality where the column covers the index
+ * Every quantity is an integer sum, minimum or maximum: exact, order-independent and the same from run to run.
+ * DINT_ERR_ARG, before anything is written or launched: whatever the filtered calls refuse; a null facets, values or
+ * group_stats; a map or a column on another device than the index; n_queries * n_groups > DINT_GROUP_STATS_MAX_RECORDS (384 MiB
+ * of records: the caller batches). Terms, query_offsets, the handle's lock and the stream are as for the filtered calls. The
+ * records are a grow-only workspace of the query index of their own (24 bytes per (query, group)), sent as the empty record
+ * once per call and copied back once. Besides the filtered call's launches a call runs one launch over the candidate slots in
+ * front of the selection per OR pass / per AND call, which gathers one word of the map and one of the column per live slot and
+ * reduces runs of equal groups in registers and, up to 256 groups, the page's records in LDS — at most one set of four global
+ * atomics per group present in a page — and, if facet_counts is given, the faceted call's launch.
+ * The hits' groups and values (the collapsed and value-stats calls give them), bucket histograms per group, several columns per
+ * call and sorting groups by a statistic are out of scope. */
+#define DINT_GROUP_STATS_MAX_RECORDS (1ull << 24)
+int dint_ranked_or_group_stats_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                       const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                       const dint_doc_facets* facets, const dint_doc_values* values, size_t n_queries, uint64_t* counts,
+                                       uint64_t* matches, float* scores, uint32_t* docids, dint_value_stats* group_stats,
+                                       uint32_t* facet_counts, uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_group_stats_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                        const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                        const dint_doc_facets* facets, const dint_doc_values* values, size_t n_queries, uint64_t* counts,
+                                        uint64_t* matches, float* scores, uint32_t* docids, dint_value_stats* group_stats,
+                                        uint32_t* facet_counts, uint64_t* blocks_decoded, void* stream);
 
 /* ---- the wand data's BM25 maxima from the index, on the device; block maxima for the pruned call --------------
  * Replaces: the max_term_weight half of wand_data's constructor (include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp),

@@ -6,8 +6,8 @@
 //   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
 //               ranked_or_bool | ranked_or_range | ranked_and_range | ranked_or_filtered | ranked_and_filtered |
 //               ranked_or_faceted | ranked_and_faceted | ranked_or_collapsed | ranked_and_collapsed | ranked_or_paged |
-//               ranked_and_paged | ranked_or_sorted | ranked_and_sorted | ranked_or_value_stats | ranked_and_value_stats, several
-//               separated by ':'
+//               ranked_and_paged | ranked_or_sorted | ranked_and_sorted | ranked_or_value_stats | ranked_and_value_stats |
+//               ranked_or_group_stats | ranked_and_group_stats, several separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
@@ -68,6 +68,13 @@
 //               must be the only type of its run; the query lines, output and keys are ranked_or's, and the JSON line carries
 //               besides "matches", "value_n" and "value_sum" (totals over the log), "value_min" and "value_max" (over the
 //               log; 4294967295 and 0 if no match has a value) and "buckets" (per bucket the log's total; [] without --edges);
+//               ranked_or_group_stats / ranked_and_group_stats (dint_ranked_or_group_stats_queries,
+//               dint_ranked_and_group_stats_queries: ranked_or / ranked_and with a column's values reduced over every match per
+//               document group) need --facets FILE as the faceted types do and --values FILE as the
+//               sorted types do, and take either --filter FILE or --value-range lo:hi; each must be the only type of its run;
+//               the query lines, output and keys are ranked_or's, and the JSON line carries besides "matches", "n_groups" and
+//               the per-group records merged over the log: "group_n", "group_sum", "group_min" and "group_max", arrays of
+//               n_groups (4294967295 and 0 where no match of a group has a value);
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -184,14 +191,23 @@ int main(int argc, char** argv) {
         for (const char* vstats : {"ranked_or_value_stats", "ranked_and_value_stats"})
             if (!is_vstats && (":" + query_type + ":").find(std::string(":") + vstats + ":") != std::string::npos)
                 throw std::runtime_error(std::string(vstats) + " answers its whole log under --values: it must be the only query type of a run");
+        const bool is_gstats = query_type == "ranked_or_group_stats" || query_type == "ranked_and_group_stats";
+        for (const char* gstats : {"ranked_or_group_stats", "ranked_and_group_stats"})
+            if (!is_gstats && (":" + query_type + ":").find(std::string(":") + gstats + ":") != std::string::npos)
+                throw std::runtime_error(std::string(gstats) + " answers its whole log under --facets and --values: it must be the only query type of a run");
+        if (is_gstats && !facets_filename) {
+            std::cerr << query_type << " needs --facets FILE (every line `d g` or `lo:hi g`: document d, or every document of [lo, hi), is in group g)"
+                      << std::endl;
+            return 1;
+        }
         if (!is_paged && !is_sorted && pages) throw std::runtime_error("--pages goes with ranked_or_paged, ranked_and_paged, ranked_or_sorted and ranked_and_sorted only");
         if (is_paged && !pages) pages = 2;
         if (is_sorted && !pages) pages = 1;
-        if (!is_sorted && !is_vstats && (values_filename || value_range || !order_name.empty()))
+        if (!is_sorted && !is_vstats && !is_gstats && (values_filename || value_range || !order_name.empty()))
             throw std::runtime_error("--values, --order and --value-range go with ranked_or_sorted and ranked_and_sorted only");
-        if (is_vstats && !order_name.empty()) throw std::runtime_error("--order goes with ranked_or_sorted and ranked_and_sorted only");
+        if ((is_vstats || is_gstats) && !order_name.empty()) throw std::runtime_error("--order goes with ranked_or_sorted and ranked_and_sorted only");
         if (!is_vstats && edges_text) throw std::runtime_error("--edges goes with ranked_or_value_stats and ranked_and_value_stats only");
-        if ((is_sorted || is_vstats) && !values_filename) {
+        if ((is_sorted || is_vstats || is_gstats) && !values_filename) {
             std::cerr << query_type << " needs --values FILE (every line `d v` or `lo:hi v`: document d, or every document of [lo, hi), has value v)"
                       << std::endl;
             return 1;
@@ -206,16 +222,16 @@ int main(int argc, char** argv) {
         uint32_t range_lo = 0, range_hi = 0;
         if (value_range) tool::parse_value_range(value_range, range_lo, range_hi);
         tool::doc_values_column values_column;
-        if (is_sorted || is_vstats) {
+        if (is_sorted || is_vstats || is_gstats) {
             std::ifstream vf(values_filename);
             if (!vf) throw std::runtime_error(std::string("could not open the values file ") + values_filename);
             values_column = tool::parse_doc_values(vf);
         }
-        if (!needs_facets && !is_paged && facets_filename)
+        if (!needs_facets && !is_paged && !is_gstats && facets_filename)
             throw std::runtime_error("--facets goes with the ranked_*_faceted, ranked_*_collapsed and ranked_*_paged types only");
-        if (!is_filtered && !needs_facets && !is_paged && !is_sorted && !is_vstats && filter_filename)
+        if (!is_filtered && !needs_facets && !is_paged && !is_sorted && !is_vstats && !is_gstats && filter_filename)
             throw std::runtime_error("--filter goes with the ranked_*_filtered, ranked_*_faceted, ranked_*_collapsed, ranked_*_paged and ranked_*_sorted types only");
-        const bool uses_facets = needs_facets || (is_paged && facets_filename);  // (a paged type: the collapsed paged entry)
+        const bool uses_facets = needs_facets || is_gstats || (is_paged && facets_filename);  // (a paged type: the collapsed paged entry)
         tool::doc_facets_map facets_map;
         if (uses_facets) {
             std::ifstream ff(facets_filename);
@@ -343,8 +359,8 @@ int main(int argc, char** argv) {
         }
         dint_doc_filter* doc_filter = nullptr;  // ranked_*_filtered: the run's filter
         if (filter_filename) dint_ok(dint_doc_filter_create(qi, filter_bits.words.data(), filter_bits.num_docs, &doc_filter), "dint_doc_filter_create");
-        dint_doc_values* doc_values = nullptr;  // ranked_*_sorted, ranked_*_value_stats: the run's column, and with --value-range the filter from it
-        if (is_sorted || is_vstats) {
+        dint_doc_values* doc_values = nullptr;  // ranked_*_sorted, ranked_*_value_stats, ranked_*_group_stats: the run's column, and with --value-range the filter from it
+        if (is_sorted || is_vstats || is_gstats) {
             dint_ok(dint_doc_values_create(0, values_column.values.data(), values_column.num_docs, &doc_values), "dint_doc_values_create");
             if (value_range) dint_ok(dint_doc_filter_create_from_values(qi, doc_values, range_lo, range_hi, &doc_filter), "dint_doc_filter_create_from_values");
         }
@@ -371,6 +387,8 @@ int main(int argc, char** argv) {
         std::vector<dint_value_stats> value_stats;
         std::vector<uint32_t> bucket_rows;
         const size_t n_buckets = value_edges.empty() ? 0 : value_edges.size() + 1;
+        // ranked_*_group_stats: a call's records, n_groups per query
+        std::vector<dint_value_stats> group_recs;
 
         std::vector<std::string> types;
         for (size_t a = 0; a <= query_type.size();) {
@@ -392,7 +410,8 @@ int main(int argc, char** argv) {
             const bool is_or_paged = t == "ranked_or_paged" && wand, is_and_paged = t == "ranked_and_paged" && wand;
             const bool is_or_sorted = t == "ranked_or_sorted" && wand, is_and_sorted = t == "ranked_and_sorted" && wand;
             const bool is_or_vstats = t == "ranked_or_value_stats" && wand, is_and_vstats = t == "ranked_and_value_stats" && wand;
-            const bool is_ranked = (t == "ranked_and" && wand) || is_or_vstats || is_and_vstats || is_or_sorted || is_and_sorted || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
+            const bool is_or_gstats = t == "ranked_or_group_stats" && wand, is_and_gstats = t == "ranked_and_group_stats" && wand;
+            const bool is_ranked = (t == "ranked_and" && wand) || is_or_gstats || is_and_gstats || is_or_vstats || is_and_vstats || is_or_sorted || is_and_sorted || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
                                    is_or_range || is_and_range || is_or_filtered || is_and_filtered || is_or_faceted || is_and_faceted ||
                                    is_or_collapsed || is_and_collapsed;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
@@ -538,6 +557,14 @@ int main(int argc, char** argv) {
                                 n, q_counts, facet_matches.data(), top_scores.data(), nullptr, value_stats.data(), bucket_rows.data(), nullptr,
                                 nullptr, nullptr),
                             "dint_ranked_*_value_stats_queries");
+                } else if (is_or_gstats || is_and_gstats) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    facet_matches.resize(n);
+                    group_recs.resize(n * n_groups);
+                    dint_ok((is_or_gstats ? dint_ranked_or_group_stats_queries : dint_ranked_and_group_stats_queries)(
+                                qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_facets, doc_values, n, q_counts, facet_matches.data(),
+                                top_scores.data(), nullptr, group_recs.data(), nullptr, nullptr, nullptr),
+                            "dint_ranked_*_group_stats_queries");
                 } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
@@ -577,6 +604,18 @@ int main(int argc, char** argv) {
                     for (size_t b = 0; b != n_buckets; ++b) buckets[b] += bucket_rows[q * n_buckets + b];
                 }
             };
+            // a group-stats type: per group the log's records merged (the first run's)
+            std::vector<dint_value_stats> group_totals(is_gstats ? n_groups : 0, dint_value_stats{0, 0, 0xFFFFFFFFu, 0});
+            auto merge_groups = [&](std::vector<dint_value_stats>& into, size_t n) {
+                for (size_t q = 0; q != n; ++q)
+                    for (size_t g = 0; g != n_groups; ++g) {
+                        const dint_value_stats& r = group_recs[q * n_groups + g];
+                        into[g].n += r.n;
+                        into[g].sum += r.sum;
+                        into[g].min = std::min(into[g].min, r.min);
+                        into[g].max = std::max(into[g].max, r.max);
+                    }
+            };
             for (size_t run = 0; run != runs; ++run) {  // op_perftest
                 for (size_t i = 0; i != queries.size(); ++i) {
                     auto const& q = queries[i];
@@ -587,7 +626,8 @@ int main(int argc, char** argv) {
                     total += results;
                     if (run == 0) total_one_run += results;
                     if (run == 0 && is_vstats && is_ranked) merge_stats(log_stats, bucket_totals, 1);
-                    if (run == 0 && (needs_facets || is_paged || is_sorted || is_vstats)) {
+                    if (run == 0 && is_gstats && is_ranked) merge_groups(group_totals, 1);
+                    if (run == 0 && (needs_facets || is_paged || is_sorted || is_vstats || is_gstats)) {
                         all_matches += facet_matches[0];
                         if (is_collapsed || (is_paged && doc_facets)) all_collapsed += collapsed_counts[0];
                         for (size_t g = 0; g != facet_totals.size(); ++g) facet_totals[g] += facet_rows[g];
@@ -632,6 +672,16 @@ int main(int argc, char** argv) {
                     if (batch_matches != all_matches || batch_stats.n != log_stats.n || batch_stats.sum != log_stats.sum ||
                         batch_stats.min != log_stats.min || batch_stats.max != log_stats.max || batch_buckets != bucket_totals)
                         throw std::runtime_error("the batch call and the one-query calls reduced other values");
+                } else if (is_gstats) {  // ... and reduce the same values per group
+                    std::vector<dint_value_stats> batch_groups(n_groups, dint_value_stats{0, 0, 0xFFFFFFFFu, 0});
+                    merge_groups(batch_groups, queries.size());
+                    uint64_t batch_matches = 0;
+                    for (size_t q = 0; q != queries.size(); ++q) batch_matches += facet_matches[q];
+                    bool same = batch_matches == all_matches;
+                    for (size_t g = 0; g != n_groups; ++g)
+                        same = same && batch_groups[g].n == group_totals[g].n && batch_groups[g].sum == group_totals[g].sum &&
+                               batch_groups[g].min == group_totals[g].min && batch_groups[g].max == group_totals[g].max;
+                    if (!same) throw std::runtime_error("the batch call and the one-query calls reduced other values per group");
                 } else if (is_faceted) {  // ... and count the same matches per group
                     std::vector<uint64_t> batch_totals(n_groups, 0);
                     for (size_t q = 0; q != queries.size(); ++q)
@@ -647,7 +697,18 @@ int main(int argc, char** argv) {
             std::cout << "{\"type\": \"" << type << "\", \"query\": \"" << t << "\", \"avg\": " << avg << ", \"q50\": " << q50
                       << ", \"q90\": " << q90 << ", \"q95\": " << q95;
             if (batch_us >= 0) std::cout << ", \"batch_us_per_query\": " << batch_us;
-            if (is_vstats) {
+            if (is_gstats) {
+                std::cout << ", \"matches\": " << all_matches << ", \"n_groups\": " << n_groups;
+                auto column = [&](const char* key, auto field) {
+                    std::cout << ", \"" << key << "\": [";
+                    for (size_t g = 0; g != n_groups; ++g) std::cout << (g ? ", " : "") << field(group_totals[g]);
+                    std::cout << "]";
+                };
+                column("group_n", [](const dint_value_stats& r) { return r.n; });
+                column("group_sum", [](const dint_value_stats& r) { return r.sum; });
+                column("group_min", [](const dint_value_stats& r) { return uint64_t(r.min); });
+                column("group_max", [](const dint_value_stats& r) { return uint64_t(r.max); });
+            } else if (is_vstats) {
                 std::cout << ", \"matches\": " << all_matches << ", \"value_n\": " << log_stats.n << ", \"value_sum\": " << log_stats.sum
                           << ", \"value_min\": " << log_stats.min << ", \"value_max\": " << log_stats.max << ", \"buckets\": [";
                 for (size_t b = 0; b != n_buckets; ++b) std::cout << (b ? ", " : "") << bucket_totals[b];
