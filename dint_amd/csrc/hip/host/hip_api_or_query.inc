@@ -42,6 +42,11 @@
 // staged as for fa, and group_stats_kernel runs between the scoring launch and ranked_topk, over the pass's slots at the pass's
 // query offset; the records go up empty once per call and come back with the last pass. Without gs nothing is planned or
 // launched differently.
+// pa (dint_ranked_or_percentile_queries, hip_api_percentiles.inc), with rk and with rg or fl: the pass's page -> query table is
+// staged as for fa, and the four rounds of the select (percentile_launch) run between the scoring launch and ranked_topk, over
+// the pass's slots at the pass's query offset — a pass holds whole queries, so a query's select completes within its pass;
+// per_million goes up and the states are cleared once per call, and the counts and the values come back with the last pass.
+// Without pa nothing is planned or launched differently.
 
 // What a ranked OR call with a minimum and exclusions adds to its passes, and what it gets back.
 struct or_bool_args {
@@ -108,11 +113,13 @@ struct or_pass_query {
 // vs (with rk; its records and edges up, its rows and hit values cleared): or_facet_layout staged as for fa, value_stats_kernel
 // behind the scoring launch, hit_values_kernel behind the selection.
 // gs (with rk; its records up): or_facet_layout staged as for fa, group_stats_kernel behind the scoring launch.
+// pa (with rk; its per_million up, its states cleared): or_facet_layout staged as for fa, the select's rounds behind the scoring launch.
 static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const ranked_args* rk, const std::vector<or_pass_query>& qs,
                        size_t min_stage, unsigned long long* d_counts, size_t n_counts, uint32_t id0, size_t n_ids, hipStream_t s,
                        or_bool_args* xb = nullptr, bool ranged = false, const filter_args* fl = nullptr, const facet_args* fa = nullptr,
                        const collapse_args* ca = nullptr, const page_args* pg = nullptr, const sort_args* sv = nullptr,
-                       const value_stats_args* vs = nullptr, const group_stats_args* gs = nullptr) {
+                       const value_stats_args* vs = nullptr, const group_stats_args* gs = nullptr,
+                       const percentile_args* pa = nullptr) {
     uint64_t n_pages = 0, n_terms = 0;
     for (const or_pass_query& q : qs) {
         n_terms += q.n;
@@ -125,8 +132,8 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
             if (q.n) n_steps = std::max<size_t>(n_steps, xb->not_at[q.id + 1] - xb->not_at[q.id]);
     const or_bool_layout B(L.words, xb ? n_pages : 0, xb ? n_terms : 0, n_steps * n_ids, n_steps);
     const or_range_layout R(B.words, ranged ? n_terms : 0);
-    const or_facet_layout F(R.words, fa || pg || sv || vs || gs ? n_pages : 0);
-    const size_t up_words = F.words;  // (without xb, fa, pg, sv, vs and gs and not ranged: L.words)
+    const or_facet_layout F(R.words, fa || pg || sv || vs || gs || pa ? n_pages : 0);
+    const size_t up_words = F.words;  // (without xb, fa, pg, sv, vs, gs and pa and not ranged: L.words)
     if (qi->stage(std::max<size_t>(up_words * 4, min_stage)) != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     uint32_t *page_block = qi->h(L.page_block), *page_term = qi->h(L.page_term), *term_order = qi->h(L.term_order);
     std::vector<uint32_t> page_query(rk ? n_pages : 0);  // (ranked_topk's: the pass's queries, from 0)
@@ -157,7 +164,7 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
             }
         }
     }
-    if ((fa || pg || sv || vs || gs) && n_pages) std::memcpy(qi->h(F.page_query), page_query.data(), n_pages * 4);
+    if ((fa || pg || sv || vs || gs || pa) && n_pages) std::memcpy(qi->h(F.page_query), page_query.data(), n_pages * 4);
     if (xb) {
         if (n_pages) std::memcpy(qi->h(B.page_query), page_query.data(), n_pages * 4);
         std::memset(qi->h(B.not_first), 0, (B.words - B.not_first) * 4);
@@ -247,6 +254,7 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
     if (fa && facet_count_launch(qi, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (vs && value_stats_launch(qi, vs, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (gs && group_stats_launch(qi, gs, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
+    if (pa && percentile_launch(qi, pa, n_pages, qi->d(F.page_query), id0, n_ids, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (ca && collapse_launch(qi, ca, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (pg && page_after_launch(qi, pg, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (sv && value_after_launch(qi, sv, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
@@ -262,7 +270,8 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream,
                            const ranked_args* rk = nullptr, or_bool_args* xb = nullptr, range_args* rg = nullptr,
                            filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr, page_args* pg = nullptr,
-                           sort_args* sv = nullptr, value_stats_args* vs = nullptr, group_stats_args* gs = nullptr) {
+                           sort_args* sv = nullptr, value_stats_args* vs = nullptr, group_stats_args* gs = nullptr,
+                           percentile_args* pa = nullptr) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -290,6 +299,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     sort_begin(sv, n_queries);
     value_stats_begin(vs, n_queries);
     group_stats_begin(gs, n_queries);
+    percentile_begin(pa, n_queries);
     if (op.all == 0) return DINT_OK;
 
     std::lock_guard<std::mutex> lock(qi->mutex);
@@ -319,6 +329,10 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         const int cleared = group_stats_clear(qi, gs, n_queries, s);
         if (cleared != DINT_OK) return cleared;
     }
+    if (pa) {
+        const int cleared = percentile_clear(qi, pa, n_queries, s);
+        if (cleared != DINT_OK) return cleared;
+    }
     // the call's counters: counts[n_queries] then freq sums[n_queries], cleared once, added to by every pass
     if (!qi->freq_sums.ensure(2 * n_queries)) return DINT_ERR_HIP;
     unsigned long long* const d_counts = qi->freq_sums.p;
@@ -344,7 +358,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         ranked_args pass_rk = rk ? *rk : ranked_args{};
         if (rk) pass_rk.keys += uint64_t(q0) * rk->k;  // (the keys of the pass's queries at their own offset)
         const int st = or_run_pass(qi, freqs_dict, rk ? &pass_rk : nullptr, qs, 2 * n_queries * sizeof(unsigned long long), d_counts,
-                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl, fa, ca, pg, sv, vs, gs);
+                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl, fa, ca, pg, sv, vs, gs, pa);
         if (st != DINT_OK) return st;
     }
     if (fa && facet_rows_back(fa, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
@@ -353,6 +367,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     if (sv && sort_back(sv, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (vs && value_stats_back(vs, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (gs && group_stats_back(gs, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
+    if (pa && percentile_back(pa, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (fl) HIP_TRY(hipMemcpyAsync(fl->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (rg) HIP_TRY(hipMemcpyAsync(rg->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (xb) HIP_TRY(hipMemcpyAsync(xb->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));

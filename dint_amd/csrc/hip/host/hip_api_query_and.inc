@@ -20,7 +20,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
                             const ranked_args* rk = nullptr, bool_steps* extra = nullptr, range_args* rg = nullptr,
                             filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr,
                             page_args* pg = nullptr, sort_args* sv = nullptr, value_stats_args* vs = nullptr,
-                            group_stats_args* gs = nullptr);
+                            group_stats_args* gs = nullptr, percentile_args* pa = nullptr);
 
 // One AND call: what its stages share.
 struct and_call {
@@ -36,6 +36,7 @@ struct and_call {
     sort_args* sv = nullptr;                // a sorted call (ranked): the survivors are selected by a column's value, after every query's cursor
     value_stats_args* vs = nullptr;         // a value-stats call (ranked): the survivors' values reduced in front of the selection
     group_stats_args* gs = nullptr;         // a group-stats call (ranked): the survivors' values reduced per group in front of the selection
+    percentile_args* pa = nullptr;          // a percentile call (ranked): the survivors' values selected from in front of the selection
     size_t n_queries = 0;
     uint64_t* counts = nullptr;
     hipStream_t s = nullptr;
@@ -526,7 +527,10 @@ static int and_batch_rounds(and_call& c, bool searched0, unsigned long long* hos
 // in front of ranked_topk and hit_values_kernel behind it; the records, the rows and the hit values travel to the host with
 // the sums.
 // c.gs (with rk): its records sent empty, group_stats_kernel over the survivors directly in front of ranked_topk; the records
-// travel to the host with the sums. ----
+// travel to the host with the sums.
+// c.pa (with rk): its per_million sent and its states cleared, the four rounds of the select (percentile_launch) over the
+// survivors directly in front of ranked_topk — the call is one pass, so every query's slots are complete; the counts and the
+// values travel to the host with the sums. ----
 static int and_freqs_pass(and_call& c) {
     dint_query_index* qi = c.qi;
     const size_t n_queries = c.n_queries, n_terms = c.rounds + 1;
@@ -613,6 +617,11 @@ static int and_freqs_pass(and_call& c) {
         if (st == DINT_OK) st = group_stats_launch(qi, c.gs, c.n_pages, c.d_page_query, 0u, c.s);
         if (st != DINT_OK) return c.failed(st);
     }
+    if (rk && c.pa) {
+        int st = percentile_clear(qi, c.pa, n_queries, c.s);
+        if (st == DINT_OK) st = percentile_launch(qi, c.pa, c.n_pages, c.d_page_query, 0u, n_queries, c.s);
+        if (st != DINT_OK) return c.failed(st);
+    }
     if (rk) {
         const int st = ranked_topk(qi, *rk, c.page_query, n_queries, c.s, c.sv);
         if (st != DINT_OK) return c.failed(st);
@@ -623,6 +632,7 @@ static int and_freqs_pass(and_call& c) {
         if (st != DINT_OK) return c.failed(st);
     }
     if (rk && c.gs && group_stats_back(c.gs, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
+    if (rk && c.pa && percentile_back(c.pa, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
     if (rk && c.sv) {
         int st = sorted_hits_launch(qi, c.sv, c.n_pages, c.d_page_query, 0u, c.s);
         if (st == DINT_OK) st = sort_back(c.sv, n_queries, c.s);
@@ -665,7 +675,8 @@ static int and_copy_back(and_call& c, uint64_t* freq_sums, uint64_t* freq_blocks
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split,
                             const ranked_args* rk, bool_steps* extra, range_args* rg, filter_args* fl, facet_args* fa,
-                            collapse_args* ca, page_args* pg, sort_args* sv, value_stats_args* vs, group_stats_args* gs) {
+                            collapse_args* ca, page_args* pg, sort_args* sv, value_stats_args* vs, group_stats_args* gs,
+                            percentile_args* pa) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -683,6 +694,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     c.sv = sv;
     c.vs = vs;
     c.gs = gs;
+    c.pa = pa;
     c.n_queries = n_queries;
     c.counts = counts;
     c.s = static_cast<hipStream_t>(stream);
@@ -697,6 +709,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     sort_begin(sv, n_queries);
     value_stats_begin(vs, n_queries);
     group_stats_begin(gs, n_queries);
+    percentile_begin(pa, n_queries);
     if (c.n_pages == 0) return DINT_OK;
     bool mixed = false;
     const int split = may_split ? and_mixed_split(c, stream, &mixed) : DINT_OK;

@@ -449,6 +449,73 @@ static int group_stats_back(const group_stats_args* gs, size_t n_queries, hipStr
     return DINT_OK;
 }
 
+// A percentile call (hip_api_percentiles.inc): the column and the caller's ranks in parts per million, where the call's
+// counts and values go on the host, and where the select lives on the device — two grow-only workspaces of the query index:
+// the counter rows, 1 KiB per (query, percentile), and behind one another the copy of per_million, per (query, percentile)
+// the state {prefix, rank} and the answer, and per query the valued matches. per_million goes up and the states, the answers
+// and the counts are cleared once per call under the lock (percentile_clear); a pass clears its own queries' rows, runs the
+// four rounds of its queries to their end (percentile_launch), and everything comes back once. Where a call takes a null one
+// nothing is planned or launched differently.
+struct percentile_args {
+    const dint_doc_values* values = nullptr;
+    const uint32_t* per_million = nullptr;  // host, n_p words, each <= 1000000 (checked by the entry)
+    uint32_t n_p = 0;
+    uint64_t* h_value_counts = nullptr;  // the caller's, n_queries
+    uint32_t* h_values = nullptr;        // the caller's percentile_values, n_queries * n_p
+    std::vector<uint32_t> h_n;           // out: per query the valued matches, a word each (the entry widens them)
+    uint32_t *d_per_million = nullptr, *d_out = nullptr, *d_n = nullptr, *d_rows = nullptr;  // (set by percentile_clear)
+    percentile_state* d_state = nullptr;
+    size_t recs(size_t n_queries) const { return n_queries * size_t(n_p); }
+};
+// the call is planned and has refused nothing: no query has a valued match, every percentile is 0 until a pass says otherwise
+static void percentile_begin(percentile_args* pa, size_t n_queries) {
+    if (!pa) return;
+    pa->h_n.assign(n_queries, 0u);
+    std::fill(pa->h_value_counts, pa->h_value_counts + n_queries, uint64_t(0));
+    std::fill(pa->h_values, pa->h_values + pa->recs(n_queries), 0u);
+}
+// under the index's lock, once per call, in front of its first launch: per_million goes up, the states, the answers and the
+// counts clear
+static int percentile_clear(dint_query_index* qi, percentile_args* pa, size_t n_queries, hipStream_t s) {
+    const size_t n_recs = pa->recs(n_queries);
+    if (!qi->percentile_rows.ensure(n_recs * kPercentileBins) || !qi->percentile_words.ensure(pa->n_p + 3 * n_recs + n_queries))
+        return DINT_ERR_HIP;
+    pa->d_rows = qi->percentile_rows.p;
+    pa->d_per_million = qi->percentile_words.p;
+    pa->d_state = reinterpret_cast<percentile_state*>(pa->d_per_million + pa->n_p);
+    pa->d_out = pa->d_per_million + pa->n_p + 2 * n_recs;
+    pa->d_n = pa->d_out + n_recs;
+    // (pageable host memory: the copy has left the caller's array when the call returns, and the call waits on the stream
+    // before it does)
+    HIP_TRY(hipMemcpyAsync(pa->d_per_million, pa->per_million, size_t(pa->n_p) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(pa->d_state, 0, (3 * n_recs + n_queries) * 4, s));
+    return DINT_OK;
+}
+// The select over the n_pages pages of qi->cand, in front of ranked_topk; d_page_query[page] + q0: the page's query of the
+// call, and the pass holds the n_ids whole queries from q0 on. Four rounds of percentile_hist_kernel and
+// percentile_resolve_kernel, all on the stream: a round reads the states the round before it left on the device. The rows of
+// the pass's queries are cleared in front of round 0 and, since the queries' percentiles share a row there, in front of
+// round 1; the resolving waves of rounds 1 and 2 clear the row they alone have read.
+static int percentile_launch(const dint_query_index* qi, const percentile_args* pa, uint64_t n_pages, const uint32_t* d_page_query, uint32_t q0,
+                             size_t n_ids, hipStream_t s) {
+    const size_t n_waves = n_ids * pa->n_p;
+    uint32_t* const pass_rows = pa->d_rows + pa->recs(q0) * kPercentileBins;
+    for (uint32_t round = 0; round != kPercentileRounds; ++round) {
+        if (round < 2) HIP_TRY(hipMemsetAsync(pass_rows, 0, n_waves * kPercentileBins * 4, s));
+        hipLaunchKernelGGL(percentile_hist_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, n_pages * kPageSlots,
+                           d_page_query, q0, pa->values->view(), round, pa->n_p, pa->d_state, pa->d_rows);
+        hipLaunchKernelGGL(percentile_resolve_kernel, dim3(uint32_t((n_waves + 3) / 4)), dim3(256), 0, s, pa->d_rows, q0, uint32_t(n_ids),
+                           pa->n_p, round, pa->d_per_million, pa->d_state, pa->d_n, pa->d_out, round == 1 || round == 2 ? 1u : 0u);
+    }
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// ... and the counts' and the answers' way back, on the stream, in front of the call's last wait
+static int percentile_back(percentile_args* pa, size_t n_queries, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(pa->h_n.data(), pa->d_n, n_queries * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(pa->h_values, pa->d_out, pa->recs(n_queries) * 4, hipMemcpyDeviceToHost, s));
+    return DINT_OK;
+}
+
 // the *_queries_freqs entries: a freqs dictionary of the index's device and kind, and somewhere for the sums
 static bool freqs_args_ok(const dint_query_index* qi, const dint_dict* freqs_dict, const uint64_t* freq_sums) {
     return freqs_dict && freq_sums && (!qi || (freqs_dict->device == qi->docs->device && freqs_dict->kind == qi->docs->kind));

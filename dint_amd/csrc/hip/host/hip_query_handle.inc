@@ -86,6 +86,9 @@ struct dint_query_index {
     device_buffer<uint32_t> value_stats_words;
     // the group-stats ranked calls (hip_api_group_stats.inc): per (query, group) of the call its record, three 64-bit words
     device_buffer<unsigned long long> group_stats_recs;
+    // the percentile ranked calls (hip_api_percentiles.inc): per (query, percentile) of the call a row of 256 counters; the
+    // call's per_million and behind them per (query, percentile) the select's state and the answer, then per query its count
+    device_buffer<uint32_t> percentile_rows, percentile_words;
     // dint_check_index (hip_api_check.inc): every block of a list but its last holds 256 postings (the in-index layout:
     // block j of a list is its positions [256 j, 256 j + n)); two pinned staging buffers of a pass's expected postings
     // and their device copies, alternating

@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     "dint_ranked_or_sorted_queries", "dint_ranked_and_sorted_queries",
     "dint_ranked_or_value_stats_queries", "dint_ranked_and_value_stats_queries",
     "dint_ranked_or_group_stats_queries", "dint_ranked_and_group_stats_queries",
+    "dint_ranked_or_percentile_queries", "dint_ranked_and_percentile_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_check_index", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -207,6 +208,10 @@ def _load():
     lib.dint_ranked_and_value_stats_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_or_group_stats_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_and_group_stats_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    # (qi, freqs, wand, k, terms, offsets, filter, values, per_million, n_percentiles, n_queries, counts, matches, scores, docids,
+    # value_counts, percentile_values, stats, blocks_decoded, stream)
+    lib.dint_ranked_or_percentile_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_percentile_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
@@ -1076,6 +1081,47 @@ class QueryIndex:
         return self._ranked_group_stats("dint_ranked_and_group_stats_queries", freqs_dict, wand, queries, facets, values, filter, k,
                                         with_facet_counts)
 
+    def _ranked_percentiles(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, values, percentiles, doc_filter, k: int,
+                            with_stats: bool):
+        per_million = _pack_percentiles(percentiles)
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        value_counts = np.zeros(n, dtype=np.uint64)
+        percentile_values = np.zeros((n, per_million.size), dtype=np.uint32)
+        stats = np.zeros(n, dtype=_VALUE_STATS) if with_stats else None
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 doc_filter._h if doc_filter is not None else None, values._h, per_million.ctypes.data, per_million.size,
+                                 n, counts.ctypes.data, matches.ctypes.data, scores.ctypes.data, docids.ctypes.data,
+                                 value_counts.ctypes.data, percentile_values.ctypes.data,
+                                 stats.ctypes.data if with_stats else None, C.byref(blocks), self._stream()), fn)
+        head = (counts, scores, docids, matches, blocks.value) if with_stats else (counts, scores, docids)
+        return head + (value_counts, percentile_values, stats)
+
+    def ranked_or_percentile_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, values: "DocValues", percentiles,
+                                     filter=None, k: int = 10, with_stats: bool = False):
+        """ranked_or_filtered_queries with exact percentiles of a column over every match (dint_ranked_or_percentile_queries,
+        DESIGN.md 4d-percentiles): values is a DocValues on this index's device, percentiles 1 to 16 numbers in percent, each in
+        [0, 100], in any order, repeats allowed, taken as round(p * 10000) parts per million (ValueError otherwise, before the
+        call), filter a DocFilter of this index or None (unrestricted) -> what ranked_or_filtered_queries returns for (queries,
+        filter, k, with_stats), bit for bit, and behind it value_counts u64[n]: the matches d < values.num_docs of every query,
+        percentile_values u32[n, n_percentiles]: [q, j] = s[((n_q - 1) * per_million[j]) // 1000000] of the ascending sort s of
+        those matches' values (the lower nearest rank; 0 where n_q == 0), and stats: with_stats the value-stats records (n, sum,
+        min, max; no valued match: (0, 0, 0xFFFFFFFF, 0)), else None — then the call launches nothing for them."""
+        return self._ranked_percentiles("dint_ranked_or_percentile_queries", freqs_dict, wand, queries, values, percentiles, filter, k,
+                                        with_stats)
+
+    def ranked_and_percentile_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, values: "DocValues", percentiles,
+                                      filter=None, k: int = 10, with_stats: bool = False):
+        """ranked_and_filtered_queries with exact percentiles of a column over every match (dint_ranked_and_percentile_queries):
+        arguments and outputs as ranked_or_percentile_queries, over the intersection."""
+        return self._ranked_percentiles("dint_ranked_and_percentile_queries", freqs_dict, wand, queries, values, percentiles, filter, k,
+                                        with_stats)
+
     def ranked_pages(self, entry: str, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10, filter=None, facets=None,
                      after=None, max_pages=None, values=None, descending: bool = True):
         """Walks a batch page by page: entry is "or", "and", "or_collapsed" or "and_collapsed" (the
@@ -1487,6 +1533,20 @@ def _pack_value_edges(edges):
     if any(a >= b for a, b in zip(e, e[1:])):
         raise ValueError("value edges: must be strictly ascending")
     return np.array(e, dtype=np.uint32)
+
+
+PERCENTILES_MAX = 16  # DINT_PERCENTILES_MAX (include/dint_hip.h)
+
+
+def _pack_percentiles(percentiles):
+    """-> the percentiles, given in percent, as a contiguous u32 array of parts per million: round(p * 10000). ValueError for
+    none, for more than PERCENTILES_MAX and for a value outside [0, 100]."""
+    p = [float(x) for x in np.asarray(percentiles, dtype=np.float64).reshape(-1).tolist()]
+    if not p or len(p) > PERCENTILES_MAX:
+        raise ValueError(f"percentiles: 1 to {PERCENTILES_MAX}, not {len(p)}")
+    if any(not 0.0 <= x <= 100.0 for x in p):  # (a NaN fails both comparisons)
+        raise ValueError("percentiles: every percentile must lie in [0, 100]")
+    return np.array([int(round(x * 10000)) for x in p], dtype=np.uint32)
 
 
 def _pack_queries(queries):

@@ -922,8 +922,9 @@ int dint_ranked_and_sorted_queries(dint_query_index* qi, const dint_dict* freqs_
  * call runs one launch over the candidate slots in front of the selection per OR pass / per AND call, which gathers one word
  * of the column per live slot and reduces in LDS — at most one global add per bucket present in a page and four atomics on the
  * query's record — and, if hit_values is given, one over the selected keys behind it.
- * Percentiles, sums or means of scores (float sums are not order-independent), several columns per call and the boolean,
- * pruned, collapsed and paged forms are out of scope; statistics per facet group are the group-stats calls below. */
+ * Sums or means of scores (float sums are not order-independent), several columns per call and the boolean, pruned, collapsed
+ * and paged forms are out of scope; statistics per facet group are the group-stats calls and exact percentiles
+ * the percentile calls below. */
 #define DINT_VALUE_STATS_MAX_EDGES 1023u
 typedef struct dint_value_stats { /* 24 bytes: offsets 0, 8, 16, 20 */
     uint64_t n;   /* matches that have a value */
@@ -980,6 +981,52 @@ int dint_ranked_and_group_stats_queries(dint_query_index* qi, const dint_dict* f
                                         const dint_doc_facets* facets, const dint_doc_values* values, size_t n_queries, uint64_t* counts,
                                         uint64_t* matches, float* scores, uint32_t* docids, dint_value_stats* group_stats,
                                         uint32_t* facet_counts, uint64_t* blocks_decoded, void* stream);
+
+/* ---- exact percentiles of a column over the matches of the ranked queries (the median and the tail of what matched) ----
+ * Adds: what a cursor engine computes with a percentiles collector beside its top-k collector — the median price of the
+ * results, the p90 / p99 age of what matched — for a batch of queries, in the call that ranks them, EXACTLY: a histogram needs
+ * its edges in advance and answers only to a bucket's width, and percentiles of fetched hits are wrong as soon as a query has
+ * more than DINT_RANKED_MAX_K matches.
+ * dint_ranked_or_percentile_queries / dint_ranked_and_percentile_queries take the arguments of the filtered calls (filter
+ * nullable: unrestricted), the column (a dint_doc_values), per_million (HOST, n_percentiles ranks in parts per million, each
+ * <= 1000000, in any order, repeats allowed) and the outputs (HOST):
+ *   counts, matches, scores, docids, *blocks_decoded   bit for bit what dint_ranked_or_filtered_queries /
+ *                    dint_ranked_and_filtered_queries return for the same arguments (filter null: the unfiltered answer with
+ *                    the matches counted); the plan depends neither on the column nor on the percentiles; matches, docids and
+ *                    blocks_decoded are nullable
+ *   value_counts[q]  n_q, the matches of query q that have a value, over EVERY match, not over the top k. As for the
+ *                    value-stats calls a match d HAS A VALUE iff d < the column's num_docs
+ *   percentile_values[q * n_percentiles + j] = s[((n_q - 1) * per_million[j]) / 1000000], s the ascending sort of those n_q
+ *                    values, duplicates kept, the division a 64-bit integer division that rounds down (the "lower" nearest
+ *                    rank: no interpolation, the answer is always a value of the column); 0 if n_q == 0. per_million 0 gives
+ *                    the minimum, 1000000 the maximum, 500000 the lower median
+ *   stats[q]         (nullable) exactly what the value-stats call with n_edges == 0 writes: {n, sum, min, max}, the empty record
+ *                    {0, 0, 0xFFFFFFFF, 0}. Null: nothing of the value-stats machinery is launched
+ * Every quantity is an integer count or a value of the column: exact, order-independent and the same from run to run.
+ * DINT_ERR_ARG, before anything is written or launched: whatever the filtered calls refuse; a null values or one on another
+ * device than the index; a filter of another index; a null per_million, value_counts or percentile_values; n_percentiles == 0
+ * or > DINT_PERCENTILES_MAX; a per_million[j] > 1000000; n_queries * n_percentiles > DINT_PERCENTILES_MAX_RECORDS (a counter row
+ * is 1 KiB: 64 MiB of rows; the caller batches). Terms, query_offsets, the handle's lock and the stream are as for the filtered
+ * calls. The rows (1 KiB per (query, percentile)) and the select's words (4 bytes * (n_percentiles + n_queries * (3 *
+ * n_percentiles + 1))) are grow-only workspaces of the query index. Besides the filtered call's launches a call runs, per OR
+ * pass / per AND call and in front of the selection, an MSB-first radix select of four rounds over the candidate slots: per
+ * round one launch that gathers one word of the column per live slot and counts a byte of it in LDS, and one of a wave per
+ * (query, percentile) that scans the 256 counters and fixes that byte of the answer. A round reads the round before it from
+ * device memory; nothing returns to the host in between.
+ * Interpolated percentiles, percentiles per facet group, the rank of a given value and the boolean, pruned, collapsed and paged
+ * forms are out of scope. */
+#define DINT_PERCENTILES_MAX 16u
+#define DINT_PERCENTILES_MAX_RECORDS (1ull << 16)
+int dint_ranked_or_percentile_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                      const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                      const dint_doc_values* values, const uint32_t* per_million, uint32_t n_percentiles, size_t n_queries,
+                                      uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids, uint64_t* value_counts,
+                                      uint32_t* percentile_values, dint_value_stats* stats, uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_percentile_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                       const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                       const dint_doc_values* values, const uint32_t* per_million, uint32_t n_percentiles, size_t n_queries,
+                                       uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids, uint64_t* value_counts,
+                                       uint32_t* percentile_values, dint_value_stats* stats, uint64_t* blocks_decoded, void* stream);
 
 /* ---- the wand data's BM25 maxima from the index, on the device; block maxima for the pruned call --------------
  * Replaces: the max_term_weight half of wand_data's constructor (include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp),

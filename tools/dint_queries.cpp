@@ -1,13 +1,14 @@
 // dint_queries — the reference's `queries` tool (src/queries.cpp:15-153) for the DINT index types, on the device path.
 //
 //   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N]
-//                [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] < query_log
+//                [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] [--percentiles p1,p2,...] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
 //   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
 //               ranked_or_bool | ranked_or_range | ranked_and_range | ranked_or_filtered | ranked_and_filtered |
 //               ranked_or_faceted | ranked_and_faceted | ranked_or_collapsed | ranked_and_collapsed | ranked_or_paged |
 //               ranked_and_paged | ranked_or_sorted | ranked_and_sorted | ranked_or_value_stats | ranked_and_value_stats |
-//               ranked_or_group_stats | ranked_and_group_stats, several separated by ':'
+//               ranked_or_group_stats | ranked_and_group_stats | ranked_or_percentiles | ranked_and_percentiles, several
+//               separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
 //               "Unsupported query type", as the reference does; ranked_or (ranked_or_query, include/ds2i/queries.hpp:387-457,
@@ -75,6 +76,14 @@
 //               the query lines, output and keys are ranked_or's, and the JSON line carries besides "matches", "n_groups" and
 //               the per-group records merged over the log: "group_n", "group_sum", "group_min" and "group_max", arrays of
 //               n_groups (4294967295 and 0 where no match of a group has a value);
+//               ranked_or_percentiles / ranked_and_percentiles (dint_ranked_or_percentile_queries,
+//               dint_ranked_and_percentile_queries: ranked_or / ranked_and with exact percentiles of a column's values over every
+//               match) need --values FILE as the sorted types do and --percentiles p1,p2,... — 1 to 16
+//               decimal percents between 0 and 100 with at most four fractional digits, in any order (percentile_list.hpp) — and
+//               take either --filter FILE or --value-range lo:hi; each must be the only type of its run; the query lines, output
+//               and keys are ranked_or's, and the JSON line carries besides "matches", "value_n" (the matches that have a
+//               value, over the log), "per_million" (the ranks as parsed) and "percentile_sum" (per requested percentile the
+//               sum of its values over the log's queries);
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -103,6 +112,7 @@
 #include "doc_filter_file.hpp"
 #include "doc_values_file.hpp"
 #include "tool_common.hpp"
+#include "percentile_list.hpp"
 #include "value_edges.hpp"
 
 static void dint_ok(int st, const char* what) {
@@ -114,7 +124,7 @@ static double now_us() {
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N] [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] < query_log"
+        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N] [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] [--percentiles p1,p2,...] < query_log"
                   << std::endl;
         return 1;
     }
@@ -128,6 +138,7 @@ int main(int argc, char** argv) {
         const char* value_range = nullptr;  // ranked_*_sorted: lo:hi, the run's filter from the column
         std::string order_name;             // ranked_*_sorted: asc | desc ("": not given)
         const char* edges_text = nullptr;   // ranked_*_value_stats: the bucket boundaries
+        const char* percentiles_text = nullptr;  // ranked_*_percentiles: the ranks, in percent
         bool batch = false;
         size_t runs = 10 + 1;  // src/queries.cpp:13
         size_t pages = 0;      // ranked_*_paged: the pages walked per query (0: not given)
@@ -141,6 +152,7 @@ int main(int argc, char** argv) {
             else if (a == "--order" && i + 1 < argc) order_name = argv[++i];
             else if (a == "--value-range" && i + 1 < argc) value_range = argv[++i];
             else if (a == "--edges" && i + 1 < argc) edges_text = argv[++i];
+            else if (a == "--percentiles" && i + 1 < argc) percentiles_text = argv[++i];
             else if (a == "--pages" && i + 1 < argc) pages = size_t(std::max(1, std::atoi(argv[++i])));
             else if (!wand_filename && a.rfind("--", 0) != 0) wand_filename = argv[i];
             else throw std::runtime_error("unknown parameter");
@@ -195,6 +207,10 @@ int main(int argc, char** argv) {
         for (const char* gstats : {"ranked_or_group_stats", "ranked_and_group_stats"})
             if (!is_gstats && (":" + query_type + ":").find(std::string(":") + gstats + ":") != std::string::npos)
                 throw std::runtime_error(std::string(gstats) + " answers its whole log under --facets and --values: it must be the only query type of a run");
+        const bool is_pct = query_type == "ranked_or_percentiles" || query_type == "ranked_and_percentiles";
+        for (const char* pct : {"ranked_or_percentiles", "ranked_and_percentiles"})
+            if (!is_pct && (":" + query_type + ":").find(std::string(":") + pct + ":") != std::string::npos)
+                throw std::runtime_error(std::string(pct) + " answers its whole log under --values: it must be the only query type of a run");
         if (is_gstats && !facets_filename) {
             std::cerr << query_type << " needs --facets FILE (every line `d g` or `lo:hi g`: document d, or every document of [lo, hi), is in group g)"
                       << std::endl;
@@ -203,12 +219,18 @@ int main(int argc, char** argv) {
         if (!is_paged && !is_sorted && pages) throw std::runtime_error("--pages goes with ranked_or_paged, ranked_and_paged, ranked_or_sorted and ranked_and_sorted only");
         if (is_paged && !pages) pages = 2;
         if (is_sorted && !pages) pages = 1;
-        if (!is_sorted && !is_vstats && !is_gstats && (values_filename || value_range || !order_name.empty()))
+        if (!is_sorted && !is_vstats && !is_gstats && !is_pct && (values_filename || value_range || !order_name.empty()))
             throw std::runtime_error("--values, --order and --value-range go with ranked_or_sorted and ranked_and_sorted only");
-        if ((is_vstats || is_gstats) && !order_name.empty()) throw std::runtime_error("--order goes with ranked_or_sorted and ranked_and_sorted only");
+        if ((is_vstats || is_gstats || is_pct) && !order_name.empty()) throw std::runtime_error("--order goes with ranked_or_sorted and ranked_and_sorted only");
         if (!is_vstats && edges_text) throw std::runtime_error("--edges goes with ranked_or_value_stats and ranked_and_value_stats only");
-        if ((is_sorted || is_vstats || is_gstats) && !values_filename) {
+        if (!is_pct && percentiles_text) throw std::runtime_error("--percentiles goes with ranked_or_percentiles and ranked_and_percentiles only");
+        if ((is_sorted || is_vstats || is_gstats || is_pct) && !values_filename) {
             std::cerr << query_type << " needs --values FILE (every line `d v` or `lo:hi v`: document d, or every document of [lo, hi), has value v)"
+                      << std::endl;
+            return 1;
+        }
+        if (is_pct && !percentiles_text) {
+            std::cerr << query_type << " needs --percentiles p1,p2,... (1 to 16 decimal percents between 0 and 100, at most four fractional digits)"
                       << std::endl;
             return 1;
         }
@@ -217,19 +239,22 @@ int main(int argc, char** argv) {
         if (value_range && filter_filename) throw std::runtime_error("--value-range and --filter exclude each other: a run has one filter");
         if (is_sorted && facets_filename) throw std::runtime_error("--facets does not go with the ranked_*_sorted types");
         if (is_vstats && facets_filename) throw std::runtime_error("--facets does not go with the ranked_*_value_stats types");
+        if (is_pct && facets_filename) throw std::runtime_error("--facets does not go with the ranked_*_percentiles types");
+        std::vector<uint32_t> per_million;
+        if (percentiles_text) per_million = tool::parse_percentiles(percentiles_text);
         std::vector<uint32_t> value_edges;
         if (edges_text) value_edges = tool::parse_value_edges(edges_text);
         uint32_t range_lo = 0, range_hi = 0;
         if (value_range) tool::parse_value_range(value_range, range_lo, range_hi);
         tool::doc_values_column values_column;
-        if (is_sorted || is_vstats || is_gstats) {
+        if (is_sorted || is_vstats || is_gstats || is_pct) {
             std::ifstream vf(values_filename);
             if (!vf) throw std::runtime_error(std::string("could not open the values file ") + values_filename);
             values_column = tool::parse_doc_values(vf);
         }
         if (!needs_facets && !is_paged && !is_gstats && facets_filename)
             throw std::runtime_error("--facets goes with the ranked_*_faceted, ranked_*_collapsed and ranked_*_paged types only");
-        if (!is_filtered && !needs_facets && !is_paged && !is_sorted && !is_vstats && !is_gstats && filter_filename)
+        if (!is_filtered && !needs_facets && !is_paged && !is_sorted && !is_vstats && !is_gstats && !is_pct && filter_filename)
             throw std::runtime_error("--filter goes with the ranked_*_filtered, ranked_*_faceted, ranked_*_collapsed, ranked_*_paged and ranked_*_sorted types only");
         const bool uses_facets = needs_facets || is_gstats || (is_paged && facets_filename);  // (a paged type: the collapsed paged entry)
         tool::doc_facets_map facets_map;
@@ -360,7 +385,7 @@ int main(int argc, char** argv) {
         dint_doc_filter* doc_filter = nullptr;  // ranked_*_filtered: the run's filter
         if (filter_filename) dint_ok(dint_doc_filter_create(qi, filter_bits.words.data(), filter_bits.num_docs, &doc_filter), "dint_doc_filter_create");
         dint_doc_values* doc_values = nullptr;  // ranked_*_sorted, ranked_*_value_stats, ranked_*_group_stats: the run's column, and with --value-range the filter from it
-        if (is_sorted || is_vstats || is_gstats) {
+        if (is_sorted || is_vstats || is_gstats || is_pct) {
             dint_ok(dint_doc_values_create(0, values_column.values.data(), values_column.num_docs, &doc_values), "dint_doc_values_create");
             if (value_range) dint_ok(dint_doc_filter_create_from_values(qi, doc_values, range_lo, range_hi, &doc_filter), "dint_doc_filter_create_from_values");
         }
@@ -389,6 +414,10 @@ int main(int argc, char** argv) {
         const size_t n_buckets = value_edges.empty() ? 0 : value_edges.size() + 1;
         // ranked_*_group_stats: a call's records, n_groups per query
         std::vector<dint_value_stats> group_recs;
+        // ranked_*_percentiles: a call's valued matches per query and its answers, n_pct per query
+        std::vector<uint64_t> value_counts;
+        std::vector<uint32_t> percentile_values;
+        const size_t n_pct = per_million.size();
 
         std::vector<std::string> types;
         for (size_t a = 0; a <= query_type.size();) {
@@ -411,7 +440,8 @@ int main(int argc, char** argv) {
             const bool is_or_sorted = t == "ranked_or_sorted" && wand, is_and_sorted = t == "ranked_and_sorted" && wand;
             const bool is_or_vstats = t == "ranked_or_value_stats" && wand, is_and_vstats = t == "ranked_and_value_stats" && wand;
             const bool is_or_gstats = t == "ranked_or_group_stats" && wand, is_and_gstats = t == "ranked_and_group_stats" && wand;
-            const bool is_ranked = (t == "ranked_and" && wand) || is_or_gstats || is_and_gstats || is_or_vstats || is_and_vstats || is_or_sorted || is_and_sorted || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
+            const bool is_or_pct = t == "ranked_or_percentiles" && wand, is_and_pct = t == "ranked_and_percentiles" && wand;
+            const bool is_ranked = (t == "ranked_and" && wand) || is_or_pct || is_and_pct || is_or_gstats || is_and_gstats || is_or_vstats || is_and_vstats || is_or_sorted || is_and_sorted || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
                                    is_or_range || is_and_range || is_or_filtered || is_and_filtered || is_or_faceted || is_and_faceted ||
                                    is_or_collapsed || is_and_collapsed;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
@@ -565,6 +595,21 @@ int main(int argc, char** argv) {
                                 qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_facets, doc_values, n, q_counts, facet_matches.data(),
                                 top_scores.data(), nullptr, group_recs.data(), nullptr, nullptr, nullptr),
                             "dint_ranked_*_group_stats_queries");
+                } else if (is_or_pct || is_and_pct) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    facet_matches.resize(n);
+                    value_counts.resize(n);
+                    percentile_values.resize(n * n_pct);
+                    // (a call takes at most DINT_PERCENTILES_MAX_RECORDS (query, percentile) pairs: a longer log goes in parts)
+                    const size_t most = size_t(DINT_PERCENTILES_MAX_RECORDS / n_pct);
+                    for (size_t at = 0; at < n; at += most) {
+                        const size_t part = std::min(most, n - at);
+                        dint_ok((is_or_pct ? dint_ranked_or_percentile_queries : dint_ranked_and_percentile_queries)(
+                                    qi, freqs_dict, wand, kTopK, q_terms, q_offs + at, doc_filter, doc_values, per_million.data(), uint32_t(n_pct), part,
+                                    q_counts + at, facet_matches.data() + at, top_scores.data() + at * kTopK, nullptr, value_counts.data() + at,
+                                    percentile_values.data() + at * n_pct, nullptr, nullptr, nullptr),
+                                "dint_ranked_*_percentile_queries");
+                    }
                 } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
@@ -616,6 +661,15 @@ int main(int argc, char** argv) {
                         into[g].max = std::max(into[g].max, r.max);
                     }
             };
+            // a percentile type: the log's valued matches and per requested percentile the sum of its values (the first run's)
+            uint64_t log_value_n = 0;
+            std::vector<uint64_t> percentile_sums(is_pct ? n_pct : 0, 0);
+            auto merge_percentiles = [&](uint64_t& into_n, std::vector<uint64_t>& sums, size_t n) {
+                for (size_t q = 0; q != n; ++q) {
+                    into_n += value_counts[q];
+                    for (size_t j = 0; j != n_pct; ++j) sums[j] += percentile_values[q * n_pct + j];
+                }
+            };
             for (size_t run = 0; run != runs; ++run) {  // op_perftest
                 for (size_t i = 0; i != queries.size(); ++i) {
                     auto const& q = queries[i];
@@ -627,7 +681,8 @@ int main(int argc, char** argv) {
                     if (run == 0) total_one_run += results;
                     if (run == 0 && is_vstats && is_ranked) merge_stats(log_stats, bucket_totals, 1);
                     if (run == 0 && is_gstats && is_ranked) merge_groups(group_totals, 1);
-                    if (run == 0 && (needs_facets || is_paged || is_sorted || is_vstats || is_gstats)) {
+                    if (run == 0 && is_pct && is_ranked) merge_percentiles(log_value_n, percentile_sums, 1);
+                    if (run == 0 && (needs_facets || is_paged || is_sorted || is_vstats || is_gstats || is_pct)) {
                         all_matches += facet_matches[0];
                         if (is_collapsed || (is_paged && doc_facets)) all_collapsed += collapsed_counts[0];
                         for (size_t g = 0; g != facet_totals.size(); ++g) facet_totals[g] += facet_rows[g];
@@ -672,6 +727,13 @@ int main(int argc, char** argv) {
                     if (batch_matches != all_matches || batch_stats.n != log_stats.n || batch_stats.sum != log_stats.sum ||
                         batch_stats.min != log_stats.min || batch_stats.max != log_stats.max || batch_buckets != bucket_totals)
                         throw std::runtime_error("the batch call and the one-query calls reduced other values");
+                } else if (is_pct) {  // ... and select the same values
+                    uint64_t batch_value_n = 0, batch_matches = 0;
+                    std::vector<uint64_t> batch_sums(n_pct, 0);
+                    merge_percentiles(batch_value_n, batch_sums, queries.size());
+                    for (size_t q = 0; q != queries.size(); ++q) batch_matches += facet_matches[q];
+                    if (batch_matches != all_matches || batch_value_n != log_value_n || batch_sums != percentile_sums)
+                        throw std::runtime_error("the batch call and the one-query calls selected other percentiles");
                 } else if (is_gstats) {  // ... and reduce the same values per group
                     std::vector<dint_value_stats> batch_groups(n_groups, dint_value_stats{0, 0, 0xFFFFFFFFu, 0});
                     merge_groups(batch_groups, queries.size());
@@ -708,6 +770,12 @@ int main(int argc, char** argv) {
                 column("group_sum", [](const dint_value_stats& r) { return r.sum; });
                 column("group_min", [](const dint_value_stats& r) { return uint64_t(r.min); });
                 column("group_max", [](const dint_value_stats& r) { return uint64_t(r.max); });
+            } else if (is_pct) {
+                std::cout << ", \"matches\": " << all_matches << ", \"value_n\": " << log_value_n << ", \"per_million\": [";
+                for (size_t j = 0; j != n_pct; ++j) std::cout << (j ? ", " : "") << per_million[j];
+                std::cout << "], \"percentile_sum\": [";
+                for (size_t j = 0; j != n_pct; ++j) std::cout << (j ? ", " : "") << percentile_sums[j];
+                std::cout << "]";
             } else if (is_vstats) {
                 std::cout << ", \"matches\": " << all_matches << ", \"value_n\": " << log_stats.n << ", \"value_sum\": " << log_stats.sum
                           << ", \"value_min\": " << log_stats.min << ", \"value_max\": " << log_stats.max << ", \"buckets\": [";
