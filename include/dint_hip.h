@@ -1167,14 +1167,24 @@ int dint_count_ngrams(int device, int multi, const uint32_t* d_gaps, uint64_t n_
  * of their context in the selection's order (occurrences first) — per context the entries whose count reaches the
  * top_k-th largest count among the n-grams the reference's filter keeps (dictionary_builders.hpp:15-38), ties
  * included: the dictionary built from them is the same, the host sorts tens of thousands of entries instead of
- * tens of millions. */
+ * tens of millions. The filter's total is the sum of the lists' lengths (in the multi flavour the integers past a
+ * list's last whole block count too). A context with fewer than top_k kept n-grams comes back whole; entries the
+ * filter drops come back as well where their count reaches their context's threshold (the selection drops them);
+ * and when there are no more than top_k distinct n-grams in all, every one comes back.
+ * DINT_ERR_ARG (*entries = NULL, *n_entries = 0): entries or n_entries NULL, list_starts not ascending or past n_ints.
+ * No list, or no list with a chunk to count: DINT_OK with *entries = NULL and *n_entries = 0. */
 
 /* The selection half on the device too: of `entries` (dint_count_ngrams' output; in place), the n-grams the reference's
  * filter keeps (dictionary_builders.hpp:15-38), every context's in dictionary order — most frequent first, then the
  * longer, then by their integers (block_statistics.hpp:246-276 freq_length sorter; ties made deterministic) — and of
  * those the first top_k (decreasing_static_frequencies::build, dictionary_builders.hpp:55-75: 65536). A filter kernel, one
  * rocPRIM merge sort whose comparator reads the integers in d_gaps, one scatter. *n_selected entries come back; the
- * host only packs them (dinth_pack_dictionary, include/dint_host.h). */
+ * host only packs them (dinth_pack_dictionary, include/dint_host.h).
+ * The filter: count * (48 * len - 16) / total_ints > 0.0001 / 1000 in double (one ulp above the literal 1e-7: a saving
+ * equal to the quotient is dropped), or len == 1; total_ints is the caller's claim and is not checked against d_gaps. The
+ * integers compare as unsigned. The counts are the caller's too: any value is taken.
+ * DINT_ERR_ARG, with `entries` untouched: top_k == 0, n_selected NULL, an entry with len 0 or above 16, ctx >= 8, or
+ * integers that do not lie inside d_gaps (pos + len > n_ints). */
 int dint_select_ngrams(int device, const uint32_t* d_gaps, uint64_t n_ints, uint64_t total_ints, dint_ngram* entries,
                        size_t n_entries, uint32_t top_k, size_t* n_selected);
 
