@@ -127,26 +127,46 @@ int dint_list_cache_create(const dint_dict* docs_c, const dint_dict* freqs_dict,
 
 void dint_list_cache_destroy(dint_list_cache* c) { delete c; }
 
-int dint_list_cache_decode(const dint_list_cache* c, size_t in_offset, uint32_t* out, size_t n, size_t* consumed) {
+namespace {
+enum class cache_part { either, docs, freqs };
+
+// The part of n integers that starts at in_offset. A docs part without bits (one posting, or consecutive docIDs: a sum of
+// zero) has no bytes, and the freqs part of its block starts where it does: `either` (the offset alone) answers with the docs
+// part there; a caller that knows which part it asks for — the Coder's sum_of_values says — gets that one.
+int list_cache_serve(const dint_list_cache* c, size_t in_offset, cache_part part, uint32_t* out, size_t n, size_t* consumed) {
     if (!c || (!out && n)) return DINT_ERR_ARG;
     if (consumed) *consumed = 0;
     // the block whose docs part starts at in_offset, else the one whose freqs part does (where its docs part ended)
     auto it = std::lower_bound(c->blocks.begin(), c->blocks.end(), in_offset,
                                [](const dint_block_ref& b, size_t off) { return b.in_off < off; });
     size_t b = size_t(it - c->blocks.begin());
-    if (b < c->n_blocks && c->blocks[b].in_off == in_offset) {
+    const bool docs_here = b < c->n_blocks && c->blocks[b].in_off == in_offset;
+    if (docs_here && part != cache_part::freqs) {
         if (n != c->blocks[b].n) return DINT_ERR_ARG;
         if (c->docs_end[b] < in_offset) return DINT_ERR_FORMAT;  // (a block the decode did not reach: its end was never written)
         std::memcpy(out, c->gaps.data() + c->blocks[b].out_off, n * 4);
         if (consumed) *consumed = size_t(c->docs_end[b] - in_offset);
         return DINT_OK;
     }
-    if (!c->with_freqs || b == 0) return DINT_ERR_ARG;
-    b -= 1;  // the last block that starts before in_offset
+    if (!c->with_freqs || part == cache_part::docs) return DINT_ERR_ARG;
+    if (!(docs_here && c->docs_end[b] == in_offset)) {  // (else: this block's own freqs part, behind a docs part of no bytes)
+        if (b == 0) return DINT_ERR_ARG;
+        b -= 1;  // the last block that starts before in_offset
+    }
     if (c->docs_end[b] != in_offset || n != c->blocks[b].n) return DINT_ERR_ARG;
     if (c->freqs_end[b] < in_offset) return DINT_ERR_FORMAT;
     std::memcpy(out, c->freqs.data() + c->blocks[b].out_off, n * 4);
     if (consumed) *consumed = size_t(c->freqs_end[b] - in_offset);
     return DINT_OK;
+}
+}  // namespace
+
+int dint_list_cache_decode(const dint_list_cache* c, size_t in_offset, uint32_t* out, size_t n, size_t* consumed) {
+    return list_cache_serve(c, in_offset, cache_part::either, out, n, consumed);
+}
+
+int dint_list_cache_decode_part(const dint_list_cache* c, size_t in_offset, uint32_t sum_of_values, uint32_t* out, size_t n,
+                                size_t* consumed) {
+    return list_cache_serve(c, in_offset, sum_of_values == 0xFFFFFFFFu ? cache_part::freqs : cache_part::docs, out, n, consumed);
 }
 

@@ -185,12 +185,14 @@ public:
         return nullptr;
     }
     // nullptr: the decoded list does not serve this call — `in` is not the start of a block's part, or it is a freqs
-    // part and the scope was made without a freqs dictionary (DINT_ERR_ARG) — and the caller decodes the block itself
-    uint8_t const* decode(uint8_t const* in, uint32_t* out, size_t n) const {
+    // part and the scope was made without a freqs dictionary (DINT_ERR_ARG) — and the caller decodes the block itself.
+    // sum_of_values says which part is asked for (-1: freqs): a docs part without bits has no bytes, and the freqs part of
+    // its block starts at the same `in`.
+    uint8_t const* decode(uint8_t const* in, uint32_t* out, uint32_t sum_of_values, size_t n) const {
         size_t consumed = 0;
-        const int st = dint_list_cache_decode(m_cache, size_t(in - m_begin), out, n, &consumed);
+        const int st = dint_list_cache_decode_part(m_cache, size_t(in - m_begin), sum_of_values, out, n, &consumed);
         if (st == DINT_ERR_ARG) return nullptr;
-        check(st, "dint_list_cache_decode");
+        check(st, "dint_list_cache_decode_part");
         return in + consumed;
     }
     uint8_t const* end() const { return m_end; }
@@ -233,7 +235,7 @@ struct dint_block_device : HostBlockCoder {
     template <typename Dictionary>
     static uint8_t const* decode(Dictionary const& dict, uint8_t const* in, uint32_t* out, uint32_t sum_of_values, size_t n) {
         if (list_scope_base const* s = list_scope_base::find(in))
-            if (uint8_t const* served = s->decode(in, out, n)) return served;
+            if (uint8_t const* served = s->decode(in, out, sum_of_values, n)) return served;
         uint8_t const* end = in + detail::worst_case_bytes(n);
         if (readable_end() && readable_end() > in && readable_end() < end) end = readable_end();
         return detail::decode_block(dict, in, end, out, sum_of_values, n);
@@ -242,7 +244,7 @@ struct dint_block_device : HostBlockCoder {
     static uint8_t const* decode(Dictionary const& dict, uint8_t const* in, uint8_t const* in_end, uint32_t* out,
                                  uint32_t sum_of_values, size_t n) {
         if (list_scope_base const* s = list_scope_base::find(in))
-            if (uint8_t const* served = s->decode(in, out, n)) return served;
+            if (uint8_t const* served = s->decode(in, out, sum_of_values, n)) return served;
         return detail::decode_block(dict, in, in_end, out, sum_of_values, n);
     }
 };

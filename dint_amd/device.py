@@ -33,7 +33,7 @@ ABI_SYMBOLS = (
     "dint_decode_units", "dint_unit_table_create", "dint_unit_table_destroy", "dint_decode_unit_table", "dint_unit_table_rank_outputs", "dint_probe_placement", "dint_decode_list_host", "dint_last_kernel_ms", "dint_recent_kernel_ms",
     "dint_stream_stats_get",
     "dint_decode_block_host", "dint_index_posting_lists", "dint_decode_posting_blocks",
-    "dint_list_cache_create", "dint_list_cache_decode", "dint_list_cache_destroy",
+    "dint_list_cache_create", "dint_list_cache_decode", "dint_list_cache_decode_part", "dint_list_cache_destroy",
     "dint_block_table_create", "dint_block_table_destroy", "dint_block_table_learn", "dint_block_table_ready", "dint_block_table_info_get", "dint_decode_block_table",
     "dint_query_index_create", "dint_query_index_destroy", "dint_and_queries", "dint_and_queries_freqs", "dint_or_queries", "dint_or_queries_freqs",
     "dint_wand_data_create", "dint_wand_data_destroy", "dint_ranked_and_queries", "dint_ranked_bool_queries", "dint_ranked_or_queries",
@@ -149,6 +149,7 @@ def _load():
     lib.dint_index_posting_lists.argtypes = [vp, sz, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]
     lib.dint_list_cache_create.argtypes = [vp, vp, vp, sz, C.POINTER(vp)]
     lib.dint_list_cache_decode.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
+    lib.dint_list_cache_decode_part.argtypes = [vp, sz, u32, vp, sz, C.POINTER(sz)]
     lib.dint_list_cache_destroy.restype = None
     lib.dint_list_cache_destroy.argtypes = [vp]
     lib.dint_debug_alloc_count.argtypes = [C.POINTER(u64)]
@@ -487,10 +488,16 @@ class ListCache:
 
     __del__ = close
 
-    def decode(self, offset: int, n: int):
+    def decode(self, offset: int, n: int, sum_of_values=None):
+        """sum_of_values: the Coder call's (0xFFFFFFFF: the freqs part that starts at `offset`, else the docs part:
+        dint_list_cache_decode_part); None: whichever part starts there (dint_list_cache_decode)."""
         out = np.empty(n, dtype=np.uint32)
         consumed = C.c_size_t()
-        _check(_lib.dint_list_cache_decode(self._h, offset, out.ctypes.data, n, C.byref(consumed)), "dint_list_cache_decode")
+        if sum_of_values is None:
+            _check(_lib.dint_list_cache_decode(self._h, offset, out.ctypes.data, n, C.byref(consumed)), "dint_list_cache_decode")
+        else:
+            _check(_lib.dint_list_cache_decode_part(self._h, offset, sum_of_values & 0xFFFFFFFF, out.ctypes.data, n,
+                                                    C.byref(consumed)), "dint_list_cache_decode_part")
         return out, consumed.value
 
 

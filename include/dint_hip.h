@@ -244,6 +244,9 @@ int dint_decode_list_host(const dint_dict* dict, const uint8_t* in, size_t in_by
  * granularity, one block per call — dint_list_cache_* decodes a list's blocks at once,
  * dint_decode_posting_blocks many lists'. Nothing past out[n - 1] is written and `out` need not be zeroed (the reference needs
  * both: block_size + overflow zeroed words, dict_posting_list.hpp:104-105, :296).
+ * Pinned by tests/test_gpu_short_blocks.py for every n = 1 .. 255: a docs part without bits (n = 1: out[0] = sum_of_values;
+ * a sum of zero: n zeros) reads nothing and *consumed = 0; the freqs part of n = 1 is its vbyte alone; sums up to
+ * 0xFFFFFFFE on either side (a 5-byte vbyte); `in + in_bytes` may be the block's last byte.
  * Replaces: dint_block::decode / opt_dint_single_dict_block::decode /
  *           opt_dint_multi_dict_block::decode (include/dint/dint_codecs.hpp:13-49, :269-274,
  *           :460-510) and interpolative_block::decode (include/ds2i/block_codecs.hpp:130-150), as
@@ -258,12 +261,21 @@ int dint_decode_block_host(const dint_dict* dict, const uint8_t* in, size_t in_b
  * stored: freq - 1) through the batched kernels on the dictionary's own stream, and downloads; it synchronises that
  * stream only. `decode` = the Coder call for the block part that starts `in_offset` bytes into the list: a memcpy;
  * *consumed = the part's bytes. DINT_ERR_ARG if no part of n integers starts there.
+ * A docs part without bits — a block of one posting, or of consecutive docIDs (a sum of zero) — has NO bytes: *consumed = 0,
+ * and the freqs part of that block starts at the same offset. dint_list_cache_decode, which has the offset alone, answers
+ * with the docs part there; dint_list_cache_decode_part takes the Coder call's sum_of_values as well (0xFFFFFFFF: the freqs
+ * part, anything else: the docs part) and serves the part asked for, DINT_ERR_ARG if that part does not start at in_offset.
+ * A cache made without a freqs dictionary refuses every freqs part (DINT_ERR_ARG: the caller decodes that block itself).
+ * Pinned by tests/test_gpu_short_blocks.py over lists of one posting, of consecutive docIDs, with tails of 1, 128 and 255
+ * postings behind full blocks and without a tail.
  * Replaces: dint_block::decode / interpolative_block::decode as called from dict_posting_list.hpp:298-301, :313-315,
  *           for a list at a time. */
 typedef struct dint_list_cache dint_list_cache;
 int dint_list_cache_create(const dint_dict* docs_dict, const dint_dict* freqs_dict, const uint8_t* list, size_t list_bytes,
                            dint_list_cache** out);
 int dint_list_cache_decode(const dint_list_cache* cache, size_t in_offset, uint32_t* out, size_t n, size_t* consumed);
+int dint_list_cache_decode_part(const dint_list_cache* cache, size_t in_offset, uint32_t sum_of_values, uint32_t* out, size_t n,
+                                size_t* consumed);
 void dint_list_cache_destroy(dint_list_cache* cache);
 
 /* One 256-posting block (the last block of a list may be shorter) of a posting list laid out as
