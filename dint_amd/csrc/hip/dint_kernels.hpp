@@ -40,7 +40,11 @@
 //  * the STREAM is read 8 bytes a lane, a tile (512 bytes) a request, three tiles ahead. The single-dictionary
 //    segments ask for two consecutive tiles back to back at the top of every second tile (DINT_SLOT_BURST), behind the
 //    tile-top wait for the tile's metadata and not in front of it: 1 KB of consecutive stream per request point,
-//    the line two tiles share fetched once, and the tile's front end for the pair to land (kernels/segment.inc).
+//    the line two tiles share fetched once, and the tile's front end for the pair to land (kernels/segment.inc). The vroom
+//    single-dictionary launches TOUCH the rest of a unit's stream in the prologue's trip for its first three tiles: a dword a
+//    lane at a 128-byte stride, up to DINT_STREAM_TOUCH_LANES lines by the unit's n, its value used for nothing
+//    (dint_stream_touch.hpp) — the pairs then find most of their lines in L2 (about half of the stream comes from HBM a second time:
+//    DESIGN.md 4e), and a wave waits for HBM once a unit, not ten times.
 //
 // LDS (160 KB/CU, one 1024-thread workgroup per CU):
 //   [ 256 u16 zeros | hot meta | hot payloads (u16) ]  <= kHotImageWords, shared by 16 waves
@@ -51,6 +55,7 @@
 #include <stdint.h>
 
 #include "dint_hip.h"
+#include "dint_stream_touch.hpp"  // DINT_STREAM_TOUCH_LANES, stream_touch: the lines a vroom single-dictionary unit touches ahead
 
 namespace dint_dev {
 
@@ -82,9 +87,6 @@ static_assert(DINT_SLOT_BURST == 1 || DINT_SLOT_BURST == 2, "DINT_SLOT_BURST: 1 
 #endif
 #ifndef DINT_SLOT_LATE
 #define DINT_SLOT_LATE 0  // A/B only, with DINT_SLOT_BURST 1: the one-tile request behind the tile-top wait, where the pairs go
-#endif
-#ifndef DINT_GATHER_AUX
-#define DINT_GATHER_AUX 0  // cache policy of the metadata / row gathers (L2-resident tables, no reuse in L1)
 #endif
 
 constexpr uint32_t kWave = 64;

@@ -3,6 +3,8 @@
 // only the dictionary source layout differed on the host) is one 16-bit segment.
 // (Chaining such units like the blocks of a multi-dictionary unit — the next unit's first tiles
 // requested while the current one is expanded — was measured in round 1: 5 % slower.)
+// TOUCH: the segment's stream touch (kernels/segment.inc) — the vroom launches only, set at compile time (kernel_body.inc).
+template <bool TOUCH>
 __device__ __forceinline__ void decode_unit_single(const decode_args& a, const wave_ctx& c, uint64_t unit_index, prof_t& pf) {
     const dint_unit* up = a.units + unit_index;
     const uint64_t out_off = up->out_off;
@@ -14,7 +16,7 @@ __device__ __forceinline__ void decode_unit_single(const decode_args& a, const w
     // left as gaps, looked at and cleared again below: nothing is left for a fix-up launch)
     volatile uint8_t* const flag = a.unit_base ? a.gaps_left + unit_index : nullptr;
     if (flag && c.lane == 0) *flag = 0;
-    const uint64_t end = decode_segment<16, kRounds, kGroups, 0>(a, c, a.dict.first, in_off, n, a.out + out_off, ch, pf, false, false,
+    const uint64_t end = decode_segment<16, kRounds, kGroups, 0, TOUCH>(a, c, a.dict.first, in_off, n, a.out + out_off, ch, pf, false, false,
                                                                  a.unit_base ? a.unit_base + unit_index : nullptr,
                                                                  a.unit_base ? a.gaps_left + unit_index : nullptr);
     if (a.end_off && c.lane == 0) a.end_off[unit_index] = end;

@@ -193,7 +193,7 @@ __device__ __forceinline__ void decode_kernel_body(const decode_args& kernarg, c
         } else {
             const uint32_t cc = uniform(a.sched ? uint32_t(a.item_cnt[w]) : 1u);
             if (__builtin_expect(cc > 1, 0)) decode_bundle_listed<false>(a, c, uu, cc, pf);
-            else decode_unit_single(a, c, uu, pf);
+            else decode_unit_single<(!INDEX && !QUERY)>(a, c, uu, pf);  // (the vroom launches: with the stream touch)
         }
         asm volatile("" : "+v"(ticket));
         w = take(ticket);

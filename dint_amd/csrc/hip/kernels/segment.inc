@@ -4,7 +4,9 @@
 // W = 16 / 8: the slot width; 0: `narrow_rt` says (wave-uniform). CHAINED = 1 / 0, or -1: `chained_rt` says.
 // (The multi-dictionary kernel has ONE instantiation for both widths, chained or not: with four, inlined side by
 // side, the register allocator spilled 127 registers to scratch.)
-template <int W, uint32_t ROUNDS, uint32_t GROUPS, int CHAINED_T>
+// TOUCH: the vroom single-dictionary launches (decode_unit_single) — the prologue's trip to memory brings the rest of the unit's
+// stream into L2 as well (dint_stream_touch.hpp). Every other segment compiles to the code it had without it.
+template <int W, uint32_t ROUNDS, uint32_t GROUPS, int CHAINED_T, bool TOUCH = false>
 __device__ __forceinline__ uint64_t decode_segment(const decode_args& a, const wave_ctx& c, const dict_desc& dd, uint64_t in_off,
                                                    uint32_t n, uint32_t* const out, chain_io& ch, prof_t& pf,
                                                    bool narrow_rt = false, bool chained_rt = false,
@@ -38,6 +40,7 @@ __device__ __forceinline__ uint64_t decode_segment(const decode_args& a, const w
     // ... and their loads are global loads (load_lane_slots<true>), not flat ones: vector memory's counter alone.
     constexpr bool kGlobalSlots = DINT_SLOT_GLOBAL != 0 && W == 16 && CHAINED_T == 0;
     constexpr bool kLateSlots = DINT_SLOT_LATE != 0 && W == 16 && CHAINED_T == 0;  // DINT_SLOT_BURST 1 only: see the loop top
+    constexpr bool kTouch = TOUCH && kPaired && DINT_STREAM_TOUCH_LANES != 0;
     const uint64_t in_off_u = uniform64(in_off);
     uint64_t slot_byte = in_off_u;  // first byte of the tile whose slots are loaded next (wave-uniform)
     // kPaired: the stream's bytes from the unit's first on, saturated to 32 bits (wave-uniform)
@@ -60,7 +63,29 @@ __device__ __forceinline__ uint64_t decode_segment(const decode_args& a, const w
         raw1 = load_lane_slots<kGlobalSlots>(narrow, a.enc, slot_byte, lane, a.enc_bytes);
         slot_byte += kTileBytes;
         raw2 = load_lane_slots<kGlobalSlots>(narrow, a.enc, slot_byte, lane, a.enc_bytes);
-        asm volatile("" : "+v"(raw0), "+v"(raw1), "+v"(raw2));
+        if (kTouch) {
+            // ... and in the same trip the lines behind tile 2, a dword of each: lane l asks for the line at stream_touch's
+            // first_line + 128 l and uses its value for nothing. The unit's pair requests — eight or nine more points at which
+            // this wave would stand at the head of the CU's in-order return queue for an HBM latency — then find their lines in
+            // L2. A plain load, consumed at the barrier the three tiles are consumed at: no wait and no request point of its own,
+            // and its register is dead from there on. The lanes past the window ask for the window's last line again (a
+            // clamp, not a branch of the lanes: one request more on a line already asked for); stream_touch keeps every line it
+            // returns inside the stream, and a unit with no window skips the load (wave-uniform).
+            // (The address is a wave-uniform base and the lane's 32-bit offset, like load_lane_slots' global form. Through a
+            // buffer descriptor whose range clips the lanes, the descriptor's four scalars were spilled: 56 -> 67 spilled scalar
+            // registers, which take a second vector register to hold, and decode_single_kernel spilled a vector register.)
+            typedef slot_stream_ptr<true>::type stream_ptr;
+            typedef slot_stream_ptr<true>::x1 dword_ptr;  // (a line of the STREAM: the buffer's own alignment is the caller's)
+            const stream_touch_window tw = stream_touch(in_off_u, uniform(n), a.enc_bytes);
+            uint32_t touched = 0;
+            if (tw.lanes != 0) {
+                const uint32_t l = lane < tw.lanes ? lane : tw.lanes - 1;
+                touched = ((dword_ptr)(((stream_ptr)a.enc + tw.first_line) + kTouchLineBytes * l))->v;
+            }
+            asm volatile("" : "+v"(raw0), "+v"(raw1), "+v"(raw2), "+v"(touched));
+        } else {
+            asm volatile("" : "+v"(raw0), "+v"(raw1), "+v"(raw2));
+        }
         unpack_slots(narrow, raw0, cur);
     }
     ch.valid = false;
