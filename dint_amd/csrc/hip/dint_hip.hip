@@ -3,7 +3,7 @@
 // host/ by subsystem and are included here in order — common helpers, handles and the query calls' staged layouts first,
 // then the extern "C" block (opened in host/hip_api_common.inc, closed at the end of this file): dictionary, vroom
 // decode, in-index decode, the query index and its page decodes, query planning, AND, OR, ranked AND, ranked OR and
-// pruned ranked OR queries, docID-range, document-filter, faceted, collapsed, paged, sorted, value-stats, group-stats and percentile ranked queries, scores of given documents, maxima from the index, the index checked against its collection,
+// pruned ranked OR queries, docID-range, document-filter, faceted, collapsed, paged, group-limited, sorted, value-stats, group-stats and percentile ranked queries, scores of given documents, maxima from the index, the index checked against its collection,
 // statistics, host-pointer calls, list cache.
 #include "dint_hip.h"
 
@@ -40,6 +40,7 @@
 #include "dint_facet_kernels.hpp"
 #include "dint_collapse_kernels.hpp"
 #include "dint_paging_kernels.hpp"
+#include "dint_group_limit_kernels.hpp"
 #include "dint_doc_values_kernels.hpp"
 #include "dint_value_stats_kernels.hpp"
 #include "dint_group_stats_kernels.hpp"
@@ -72,6 +73,7 @@
 #include "host/hip_api_facets.inc"
 #include "host/hip_api_collapse.inc"
 #include "host/hip_api_paging.inc"
+#include "host/hip_api_group_limit.inc"
 #include "host/hip_api_doc_values.inc"
 #include "host/hip_api_value_stats.inc"
 #include "host/hip_api_group_stats.inc"

@@ -47,6 +47,11 @@
 // the pass's slots at the pass's query offset — a pass holds whole queries, so a query's select completes within its pass;
 // per_million goes up and the states are cleared once per call, and the counts and the values come back with the last pass.
 // Without pa nothing is planned or launched differently.
+// gl (dint_ranked_or_group_limit_queries, hip_api_group_limit.inc), with fa and never with ca: behind facet_count_kernel the
+// rounds 0 .. per_group - 1 of group_limit_round_kernel and group_limit_keep_kernel over the pass's slots — a pass holds whole
+// queries, so a query's rounds complete within its pass — in front of page_after_kernel where pg is given, and behind
+// ranked_topk group_limit_hits_kernel over the pass's keys, at the pass's query offset; the table, the counters and the hits
+// are cleared once per call and come back with the last pass. Without gl nothing is planned or launched differently.
 
 // What a ranked OR call with a minimum and exclusions adds to its passes, and what it gets back.
 struct or_bool_args {
@@ -114,12 +119,13 @@ struct or_pass_query {
 // behind the scoring launch, hit_values_kernel behind the selection.
 // gs (with rk; its records up): or_facet_layout staged as for fa, group_stats_kernel behind the scoring launch.
 // pa (with rk; its per_million up, its states cleared): or_facet_layout staged as for fa, the select's rounds behind the scoring launch.
+// gl (with fa; its workspaces cleared): the rounds and the keep launch behind facet_count_kernel, group_limit_hits_kernel behind the selection.
 static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const ranked_args* rk, const std::vector<or_pass_query>& qs,
                        size_t min_stage, unsigned long long* d_counts, size_t n_counts, uint32_t id0, size_t n_ids, hipStream_t s,
                        or_bool_args* xb = nullptr, bool ranged = false, const filter_args* fl = nullptr, const facet_args* fa = nullptr,
                        const collapse_args* ca = nullptr, const page_args* pg = nullptr, const sort_args* sv = nullptr,
                        const value_stats_args* vs = nullptr, const group_stats_args* gs = nullptr,
-                       const percentile_args* pa = nullptr) {
+                       const percentile_args* pa = nullptr, const group_limit_args* gl = nullptr) {
     uint64_t n_pages = 0, n_terms = 0;
     for (const or_pass_query& q : qs) {
         n_terms += q.n;
@@ -256,11 +262,13 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
     if (gs && group_stats_launch(qi, gs, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (pa && percentile_launch(qi, pa, n_pages, qi->d(F.page_query), id0, n_ids, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (ca && collapse_launch(qi, ca, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
+    if (gl && group_limit_launch(qi, gl, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (pg && page_after_launch(qi, pg, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (sv && value_after_launch(qi, sv, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     const int rst = ranked_topk(qi, *rk, page_query, n_ids, s, sv);
     if (rst != DINT_OK) return stream_failed(s, rst);
     if (ca && collapse_hits_launch(qi, ca, fa, n_ids, id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
+    if (gl && group_limit_hits_launch(qi, gl, fa, n_ids, id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (sv && sorted_hits_launch(qi, sv, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     if (vs && hit_values_launch(qi, vs, n_ids, id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
     return DINT_OK;
@@ -271,7 +279,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
                            const ranked_args* rk = nullptr, or_bool_args* xb = nullptr, range_args* rg = nullptr,
                            filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr, page_args* pg = nullptr,
                            sort_args* sv = nullptr, value_stats_args* vs = nullptr, group_stats_args* gs = nullptr,
-                           percentile_args* pa = nullptr) {
+                           percentile_args* pa = nullptr, group_limit_args* gl = nullptr) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -300,6 +308,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     value_stats_begin(vs, n_queries);
     group_stats_begin(gs, n_queries);
     percentile_begin(pa, n_queries);
+    group_limit_begin(gl, n_queries);
     if (op.all == 0) return DINT_OK;
 
     std::lock_guard<std::mutex> lock(qi->mutex);
@@ -333,6 +342,10 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         const int cleared = percentile_clear(qi, pa, n_queries, s);
         if (cleared != DINT_OK) return cleared;
     }
+    if (gl) {
+        const int cleared = group_limit_clear(qi, gl, fa, n_queries, s);
+        if (cleared != DINT_OK) return cleared;
+    }
     // the call's counters: counts[n_queries] then freq sums[n_queries], cleared once, added to by every pass
     if (!qi->freq_sums.ensure(2 * n_queries)) return DINT_ERR_HIP;
     unsigned long long* const d_counts = qi->freq_sums.p;
@@ -358,7 +371,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         ranked_args pass_rk = rk ? *rk : ranked_args{};
         if (rk) pass_rk.keys += uint64_t(q0) * rk->k;  // (the keys of the pass's queries at their own offset)
         const int st = or_run_pass(qi, freqs_dict, rk ? &pass_rk : nullptr, qs, 2 * n_queries * sizeof(unsigned long long), d_counts,
-                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl, fa, ca, pg, sv, vs, gs, pa);
+                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl, fa, ca, pg, sv, vs, gs, pa, gl);
         if (st != DINT_OK) return st;
     }
     if (fa && facet_rows_back(fa, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
@@ -368,6 +381,7 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
     if (vs && value_stats_back(vs, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (gs && group_stats_back(gs, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (pa && percentile_back(pa, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
+    if (gl && group_limit_back(gl, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
     if (fl) HIP_TRY(hipMemcpyAsync(fl->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (rg) HIP_TRY(hipMemcpyAsync(rg->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (xb) HIP_TRY(hipMemcpyAsync(xb->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));

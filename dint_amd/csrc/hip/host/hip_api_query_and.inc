@@ -20,7 +20,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
                             const ranked_args* rk = nullptr, bool_steps* extra = nullptr, range_args* rg = nullptr,
                             filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr,
                             page_args* pg = nullptr, sort_args* sv = nullptr, value_stats_args* vs = nullptr,
-                            group_stats_args* gs = nullptr, percentile_args* pa = nullptr);
+                            group_stats_args* gs = nullptr, percentile_args* pa = nullptr, group_limit_args* gl = nullptr);
 
 // One AND call: what its stages share.
 struct and_call {
@@ -37,6 +37,7 @@ struct and_call {
     value_stats_args* vs = nullptr;         // a value-stats call (ranked): the survivors' values reduced in front of the selection
     group_stats_args* gs = nullptr;         // a group-stats call (ranked): the survivors' values reduced per group in front of the selection
     percentile_args* pa = nullptr;          // a percentile call (ranked): the survivors' values selected from in front of the selection
+    group_limit_args* gl = nullptr;         // a group-limited call (with fa, never with ca): of every group up to per_group survivors are selected from
     size_t n_queries = 0;
     uint64_t* counts = nullptr;
     hipStream_t s = nullptr;
@@ -530,7 +531,10 @@ static int and_batch_rounds(and_call& c, bool searched0, unsigned long long* hos
 // travel to the host with the sums.
 // c.pa (with rk): its per_million sent and its states cleared, the four rounds of the select (percentile_launch) over the
 // survivors directly in front of ranked_topk — the call is one pass, so every query's slots are complete; the counts and the
-// values travel to the host with the sums. ----
+// values travel to the host with the sums.
+// c.gl (with c.fa, never with c.ca): its workspaces cleared, the rounds 0 .. per_group - 1 of group_limit_round_kernel and
+// group_limit_keep_kernel behind facet_count_kernel, in front of page_after_kernel where c.pg is given — the call is one pass,
+// so every query's slots are complete — and group_limit_hits_kernel behind ranked_topk. ----
 static int and_freqs_pass(and_call& c) {
     dint_query_index* qi = c.qi;
     const size_t n_queries = c.n_queries, n_terms = c.rounds + 1;
@@ -597,6 +601,11 @@ static int and_freqs_pass(and_call& c) {
         if (st == DINT_OK) st = collapse_launch(qi, c.ca, c.fa, c.n_pages, c.d_page_query, 0u, c.s);
         if (st != DINT_OK) return c.failed(st);
     }
+    if (rk && c.fa && c.gl) {
+        int st = group_limit_clear(qi, c.gl, c.fa, n_queries, c.s);
+        if (st == DINT_OK) st = group_limit_launch(qi, c.gl, c.fa, c.n_pages, c.d_page_query, 0u, c.s);
+        if (st != DINT_OK) return c.failed(st);
+    }
     if (rk && c.pg) {
         int st = page_begin_device(qi, c.pg, n_queries, c.s);
         if (st == DINT_OK) st = page_after_launch(qi, c.pg, c.n_pages, c.d_page_query, 0u, c.s);
@@ -643,6 +652,11 @@ static int and_freqs_pass(and_call& c) {
         if (st == DINT_OK) st = collapse_back(c.ca, n_queries, c.s);
         if (st != DINT_OK) return c.failed(st);
     }
+    if (rk && c.fa && c.gl) {
+        int st = group_limit_hits_launch(qi, c.gl, c.fa, n_queries, 0u, c.s);
+        if (st == DINT_OK) st = group_limit_back(c.gl, n_queries, c.s);
+        if (st != DINT_OK) return c.failed(st);
+    }
     if (rk && c.fa && facet_rows_back(c.fa, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
     if (rk && c.pg && page_back(c.pg, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
     c.h_sums.resize(n_queries);
@@ -676,7 +690,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
                             size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split,
                             const ranked_args* rk, bool_steps* extra, range_args* rg, filter_args* fl, facet_args* fa,
                             collapse_args* ca, page_args* pg, sort_args* sv, value_stats_args* vs, group_stats_args* gs,
-                            percentile_args* pa) {
+                            percentile_args* pa, group_limit_args* gl) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -695,6 +709,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     c.vs = vs;
     c.gs = gs;
     c.pa = pa;
+    c.gl = gl;
     c.n_queries = n_queries;
     c.counts = counts;
     c.s = static_cast<hipStream_t>(stream);
@@ -710,6 +725,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     value_stats_begin(vs, n_queries);
     group_stats_begin(gs, n_queries);
     percentile_begin(pa, n_queries);
+    group_limit_begin(gl, n_queries);
     if (c.n_pages == 0) return DINT_OK;
     bool mixed = false;
     const int split = may_split ? and_mixed_split(c, stream, &mixed) : DINT_OK;

@@ -234,6 +234,76 @@ static int collapse_back(collapse_args* ca, size_t n_queries, hipStream_t s) {
     return DINT_OK;
 }
 
+// A group-limited call (hip_api_group_limit.inc): a faceted call — it needs fa, whose rows and staged page -> query table it
+// reuses, and is never combined with a collapse_args — that lets up to per_group documents of every group into the
+// selection. Its workspaces are the query index's, sized and cleared once per call (group_limit_clear): the table of keys,
+// 8 bytes per (query, place, group), the survivors' counters behind it, and the hits' groups, group matches and places,
+// n_queries * k words each; per pass the slots' groups (collapse_slot_group). Where a call takes a null one nothing is
+// planned or launched differently.
+struct group_limit_args {
+    uint32_t per_group = 0, k = 0;
+    uint32_t *h_hit_groups = nullptr, *h_hit_group_matches = nullptr, *h_hit_group_ranks = nullptr;  // the caller's, n_queries * k each
+    std::vector<unsigned long long> h_kept;                                                           // per query: the kept documents
+    unsigned long long *d_top = nullptr, *d_kept = nullptr;                                           // (set by group_limit_clear)
+    uint32_t *d_hit_groups = nullptr, *d_hit_group_matches = nullptr, *d_hit_group_ranks = nullptr;
+};
+// the call is planned and has refused nothing: no query has kept a document or has a hit until a pass says otherwise
+static void group_limit_begin(group_limit_args* gl, size_t n_queries) {
+    if (!gl) return;
+    gl->h_kept.assign(n_queries, 0ull);
+    std::fill(gl->h_hit_groups, gl->h_hit_groups + n_queries * gl->k, kFacetNone);
+    std::fill(gl->h_hit_group_matches, gl->h_hit_group_matches + n_queries * gl->k, 0u);
+    std::fill(gl->h_hit_group_ranks, gl->h_hit_group_ranks + n_queries * gl->k, 0u);
+}
+// under the index's lock, once per call, in front of its first launch: the table (a live key is never 0) and the counters
+// zero, every hit in no group with no matches at place 0
+static int group_limit_clear(dint_query_index* qi, group_limit_args* gl, const facet_args* fa, size_t n_queries, hipStream_t s) {
+    const size_t n_top = fa->words(n_queries) * gl->per_group, n_hits = n_queries * gl->k;
+    if (!qi->group_limit_top.ensure(n_top + n_queries) || !qi->group_limit_hits.ensure(3 * n_hits)) return DINT_ERR_HIP;
+    gl->d_top = qi->group_limit_top.p;
+    gl->d_kept = gl->d_top + n_top;
+    gl->d_hit_groups = qi->group_limit_hits.p;
+    gl->d_hit_group_matches = gl->d_hit_groups + n_hits;
+    gl->d_hit_group_ranks = gl->d_hit_group_matches + n_hits;
+    HIP_TRY(hipMemsetAsync(gl->d_top, 0, (n_top + n_queries) * sizeof(unsigned long long), s));
+    HIP_TRY(hipMemsetAsync(gl->d_hit_groups, 0xFF, n_hits * 4, s));
+    HIP_TRY(hipMemsetAsync(gl->d_hit_group_matches, 0, 2 * n_hits * 4, s));
+    return DINT_OK;
+}
+// the rounds 0 .. per_group - 1 of group_limit_round_kernel, in stream order, and group_limit_keep_kernel over the n_pages
+// pages of qi->cand, behind facet_count_launch (the rows count every match) and in front of page_after_kernel and
+// ranked_topk; d_page_query[page] + q0: the page's query of the call
+static int group_limit_launch(dint_query_index* qi, const group_limit_args* gl, const facet_args* fa, uint64_t n_pages,
+                              const uint32_t* d_page_query, uint32_t q0, hipStream_t s) {
+    const uint64_t n_slots = n_pages * kPageSlots;
+    if (!qi->collapse_slot_group.ensure(n_slots)) return DINT_ERR_HIP;
+    const doc_facets_view f = fa->facets->view();
+    for (uint32_t r = 0; r != gl->per_group; ++r)
+        hipLaunchKernelGGL(group_limit_round_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, qi->slot_score.p, n_slots,
+                           d_page_query, q0, f, r, gl->per_group, gl->d_top, qi->collapse_slot_group.p);
+    hipLaunchKernelGGL(group_limit_keep_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, qi->slot_score.p,
+                       qi->collapse_slot_group.p, n_slots, d_page_query, q0, f.n_groups, gl->per_group, gl->d_top, gl->d_kept);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// group_limit_hits_kernel behind ranked_topk, over the keys it selected for the n_ids queries from q0 on (qi->topk_out)
+static int group_limit_hits_launch(const dint_query_index* qi, const group_limit_args* gl, const facet_args* fa, size_t n_ids, uint32_t q0,
+                                   hipStream_t s) {
+    const uint64_t n_out = uint64_t(n_ids) * gl->k;
+    hipLaunchKernelGGL(group_limit_hits_kernel, dim3(uint32_t((n_out + 255) / 256)), dim3(256), 0, s, qi->topk_out.p, uint32_t(n_ids), gl->k, q0,
+                       fa->facets->view(), gl->per_group, fa->d_rows, gl->d_top, gl->d_hit_groups, gl->d_hit_group_matches,
+                       gl->d_hit_group_ranks);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// ... and the counters' and the hits' way back, on the stream, in front of the call's last wait
+static int group_limit_back(group_limit_args* gl, size_t n_queries, hipStream_t s) {
+    const size_t n_hits = n_queries * gl->k;
+    HIP_TRY(hipMemcpyAsync(gl->h_kept.data(), gl->d_kept, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(gl->h_hit_groups, gl->d_hit_groups, n_hits * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(gl->h_hit_group_matches, gl->d_hit_group_matches, n_hits * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(gl->h_hit_group_ranks, gl->d_hit_group_ranks, n_hits * 4, hipMemcpyDeviceToHost, s));
+    return DINT_OK;
+}
+
 // A paged call (hip_api_paging.inc): per query of the call a cursor key — the selection's key (collapse_key) of the last hit
 // the caller has seen, kPageFromStart for a query read from the start, 0 where nothing lies after the cursor — and what the
 // call reports besides its answer: per query the matches (a collapsed call: the kept documents) that are NOT after the

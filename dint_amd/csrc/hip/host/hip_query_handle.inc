@@ -73,6 +73,11 @@ struct dint_query_index {
     // query the kept documents; per slot of a pass its group; per (query, i) the hit's group, then its group's matches
     device_buffer<unsigned long long> collapse_best;
     device_buffer<uint32_t> collapse_slot_group, collapse_hits;
+    // the group-limited ranked calls (hip_api_group_limit.inc): per (query, place, group) of the call a key and behind them
+    // per query the kept documents; per (query, i) the hit's group, then its group's matches, then its place in the group.
+    // The slots' groups of a pass go to collapse_slot_group (written and read under the lock within one pass)
+    device_buffer<unsigned long long> group_limit_top;
+    device_buffer<uint32_t> group_limit_hits;
     // the paged ranked calls (hip_api_paging.inc): per query of the call the cursor's key and behind them per query the
     // matches that are not after it
     device_buffer<unsigned long long> page_keys;

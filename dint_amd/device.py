@@ -44,6 +44,7 @@ ABI_SYMBOLS = (
     "dint_ranked_or_collapsed_queries", "dint_ranked_and_collapsed_queries",
     "dint_ranked_or_paged_queries", "dint_ranked_and_paged_queries",
     "dint_ranked_or_collapsed_paged_queries", "dint_ranked_and_collapsed_paged_queries",
+    "dint_ranked_or_group_limit_queries", "dint_ranked_and_group_limit_queries",
     "dint_doc_values_create", "dint_doc_values_info_get", "dint_doc_values_destroy", "dint_doc_filter_create_from_values",
     "dint_ranked_or_sorted_queries", "dint_ranked_and_sorted_queries",
     "dint_ranked_or_value_stats_queries", "dint_ranked_and_value_stats_queries",
@@ -196,6 +197,8 @@ def _load():
     lib.dint_ranked_and_paged_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_or_collapsed_paged_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_and_collapsed_paged_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_or_group_limit_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_group_limit_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_doc_values_create.argtypes = [C.c_int, vp, u64, C.POINTER(vp)]
     lib.dint_doc_values_info_get.argtypes = [vp, C.POINTER(DocValuesInfo)]
     lib.dint_doc_values_destroy.argtypes = [vp]
@@ -967,6 +970,55 @@ class QueryIndex:
         return self._ranked_collapsed_paged("dint_ranked_and_collapsed_paged_queries", freqs_dict, wand, queries, facets, after, filter, k,
                                             with_stats, with_rows)
 
+    def _ranked_group_limit(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, facets, per_group: int, after, doc_filter,
+                            k: int, with_stats: bool, with_rows: bool):
+        if not 1 <= int(per_group) <= GROUP_LIMIT_MAX:
+            raise ValueError(f"{fn}: per_group must be in 1 .. {GROUP_LIMIT_MAX}, not {per_group!r}")
+        terms, offs = _pack_queries(queries)
+        n = len(queries)
+        cursors = _pack_cursors(after, n)
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        kept = np.zeros(n, dtype=np.uint64)
+        skipped = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        hit_groups = np.zeros((n, k), dtype=np.uint32)
+        hit_group_matches = np.zeros((n, k), dtype=np.uint32)
+        hit_group_ranks = np.zeros((n, k), dtype=np.uint32)
+        rows = np.zeros((n, facets.n_groups), dtype=np.uint32) if with_rows else None
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 doc_filter._h if doc_filter is not None else None, facets._h, int(per_group),
+                                 cursors.ctypes.data if cursors is not None else None, n, counts.ctypes.data, matches.ctypes.data,
+                                 kept.ctypes.data, skipped.ctypes.data, scores.ctypes.data, docids.ctypes.data,
+                                 hit_groups.ctypes.data, hit_group_matches.ctypes.data, hit_group_ranks.ctypes.data,
+                                 rows.ctypes.data if with_rows else None, C.byref(blocks), self._stream()), fn)
+        out = (counts, scores, docids, matches, blocks.value) if with_stats else (counts, scores, docids)
+        out += (kept, hit_groups, hit_group_matches, hit_group_ranks)
+        return (out + (rows,) if with_rows else out) + (skipped,)
+
+    def ranked_or_group_limit_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, facets: "DocFacets", per_group: int,
+                                      after=None, filter=None, k: int = 10, with_stats: bool = False, with_rows: bool = False):
+        """ranked_or_faceted_queries with at most per_group hits per document group (dint_ranked_or_group_limit_queries,
+        DESIGN.md 4d-group-limit): of every group a query matches its min(per_group, matches) matches with the best keys
+        (higher score, then smaller docID) are kept, a match in no group stands for itself, and the top k of the kept
+        documents after the cursor are returned. per_group: 1 .. GROUP_LIMIT_MAX (ValueError otherwise); after as
+        ranked_or_paged_queries takes it, applied to the kept documents -> what ranked_or_collapsed_paged_queries returns
+        for the same arguments, with kept u64[n] where collapsed stands (counts = min(k, kept - skipped)) and
+        hit_group_ranks u32[n, k] behind hit_group_matches: the hit's 0-based place among all matches of its group in key
+        order (< per_group; 0 for an ungrouped hit and past the count); skipped u64[n] stays last. per_group = 1 is the
+        collapsed paged method, every rank 0."""
+        return self._ranked_group_limit("dint_ranked_or_group_limit_queries", freqs_dict, wand, queries, facets, per_group, after, filter, k,
+                                        with_stats, with_rows)
+
+    def ranked_and_group_limit_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, facets: "DocFacets", per_group: int,
+                                       after=None, filter=None, k: int = 10, with_stats: bool = False, with_rows: bool = False):
+        """ranked_and_faceted_queries with at most per_group hits per document group (dint_ranked_and_group_limit_queries):
+        arguments and outputs as ranked_or_group_limit_queries, over the intersection."""
+        return self._ranked_group_limit("dint_ranked_and_group_limit_queries", freqs_dict, wand, queries, facets, per_group, after, filter, k,
+                                        with_stats, with_rows)
+
     def doc_filter_from_values(self, values: "DocValues", lo: int, hi: int) -> "DocFilter":
         """The filter of the documents d < values.num_docs with lo <= v(d) <= hi (closed; lo > hi: the empty filter), built
         on the device from the column (dint_doc_filter_create_from_values): in its info and under every
@@ -1130,9 +1182,10 @@ class QueryIndex:
                                         with_stats)
 
     def ranked_pages(self, entry: str, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10, filter=None, facets=None,
-                     after=None, max_pages=None, values=None, descending: bool = True):
+                     after=None, max_pages=None, values=None, descending: bool = True, per_group=None):
         """Walks a batch page by page: entry is "or", "and", "or_collapsed" or "and_collapsed" (the
-        collapsed ones need facets), or "or_sorted" / "and_sorted" (they need values, a DocValues, and
+        collapsed ones need facets), "or_group_limit" or "and_group_limit" (they need facets and
+        per_group), or "or_sorted" / "and_sorted" (they need values, a DocValues, and
         take descending). The first page starts at `after` (None: from the start); each query's next cursor is its
         last hit, and a query drops out of the batch when a page comes back short (fewer than k hits: nothing lies behind it).
         Yields per page (query ids — indices into `queries` of the queries still in the batch —, counts, scores, docids,
@@ -1141,12 +1194,16 @@ class QueryIndex:
         a call of its own and decodes and scores its queries again."""
         calls = {"or": self.ranked_or_paged_queries, "and": self.ranked_and_paged_queries,
                  "or_collapsed": self.ranked_or_collapsed_paged_queries, "and_collapsed": self.ranked_and_collapsed_paged_queries,
+                 "or_group_limit": self.ranked_or_group_limit_queries, "and_group_limit": self.ranked_and_group_limit_queries,
                  "or_sorted": self.ranked_or_sorted_queries, "and_sorted": self.ranked_and_sorted_queries}
         if entry not in calls:
             raise ValueError(f"ranked_pages: entry must be one of {sorted(calls)}, not {entry!r}")
         collapsed = entry.endswith("_collapsed")
         if collapsed and facets is None:
             raise ValueError("ranked_pages: a collapsed entry needs facets")
+        limited = entry.endswith("_group_limit")
+        if limited and (facets is None or per_group is None):
+            raise ValueError("ranked_pages: a group_limit entry needs facets and per_group")
         if entry.endswith("_sorted"):
             if values is None:
                 raise ValueError("ranked_pages: a sorted entry needs values")
@@ -1174,7 +1231,9 @@ class QueryIndex:
         while len(ids) and (max_pages is None or page < max_pages):
             batch = [queries[i] for i in ids]
             batch_after = [cursors[i] for i in ids]
-            if collapsed:
+            if limited:
+                out = calls[entry](freqs_dict, wand, batch, facets, per_group, after=batch_after, filter=filter, k=k)
+            elif collapsed:
                 out = calls[entry](freqs_dict, wand, batch, facets, after=batch_after, filter=filter, k=k)
             else:
                 out = calls[entry](freqs_dict, wand, batch, after=batch_after, filter=filter, k=k)
@@ -1329,6 +1388,7 @@ class DocFilter:
 
 FACET_NONE = 0xFFFFFFFF        # DINT_FACET_NONE (include/dint_hip.h): a document in no group
 FACETS_MAX_GROUPS = 65536      # DINT_FACETS_MAX_GROUPS
+GROUP_LIMIT_MAX = 16           # DINT_GROUP_LIMIT_MAX: the largest per_group of the group-limited ranked calls
 
 
 def doc_facets_map(group_of, n_groups=None):

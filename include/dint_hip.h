@@ -835,6 +835,53 @@ int dint_ranked_and_collapsed_paged_queries(dint_query_index* qi, const dint_dic
                                             uint32_t* hit_groups, uint32_t* hit_group_matches, uint32_t* facet_counts,
                                             uint64_t* blocks_decoded, void* stream);
 
+/* ---- group-limited ranked queries (up to n hits of every document group) --------------------------------------------
+ * Adds: what a front end most often needs from grouping and the all-or-one collapse cannot give — "at most two results per
+ * site", "three offers per product", "the top five messages per thread". One filtered call per group decodes and scores the
+ * query once per group; over-fetching and cutting on the host ends at DINT_RANKED_MAX_K and is wrong as soon as one group
+ * fills the over-fetch.
+ * dint_ranked_or_group_limit_queries / dint_ranked_and_group_limit_queries take the collapsed paged calls' arguments and
+ * per_group, 1 .. DINT_GROUP_LIMIT_MAX. A document's key is the selection's: the score's bits, then the inverted docID. A
+ * query's KEPT documents are, for every group with at least one match, its min(per_group, matches in the group) matches
+ * with the largest keys — equal scores: the smaller docID first — and every match in no group (DINT_FACET_NONE, or a docID
+ * at or past the map's num_docs), which stands for itself as in the collapsed call. The outputs (HOST):
+ *   kept[q]               the kept documents
+ *   skipped[q]            (nullable) the kept documents that are NOT after after[q]: the cursor applies to the kept documents,
+ *                         AFTER the groups' best are taken, exactly as the collapsed paged calls apply it (NULL or +inf: from
+ *                         the start; a score <= 0 leaves nothing after it; NaN: DINT_ERR_ARG)
+ *   counts[q]             min(k, kept[q] - skipped[q])
+ *   scores, docids        the best k kept documents after the cursor; order and filler are the other ranked calls'
+ *   hit_groups, hit_group_matches   [q * k + i] as the collapsed call defines them
+ *   hit_group_ranks       [q * k + i] the hit's 0-based position among ALL matches of its group in key order: 0 is the
+ *                         group's best, always < per_group; 0 for an ungrouped hit and past the count
+ *   matches, facet_counts, *blocks_decoded   (nullable) the faceted call's, bit for bit: the plan depends on neither
+ *                         per_group nor the cursor
+ * Every kept hit carries exactly the score the unfiltered call gives that document. per_group == 1 is the collapsed paged
+ * call byte for byte, with every rank 0; a per_group of at least the largest group's matches keeps every match, and the hits
+ * are the paged call's.
+ * What it costs: the whole query, the faceted call's launches, and per OR pass / per AND call per_group + 2 more — one pass
+ * over the candidate slots per place (place r of a group is the largest key strictly below its place r - 1: a 64-bit
+ * maximum of integers, exact and the same from run to run), one that kills what lies below a group's last place, and one
+ * over the selected keys. The table of places is a grow-only workspace of the query index, 8 BYTES PER (QUERY, GROUP,
+ * PLACE), cleared once per call; n_queries * n_groups * per_group is capped at 2^27 (1 GiB): the caller batches.
+ * DINT_ERR_ARG, before anything is written or launched: what the collapsed paged calls refuse, a null kept, hit_groups,
+ * hit_group_matches or hit_group_ranks, per_group == 0 or > DINT_GROUP_LIMIT_MAX, and n_queries * n_groups * per_group > 2^27.
+ * A grouped response (k groups with n hits each), a per_group per query, the boolean, pruned and sorted forms and a one-pass
+ * in-register top-n are out of scope. */
+#define DINT_GROUP_LIMIT_MAX 16 /* the largest per_group the group-limited calls take */
+int dint_ranked_or_group_limit_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                       const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                       const dint_doc_facets* facets, uint32_t per_group, const dint_rank_cursor* after, size_t n_queries,
+                                       uint64_t* counts, uint64_t* matches, uint64_t* kept, uint64_t* skipped, float* scores,
+                                       uint32_t* docids, uint32_t* hit_groups, uint32_t* hit_group_matches, uint32_t* hit_group_ranks,
+                                       uint32_t* facet_counts, uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_group_limit_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                        const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                        const dint_doc_facets* facets, uint32_t per_group, const dint_rank_cursor* after, size_t n_queries,
+                                        uint64_t* counts, uint64_t* matches, uint64_t* kept, uint64_t* skipped, float* scores,
+                                        uint32_t* docids, uint32_t* hit_groups, uint32_t* hit_group_matches, uint32_t* hit_group_ranks,
+                                        uint32_t* facet_counts, uint64_t* blocks_decoded, void* stream);
+
 /* ---- document values: ranked hits sorted by a per-document number, value-range filters ------------------------------
  * Adds: what a cursor engine computes with a field-sort collector in place of its top-k queue (ranked_or_query /
  * ranked_and_query, include/ds2i/queries.hpp:309-457, order by score only) — "the matches of this query, newest first" (or

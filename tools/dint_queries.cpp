@@ -1,13 +1,14 @@
 // dint_queries — the reference's `queries` tool (src/queries.cpp:15-153) for the DINT index types, on the device path.
 //
 //   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N]
-//                [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] [--percentiles p1,p2,...] < query_log
+//                [--per-group N] [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] [--percentiles p1,p2,...] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
 //   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
 //               ranked_or_bool | ranked_or_range | ranked_and_range | ranked_or_filtered | ranked_and_filtered |
 //               ranked_or_faceted | ranked_and_faceted | ranked_or_collapsed | ranked_and_collapsed | ranked_or_paged |
 //               ranked_and_paged | ranked_or_sorted | ranked_and_sorted | ranked_or_value_stats | ranked_and_value_stats |
-//               ranked_or_group_stats | ranked_and_group_stats | ranked_or_percentiles | ranked_and_percentiles, several
+//               ranked_or_group_stats | ranked_and_group_stats | ranked_or_percentiles | ranked_and_percentiles |
+//               ranked_or_group_limit | ranked_and_group_limit, several
 //               separated by ':'
 //               (src/queries.cpp:93-111);
 //               ranked_and (BM25 top 10, as the reference's driver asks for) needs the wand file, and without one prints
@@ -54,6 +55,14 @@
 //               the only type of its run; the result counts are the hits summed over the pages, and the JSON line carries
 //               besides "pages", "hits" (the hits of the log's queries over their pages) and "matches" (every match of
 //               the log; with --facets also "collapsed" and "n_groups"); --pages 1 answers what ranked_*_filtered answers;
+//               ranked_or_group_limit / ranked_and_group_limit (dint_ranked_or_group_limit_queries,
+//               dint_ranked_and_group_limit_queries: of every document group a query matches at most N documents are ranked,
+//               DESIGN.md 4d-group-limit) need --facets FILE as the faceted types do and --per-group N (1 to 16), take
+//               --filter FILE and --pages P (default 1: pages of 10 kept documents, each behind the last hit of the one
+//               before), and each must be the only type of its run; the result counts are the hits summed over the pages,
+//               and the JSON line carries besides "pages", "hits", "matches" (every match of the log), "kept" (the kept
+//               documents of the log's queries), "per_group" and "n_groups"; --per-group 1 answers what ranked_*_paged
+//               answers under the same --facets and --pages;
 //               ranked_or_sorted / ranked_and_sorted (dint_ranked_or_sorted_queries, dint_ranked_and_sorted_queries: the matches
 //               ordered by a per-document value) need --values FILE — every line `d v` or `lo:hi v`,
 //               later lines win, a document no line names has value 0 (doc_values_file.hpp) — and take --order asc|desc
@@ -124,7 +133,7 @@ static double now_us() {
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N] [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] [--percentiles p1,p2,...] < query_log"
+        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N] [--per-group N] [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] [--percentiles p1,p2,...] < query_log"
                   << std::endl;
         return 1;
     }
@@ -142,6 +151,7 @@ int main(int argc, char** argv) {
         bool batch = false;
         size_t runs = 10 + 1;  // src/queries.cpp:13
         size_t pages = 0;      // ranked_*_paged: the pages walked per query (0: not given)
+        long per_group = -1;   // ranked_*_group_limit: the hits a document group may show (-1: not given)
         for (int i = 4; i < argc; ++i) {
             std::string a = argv[i];
             if (a == "--batch") batch = true;
@@ -154,6 +164,7 @@ int main(int argc, char** argv) {
             else if (a == "--edges" && i + 1 < argc) edges_text = argv[++i];
             else if (a == "--percentiles" && i + 1 < argc) percentiles_text = argv[++i];
             else if (a == "--pages" && i + 1 < argc) pages = size_t(std::max(1, std::atoi(argv[++i])));
+            else if (a == "--per-group" && i + 1 < argc) per_group = std::max(0, std::atoi(argv[++i]));
             else if (!wand_filename && a.rfind("--", 0) != 0) wand_filename = argv[i];
             else throw std::runtime_error("unknown parameter");
         }
@@ -195,6 +206,22 @@ int main(int argc, char** argv) {
         for (const char* paged : {"ranked_or_paged", "ranked_and_paged"})
             if (!is_paged && (":" + query_type + ":").find(std::string(":") + paged + ":") != std::string::npos)
                 throw std::runtime_error(std::string(paged) + " walks its whole log page by page: it must be the only query type of a run");
+        const bool is_glimit = query_type == "ranked_or_group_limit" || query_type == "ranked_and_group_limit";
+        for (const char* glimit : {"ranked_or_group_limit", "ranked_and_group_limit"})
+            if (!is_glimit && (":" + query_type + ":").find(std::string(":") + glimit + ":") != std::string::npos)
+                throw std::runtime_error(std::string(glimit) + " walks its whole log page by page under --facets: it must be the only query type of a run");
+        if (is_glimit && !facets_filename) {
+            std::cerr << query_type << " needs --facets FILE (every line `d g` or `lo:hi g`: document d, or every document of [lo, hi), is in group g)"
+                      << std::endl;
+            return 1;
+        }
+        if (is_glimit && per_group < 0) {
+            std::cerr << query_type << " needs --per-group N (1 to " << DINT_GROUP_LIMIT_MAX << ": the hits a document group may show)" << std::endl;
+            return 1;
+        }
+        if (!is_glimit && per_group >= 0) throw std::runtime_error("--per-group goes with ranked_or_group_limit and ranked_and_group_limit only");
+        if (is_glimit && (per_group < 1 || per_group > DINT_GROUP_LIMIT_MAX))
+            throw std::runtime_error("--per-group is 1 to " + std::to_string(DINT_GROUP_LIMIT_MAX));
         const bool is_sorted = query_type == "ranked_or_sorted" || query_type == "ranked_and_sorted";
         for (const char* sorted : {"ranked_or_sorted", "ranked_and_sorted"})
             if (!is_sorted && (":" + query_type + ":").find(std::string(":") + sorted + ":") != std::string::npos)
@@ -216,9 +243,9 @@ int main(int argc, char** argv) {
                       << std::endl;
             return 1;
         }
-        if (!is_paged && !is_sorted && pages) throw std::runtime_error("--pages goes with ranked_or_paged, ranked_and_paged, ranked_or_sorted and ranked_and_sorted only");
+        if (!is_paged && !is_sorted && !is_glimit && pages) throw std::runtime_error("--pages goes with ranked_or_paged, ranked_and_paged, ranked_or_sorted and ranked_and_sorted only");
         if (is_paged && !pages) pages = 2;
-        if (is_sorted && !pages) pages = 1;
+        if ((is_sorted || is_glimit) && !pages) pages = 1;
         if (!is_sorted && !is_vstats && !is_gstats && !is_pct && (values_filename || value_range || !order_name.empty()))
             throw std::runtime_error("--values, --order and --value-range go with ranked_or_sorted and ranked_and_sorted only");
         if ((is_vstats || is_gstats || is_pct) && !order_name.empty()) throw std::runtime_error("--order goes with ranked_or_sorted and ranked_and_sorted only");
@@ -252,11 +279,11 @@ int main(int argc, char** argv) {
             if (!vf) throw std::runtime_error(std::string("could not open the values file ") + values_filename);
             values_column = tool::parse_doc_values(vf);
         }
-        if (!needs_facets && !is_paged && !is_gstats && facets_filename)
+        if (!needs_facets && !is_paged && !is_gstats && !is_glimit && facets_filename)
             throw std::runtime_error("--facets goes with the ranked_*_faceted, ranked_*_collapsed and ranked_*_paged types only");
-        if (!is_filtered && !needs_facets && !is_paged && !is_sorted && !is_vstats && !is_gstats && !is_pct && filter_filename)
+        if (!is_filtered && !needs_facets && !is_paged && !is_sorted && !is_vstats && !is_gstats && !is_pct && !is_glimit && filter_filename)
             throw std::runtime_error("--filter goes with the ranked_*_filtered, ranked_*_faceted, ranked_*_collapsed, ranked_*_paged and ranked_*_sorted types only");
-        const bool uses_facets = needs_facets || is_gstats || (is_paged && facets_filename);  // (a paged type: the collapsed paged entry)
+        const bool uses_facets = needs_facets || is_gstats || is_glimit || (is_paged && facets_filename);  // (a paged type: the collapsed paged entry)
         tool::doc_facets_map facets_map;
         if (uses_facets) {
             std::ifstream ff(facets_filename);
@@ -399,6 +426,8 @@ int main(int argc, char** argv) {
         // the tool, which prints totals, does not read them
         std::vector<uint64_t> collapsed_counts;
         std::vector<uint32_t> hit_groups, hit_group_matches;
+        // ranked_*_group_limit: its kept documents go where the collapsed types' do; the hits' places in their groups besides
+        std::vector<uint32_t> hit_group_ranks;
         constexpr uint32_t kTopK = 10;  // ranked_and_query(wdata, 10), src/queries.cpp:106-108
         std::vector<float> top_scores;
         // ranked_*_paged: a page's docIDs and counts, and every query's cursor — the last hit of its page before
@@ -437,13 +466,14 @@ int main(int argc, char** argv) {
             const bool is_or_faceted = t == "ranked_or_faceted" && wand, is_and_faceted = t == "ranked_and_faceted" && wand;
             const bool is_or_collapsed = t == "ranked_or_collapsed" && wand, is_and_collapsed = t == "ranked_and_collapsed" && wand;
             const bool is_or_paged = t == "ranked_or_paged" && wand, is_and_paged = t == "ranked_and_paged" && wand;
+            const bool is_or_glimit = t == "ranked_or_group_limit" && wand, is_and_glimit = t == "ranked_and_group_limit" && wand;
             const bool is_or_sorted = t == "ranked_or_sorted" && wand, is_and_sorted = t == "ranked_and_sorted" && wand;
             const bool is_or_vstats = t == "ranked_or_value_stats" && wand, is_and_vstats = t == "ranked_and_value_stats" && wand;
             const bool is_or_gstats = t == "ranked_or_group_stats" && wand, is_and_gstats = t == "ranked_and_group_stats" && wand;
             const bool is_or_pct = t == "ranked_or_percentiles" && wand, is_and_pct = t == "ranked_and_percentiles" && wand;
             const bool is_ranked = (t == "ranked_and" && wand) || is_or_pct || is_and_pct || is_or_gstats || is_and_gstats || is_or_vstats || is_and_vstats || is_or_sorted || is_and_sorted || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
                                    is_or_range || is_and_range || is_or_filtered || is_and_filtered || is_or_faceted || is_and_faceted ||
-                                   is_or_collapsed || is_and_collapsed;
+                                   is_or_collapsed || is_and_collapsed || is_or_glimit || is_and_glimit;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
                 std::cerr << "Unsupported query type: " << t << std::endl;  // src/queries.cpp:108-110
                 continue;
@@ -512,7 +542,7 @@ int main(int argc, char** argv) {
                                                                   facet_matches.data(), collapsed_counts.data(), top_scores.data(), nullptr,
                                                                   hit_groups.data(), hit_group_matches.data(), nullptr, nullptr, nullptr),
                                 "dint_ranked_and_collapsed_queries");
-                } else if (is_or_paged || is_and_paged) {
+                } else if (is_or_paged || is_and_paged || is_or_glimit || is_and_glimit) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     top_docids.resize(n * kTopK);
                     page_counts.resize(n);
@@ -523,9 +553,17 @@ int main(int argc, char** argv) {
                         collapsed_counts.resize(n);
                         hit_groups.resize(n * kTopK);
                         hit_group_matches.resize(n * kTopK);
+                        hit_group_ranks.resize(n * kTopK);
                     }
                     for (size_t page = 0; page != pages; ++page) {
-                        if (doc_facets)
+                        if (is_or_glimit || is_and_glimit)
+                            dint_ok((is_or_glimit ? dint_ranked_or_group_limit_queries : dint_ranked_and_group_limit_queries)(
+                                        qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_facets, uint32_t(per_group), cursors.data(), n,
+                                        page_counts.data(), facet_matches.data(), collapsed_counts.data(), nullptr, top_scores.data(),
+                                        top_docids.data(), hit_groups.data(), hit_group_matches.data(), hit_group_ranks.data(), nullptr, nullptr,
+                                        nullptr),
+                                    "dint_ranked_*_group_limit_queries");
+                        else if (doc_facets)
                             dint_ok((is_or_paged ? dint_ranked_or_collapsed_paged_queries : dint_ranked_and_collapsed_paged_queries)(
                                         qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_facets, cursors.data(), n, page_counts.data(),
                                         facet_matches.data(), collapsed_counts.data(), nullptr, top_scores.data(), top_docids.data(),
@@ -682,9 +720,9 @@ int main(int argc, char** argv) {
                     if (run == 0 && is_vstats && is_ranked) merge_stats(log_stats, bucket_totals, 1);
                     if (run == 0 && is_gstats && is_ranked) merge_groups(group_totals, 1);
                     if (run == 0 && is_pct && is_ranked) merge_percentiles(log_value_n, percentile_sums, 1);
-                    if (run == 0 && (needs_facets || is_paged || is_sorted || is_vstats || is_gstats || is_pct)) {
+                    if (run == 0 && (needs_facets || is_paged || is_glimit || is_sorted || is_vstats || is_gstats || is_pct)) {
                         all_matches += facet_matches[0];
-                        if (is_collapsed || (is_paged && doc_facets)) all_collapsed += collapsed_counts[0];
+                        if (is_collapsed || is_glimit || (is_paged && doc_facets)) all_collapsed += collapsed_counts[0];
                         for (size_t g = 0; g != facet_totals.size(); ++g) facet_totals[g] += facet_rows[g];
                     }
                     if (run != 0) query_times.push_back(now_us() - tick);  // first run is not timed
@@ -712,7 +750,7 @@ int main(int argc, char** argv) {
                 if (batch_total != total_one_run)
                     throw std::runtime_error("the batch call counted " + std::to_string(batch_total) + " results, the one-query calls " +
                                              std::to_string(total_one_run));
-                if (is_collapsed || is_paged || is_sorted) {  // ... and keep the same documents
+                if (is_collapsed || is_paged || is_glimit || is_sorted) {  // ... and keep the same documents
                     uint64_t batch_matches = 0, batch_collapsed = 0;
                     for (size_t q = 0; q != queries.size(); ++q)
                         batch_matches += facet_matches[q], batch_collapsed += is_collapsed || doc_facets ? collapsed_counts[q] : 0;
@@ -784,6 +822,9 @@ int main(int argc, char** argv) {
             } else if (is_sorted) {
                 std::cout << ", \"pages\": " << pages << ", \"hits\": " << total_one_run << ", \"matches\": " << all_matches << ", \"order\": \""
                           << (sort_order == DINT_SORT_ASC ? "asc" : "desc") << "\"";
+            } else if (is_glimit) {
+                std::cout << ", \"pages\": " << pages << ", \"hits\": " << total_one_run << ", \"matches\": " << all_matches << ", \"kept\": "
+                          << all_collapsed << ", \"per_group\": " << per_group << ", \"n_groups\": " << n_groups;
             } else if (is_paged) {
                 std::cout << ", \"pages\": " << pages << ", \"hits\": " << total_one_run << ", \"matches\": " << all_matches;
                 if (doc_facets) std::cout << ", \"collapsed\": " << all_collapsed << ", \"n_groups\": " << n_groups;
