@@ -9,8 +9,20 @@ __device__ __forceinline__ void decode_unit_single(const decode_args& a, const w
     const dint_unit* up = a.units + unit_index;
     const uint64_t out_off = up->out_off;
     const uint32_t n = up->n;
+    // TOUCH: the unit's byte span, for its window (dint_stream_touch.hpp) — as bundle_schedule_kernel bounds it: up to the next
+    // record of the table (of a scheduled launch: the next UNIT, bundled or not), the stream's end for the last one. The next
+    // record's offset is asked for here, in the same trip as this record.
+    // (decode_args::spans is not looked at: only the in-index launches give spans — every caller that does sets only_full — and
+    // those are compiled without the touch. Reading it here, a pointer out of the kernel-argument segment that own_scalars
+    // leaves to the compiler, took decode_single_kernel from 54 to 71 spilled scalar registers and spilled a vector register.)
+    constexpr bool kSpan = TOUCH && DINT_STREAM_TOUCH_LANES != 0 && DINT_STREAM_TOUCH_LINES != 0;
+    const bool has_next = unit_index + 1 < a.n_units;
+    uint64_t next_in_off = 0;
+    if (kSpan) next_in_off = a.units[has_next ? unit_index + 1 : unit_index].in_off;
     if (n == 0 || n > kMaxUnitInts || out_off > a.out_capacity || a.out_capacity - out_off < n || (a.only_full && n != 256)) return;
     const uint64_t in_off = uniform64(up->in_off);
+    uint32_t span = 0;
+    if (kSpan) span = uniform(unit_stream_span(in_off, n, has_next, next_in_off, a.enc_bytes));
     chain_io ch{};
     // (in-index docs part: the flag is this wave's own — cleared here, set by the segment's first lane if the block had to be
     // left as gaps, looked at and cleared again below: nothing is left for a fix-up launch)
@@ -18,7 +30,7 @@ __device__ __forceinline__ void decode_unit_single(const decode_args& a, const w
     if (flag && c.lane == 0) *flag = 0;
     const uint64_t end = decode_segment<16, kRounds, kGroups, 0, TOUCH>(a, c, a.dict.first, in_off, n, a.out + out_off, ch, pf, false, false,
                                                                  a.unit_base ? a.unit_base + unit_index : nullptr,
-                                                                 a.unit_base ? a.gaps_left + unit_index : nullptr);
+                                                                 a.unit_base ? a.gaps_left + unit_index : nullptr, span);
     if (a.end_off && c.lane == 0) a.end_off[unit_index] = end;
     if (flag && n <= 256) {
         uint32_t left = 0;

@@ -10,7 +10,8 @@ template <int W, uint32_t ROUNDS, uint32_t GROUPS, int CHAINED_T, bool TOUCH = f
 __device__ __forceinline__ uint64_t decode_segment(const decode_args& a, const wave_ctx& c, const dict_desc& dd, uint64_t in_off,
                                                    uint32_t n, uint32_t* const out, chain_io& ch, prof_t& pf,
                                                    bool narrow_rt = false, bool chained_rt = false,
-                                                   const uint32_t* block_base = nullptr, uint8_t* gaps_left = nullptr) {
+                                                   const uint32_t* block_base = nullptr, uint8_t* gaps_left = nullptr,
+                                                   uint32_t touch_span = 0) {  // TOUCH: the unit's stream bytes (wave-uniform), 0: not known
     SECTION(pf, 11, "segment_prologue");
     docid_bases gb;  // (in-index docs part: the block's docID base, asked for now — see docid_bases)
     if (block_base != nullptr) gb.v = *block_base;
@@ -76,13 +77,26 @@ __device__ __forceinline__ uint64_t decode_segment(const decode_args& a, const w
             // registers, which take a second vector register to hold, and decode_single_kernel spilled a vector register.)
             typedef slot_stream_ptr<true>::type stream_ptr;
             typedef slot_stream_ptr<true>::x1 dword_ptr;  // (a line of the STREAM: the buffer's own alignment is the caller's)
-            const stream_touch_window tw = stream_touch(in_off_u, uniform(n), a.enc_bytes);
-            uint32_t touched = 0;
-            if (tw.lanes != 0) {
-                const uint32_t l = lane < tw.lanes ? lane : tw.lanes - 1;
+            // The window is the unit's own lines where decode_unit_single found its span in the table (unit_touch: up to
+            // DINT_STREAM_TOUCH_LINES = 128 of them, through DINT_STREAM_TOUCH_PAST bytes behind the unit's end: the next unit's
+            // first three tiles), the rule of n where it did not. A wave has 64 lanes: the lines from kOneLoad on are a SECOND
+            // load in the same trip, lane l asking for line kOneLoad + l, clamped like the first — issued for the units that
+            // have such lines (wave-uniform; nearly half of the bench's long units), consumed at the same barrier, dead behind it.
+            constexpr uint32_t kOneLoad = DINT_STREAM_TOUCH_LANES;
+            constexpr uint32_t kMaxLines = DINT_STREAM_TOUCH_LINES < 2 * kOneLoad ? DINT_STREAM_TOUCH_LINES : 2 * kOneLoad;
+            const stream_touch_lines tw = unit_touch(in_off_u, uniform(n), uniform(touch_span), a.enc_bytes, kMaxLines);
+            const uint32_t last = tw.lines - 1;
+            uint32_t touched = 0, touched2 = 0;
+            if (tw.lines != 0) {
+                const uint32_t last0 = last < kOneLoad - 1 ? last : kOneLoad - 1;
+                const uint32_t l = lane < last0 ? lane : last0;
                 touched = ((dword_ptr)(((stream_ptr)a.enc + tw.first_line) + kTouchLineBytes * l))->v;
             }
-            asm volatile("" : "+v"(raw0), "+v"(raw1), "+v"(raw2), "+v"(touched));
+            if (kMaxLines > kOneLoad && tw.lines > kOneLoad) {
+                const uint32_t l = kOneLoad + lane < last ? kOneLoad + lane : last;
+                touched2 = ((dword_ptr)(((stream_ptr)a.enc + tw.first_line) + kTouchLineBytes * l))->v;
+            }
+            asm volatile("" : "+v"(raw0), "+v"(raw1), "+v"(raw2), "+v"(touched), "+v"(touched2));
         } else {
             asm volatile("" : "+v"(raw0), "+v"(raw1), "+v"(raw2));
         }
