@@ -30,26 +30,21 @@ static void collapsed_outputs(const collapse_args& ca, const std::vector<unsigne
 // What either entry threads through its call beside rk: the ranged call on null ranges or the filtered call (as the faceted
 // entries have it), the facet rows — kept on the device where facet_counts is null — and the collapse itself.
 struct collapsed_call {
-    std::vector<dint_doc_range> all;
-    range_args rg;
-    filter_args fl;
+    restriction r;
     facet_args fa;
     collapse_args ca;
+    ranked_extras x;
     collapsed_call(const dint_doc_filter* filter, const dint_doc_facets* facets, size_t n_queries, uint32_t k, uint32_t* facet_counts,
-                   uint32_t* hit_groups, uint32_t* hit_group_matches) {
-        if (filter)
-            fl.filter = filter;
-        else
-            rg.ranges = ranges_or_all(nullptr, n_queries, all);
+                   uint32_t* hit_groups, uint32_t* hit_group_matches)
+        : r(filter, nullptr, n_queries) {
         fa.facets = facets;
         fa.h_rows = facet_counts;
         ca.k = k;
         ca.h_hit_groups = hit_groups;
         ca.h_hit_group_matches = hit_group_matches;
+        x.fa = &fa;
+        x.ca = &ca;
     }
-    range_args* ranged() { return fl.filter ? nullptr : &rg; }
-    filter_args* filtered() { return fl.filter ? &fl : nullptr; }
-    uint64_t blocks() const { return fl.filter ? fl.blocks : rg.blocks; }
 };
 
 int dint_ranked_or_collapsed_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
@@ -60,15 +55,12 @@ int dint_ranked_or_collapsed_queries(dint_query_index* qi, const dint_dict* freq
     if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) ||
         !collapsed_args_ok(qi, filter, facets, n_queries, collapsed, hit_groups, hit_group_matches))
         return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
     collapsed_call c(filter, facets, n_queries, k, facet_counts, hit_groups, hit_group_matches);
-    // (or_queries_impl checks the offsets and the terms before anything is written or launched)
-    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk, nullptr, c.ranged(),
-                                   c.filtered(), &c.fa, &c.ca);
+    const int st = ranked_restricted_call(false, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    collapsed_outputs(c.ca, keys, n_queries, k, (filter ? c.fl.h_matches : c.rg.h_matches).data(), counts, matches, collapsed, scores, docids);
+    collapsed_outputs(c.ca, keys, n_queries, k, h_matches.data(), counts, matches, collapsed, scores, docids);
     return DINT_OK;
 }
 
@@ -80,17 +72,11 @@ int dint_ranked_and_collapsed_queries(dint_query_index* qi, const dint_dict* fre
     if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) ||
         !collapsed_args_ok(qi, filter, facets, n_queries, collapsed, hit_groups, hit_group_matches))
         return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    std::vector<uint64_t> freq_sums(n_queries, 0);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
     collapsed_call c(filter, facets, n_queries, k, facet_counts, hit_groups, hit_group_matches);
-    // (and_queries_impl checks the offsets and the terms before anything is written or launched; its counts are the
-    // survivors of the rounds: the matches)
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk,
-                                    nullptr, c.ranged(), c.filtered(), &c.fa, &c.ca);
+    const int st = ranked_restricted_call(true, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    const std::vector<unsigned long long> h_matches(counts, counts + n_queries);
     collapsed_outputs(c.ca, keys, n_queries, k, h_matches.data(), counts, matches, collapsed, scores, docids);
     return DINT_OK;
 }

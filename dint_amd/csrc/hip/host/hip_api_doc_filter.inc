@@ -113,24 +113,13 @@ int dint_ranked_or_filtered_queries(dint_query_index* qi, const dint_dict* freqs
                                     const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter, size_t n_queries,
                                     uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids, uint64_t* blocks_decoded,
                                     void* stream) {
-    // (no filter: the ranged call on null ranges, which is the unfiltered call with the matches counted)
-    if (!filter)
-        return dint_ranked_or_range_queries(qi, freqs_dict, wd, k, terms, query_offsets, nullptr, n_queries, counts, matches, scores, docids,
-                                            blocks_decoded, stream);
-    if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) || filter->qi != qi) return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    filter_args fl;
-    fl.filter = filter;
-    // (or_queries_impl checks the offsets and the terms before anything is written or launched)
-    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk, nullptr, nullptr, &fl);
+    if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) || (filter && filter->qi != qi)) return DINT_ERR_ARG;
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    restriction r(filter, nullptr, n_queries);  // (no filter: the ranged call on null ranges)
+    const int st = ranked_restricted_call(false, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, r,
+                                          ranked_extras(), blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = fl.blocks;
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (matches) matches[q] = fl.h_matches[q];
-        counts[q] = std::min<uint64_t>(fl.h_matches[q], k);
-    }
-    unpack_keys(keys, n_queries, k, counts, scores, docids);
+    restricted_outputs(keys, n_queries, k, h_matches, counts, matches, scores, docids);
     return DINT_OK;
 }
 
@@ -138,25 +127,12 @@ int dint_ranked_and_filtered_queries(dint_query_index* qi, const dint_dict* freq
                                      const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter, size_t n_queries,
                                      uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids, uint64_t* blocks_decoded,
                                      void* stream) {
-    if (!filter)
-        return dint_ranked_and_range_queries(qi, freqs_dict, wd, k, terms, query_offsets, nullptr, n_queries, counts, matches, scores, docids,
-                                             blocks_decoded, stream);
-    if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) || filter->qi != qi) return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    std::vector<uint64_t> freq_sums(n_queries, 0);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    filter_args fl;
-    fl.filter = filter;
-    // (and_queries_impl checks the offsets and the terms before anything is written or launched; its counts are the
-    // survivors of the rounds, which run behind the kill: the matches in the filter)
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk,
-                                    nullptr, nullptr, &fl);
+    if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) || (filter && filter->qi != qi)) return DINT_ERR_ARG;
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    restriction r(filter, nullptr, n_queries);  // (no filter: the ranged call on null ranges)
+    const int st = ranked_restricted_call(true, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, r,
+                                          ranked_extras(), blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = fl.blocks;
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (matches) matches[q] = counts[q];
-        counts[q] = std::min<uint64_t>(counts[q], k);
-    }
-    unpack_keys(keys, n_queries, k, counts, scores, docids);
+    restricted_outputs(keys, n_queries, k, h_matches, counts, matches, scores, docids);
     return DINT_OK;
 }

@@ -66,16 +66,12 @@ static bool sorted_args_ok(const dint_query_index* qi, const dint_dict* freqs_di
 // What a sorted entry threads through its call beside rk: the ranged call on null ranges or the filtered call, as
 // dint_ranked_or_filtered_queries chooses, and the column, the order and the cursors as keys.
 struct sorted_call {
-    std::vector<dint_doc_range> all;
-    range_args rg;
-    filter_args fl;
+    restriction r;
     sort_args sv;
+    ranked_extras x;
     sorted_call(const dint_doc_filter* filter, const dint_doc_values* values, uint32_t order, uint32_t k, const dint_value_cursor* after,
-                bool want_scores, size_t n_queries) {
-        if (filter)
-            fl.filter = filter;
-        else
-            rg.ranges = ranges_or_all(nullptr, n_queries, all);
+                bool want_scores, size_t n_queries)
+        : r(filter, nullptr, n_queries) {
         sv.values = values;
         sv.order = order;
         sv.k = k;
@@ -89,10 +85,8 @@ struct sorted_call {
             sv.set[q] = 1;
             sv.any_set = true;
         }
+        x.sv = &sv;
     }
-    range_args* ranged() { return fl.filter ? nullptr : &rg; }
-    filter_args* filtered() { return fl.filter ? &fl : nullptr; }
-    uint64_t blocks() const { return fl.filter ? fl.blocks : rg.blocks; }
 };
 
 // the outputs from what the call brought back: h_matches[q] the matches, sv.h_skipped[q] those not after the cursor, keys the
@@ -122,15 +116,11 @@ int dint_ranked_or_sorted_queries(dint_query_index* qi, const dint_dict* freqs_d
                                   uint64_t* blocks_decoded, void* stream) {
     if (!sorted_args_ok(qi, freqs_dict, wd, k, query_offsets, filter, values, order, n_queries, counts, docids)) return DINT_ERR_ARG;
     sorted_call c(filter, values, order, k, after, scores != nullptr, n_queries);
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (or_queries_impl checks the offsets and the terms before anything is written or launched)
-    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk, nullptr, c.ranged(),
-                                   c.filtered(), nullptr, nullptr, nullptr, &c.sv);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    const int st = ranked_restricted_call(false, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    sorted_outputs(c.sv, keys, n_queries, k, (filter ? c.fl.h_matches : c.rg.h_matches).data(), counts, matches, skipped, hit_values, docids,
-                   scores);
+    sorted_outputs(c.sv, keys, n_queries, k, h_matches.data(), counts, matches, skipped, hit_values, docids, scores);
     return DINT_OK;
 }
 
@@ -141,16 +131,10 @@ int dint_ranked_and_sorted_queries(dint_query_index* qi, const dint_dict* freqs_
                                    uint64_t* blocks_decoded, void* stream) {
     if (!sorted_args_ok(qi, freqs_dict, wd, k, query_offsets, filter, values, order, n_queries, counts, docids)) return DINT_ERR_ARG;
     sorted_call c(filter, values, order, k, after, scores != nullptr, n_queries);
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    std::vector<uint64_t> freq_sums(n_queries, 0);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (and_queries_impl checks the offsets and the terms before anything is written or launched; its counts are the
-    // survivors of the rounds, counted in front of the cursor's kill: the matches)
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk,
-                                    nullptr, c.ranged(), c.filtered(), nullptr, nullptr, nullptr, &c.sv);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    const int st = ranked_restricted_call(true, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    const std::vector<unsigned long long> h_matches(counts, counts + n_queries);
     sorted_outputs(c.sv, keys, n_queries, k, h_matches.data(), counts, matches, skipped, hit_values, docids, scores);
     return DINT_OK;
 }

@@ -88,30 +88,17 @@ int dint_ranked_or_faceted_queries(dint_query_index* qi, const dint_dict* freqs_
     if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) ||
         !faceted_args_ok(qi, filter, facets, n_queries, facet_counts))
         return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (no filter: the ranged call on null ranges, as dint_ranked_or_filtered_queries has it)
-    std::vector<dint_doc_range> all;
-    range_args rg;
-    filter_args fl;
-    if (filter)
-        fl.filter = filter;
-    else
-        rg.ranges = ranges_or_all(nullptr, n_queries, all);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    restriction r(filter, nullptr, n_queries);
     facet_args fa;
     fa.facets = facets;
     fa.h_rows = facet_counts;
-    // (or_queries_impl checks the offsets and the terms before anything is written or launched)
-    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk, nullptr,
-                                   filter ? nullptr : &rg, filter ? &fl : nullptr, &fa);
+    ranked_extras x;
+    x.fa = &fa;
+    const int st = ranked_restricted_call(false, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, r, x,
+                                          blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    const std::vector<unsigned long long>& h_matches = filter ? fl.h_matches : rg.h_matches;
-    if (blocks_decoded) *blocks_decoded = filter ? fl.blocks : rg.blocks;
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (matches) matches[q] = h_matches[q];
-        counts[q] = std::min<uint64_t>(h_matches[q], k);
-    }
-    unpack_keys(keys, n_queries, k, counts, scores, docids);
+    restricted_outputs(keys, n_queries, k, h_matches, counts, matches, scores, docids);
     return DINT_OK;
 }
 
@@ -122,29 +109,16 @@ int dint_ranked_and_faceted_queries(dint_query_index* qi, const dint_dict* freqs
     if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) ||
         !faceted_args_ok(qi, filter, facets, n_queries, facet_counts))
         return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    std::vector<uint64_t> freq_sums(n_queries, 0);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    std::vector<dint_doc_range> all;
-    range_args rg;
-    filter_args fl;
-    if (filter)
-        fl.filter = filter;
-    else
-        rg.ranges = ranges_or_all(nullptr, n_queries, all);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    restriction r(filter, nullptr, n_queries);
     facet_args fa;
     fa.facets = facets;
     fa.h_rows = facet_counts;
-    // (and_queries_impl checks the offsets and the terms before anything is written or launched; its counts are the
-    // survivors of the rounds, and the rows are counted over exactly those slots)
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk,
-                                    nullptr, filter ? nullptr : &rg, filter ? &fl : nullptr, &fa);
+    ranked_extras x;
+    x.fa = &fa;
+    const int st = ranked_restricted_call(true, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, r, x,
+                                          blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = filter ? fl.blocks : rg.blocks;
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (matches) matches[q] = counts[q];
-        counts[q] = std::min<uint64_t>(counts[q], k);
-    }
-    unpack_keys(keys, n_queries, k, counts, scores, docids);
+    restricted_outputs(keys, n_queries, k, h_matches, counts, matches, scores, docids);
     return DINT_OK;
 }

@@ -50,19 +50,14 @@ static void group_limit_outputs(const group_limit_args& gl, const page_args& pg,
 // What either entry threads through its call beside rk: the ranged call on null ranges or the filtered call (as the faceted
 // entries have it), the facet rows — kept on the device where facet_counts is null —, the limit itself and the cursors.
 struct group_limit_call {
-    std::vector<dint_doc_range> all;
-    range_args rg;
-    filter_args fl;
+    restriction r;
     facet_args fa;
     group_limit_args gl;
     page_args pg;
-    bool paged = false;  // some query has a cursor: page_after_kernel runs
+    ranked_extras x;
     group_limit_call(const dint_doc_filter* filter, const dint_doc_facets* facets, size_t n_queries, uint32_t k, uint32_t per_group,
-                     uint32_t* facet_counts, uint32_t* hit_groups, uint32_t* hit_group_matches, uint32_t* hit_group_ranks) {
-        if (filter)
-            fl.filter = filter;
-        else
-            rg.ranges = ranges_or_all(nullptr, n_queries, all);
+                     uint32_t* facet_counts, uint32_t* hit_groups, uint32_t* hit_group_matches, uint32_t* hit_group_ranks)
+        : r(filter, nullptr, n_queries) {
         fa.facets = facets;
         fa.h_rows = facet_counts;
         gl.per_group = per_group;
@@ -70,19 +65,18 @@ struct group_limit_call {
         gl.h_hit_groups = hit_groups;
         gl.h_hit_group_matches = hit_group_matches;
         gl.h_hit_group_ranks = hit_group_ranks;
+        x.fa = &fa;
+        x.gl = &gl;
     }
-    // the cursors as keys; false: a NaN score. A call whose every query reads from the start plans no page_args at all:
+    // the cursors as keys; false: a NaN score. A call whose every query reads from the start threads no page_args at all:
     // page_after_kernel runs only where a cursor is given.
     bool cursors(const dint_rank_cursor* after, size_t n_queries) {
         if (!page_cursor_keys(after, n_queries, pg.keys)) return false;
-        paged = std::any_of(pg.keys.begin(), pg.keys.end(), [](unsigned long long key) { return key != kPageFromStart; });
+        const bool paged = std::any_of(pg.keys.begin(), pg.keys.end(), [](unsigned long long key) { return key != kPageFromStart; });
+        x.pg = paged ? &pg : nullptr;
         pg.h_skipped.assign(n_queries, 0ull);
         return true;
     }
-    range_args* ranged() { return fl.filter ? nullptr : &rg; }
-    filter_args* filtered() { return fl.filter ? &fl : nullptr; }
-    page_args* cursor() { return paged ? &pg : nullptr; }
-    uint64_t blocks() const { return fl.filter ? fl.blocks : rg.blocks; }
 };
 
 int dint_ranked_or_group_limit_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
@@ -98,15 +92,11 @@ int dint_ranked_or_group_limit_queries(dint_query_index* qi, const dint_dict* fr
         return DINT_ERR_ARG;
     group_limit_call c(filter, facets, n_queries, k, per_group, facet_counts, hit_groups, hit_group_matches, hit_group_ranks);
     if (!c.cursors(after, n_queries)) return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (or_queries_impl checks the offsets and the terms before anything is written or launched)
-    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk, nullptr, c.ranged(),
-                                   c.filtered(), &c.fa, nullptr, c.cursor(), nullptr, nullptr, nullptr, nullptr, &c.gl);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    const int st = ranked_restricted_call(false, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    group_limit_outputs(c.gl, c.pg, keys, n_queries, k, (filter ? c.fl.h_matches : c.rg.h_matches).data(), counts, matches, kept, skipped, scores,
-                        docids);
+    group_limit_outputs(c.gl, c.pg, keys, n_queries, k, h_matches.data(), counts, matches, kept, skipped, scores, docids);
     return DINT_OK;
 }
 
@@ -123,16 +113,10 @@ int dint_ranked_and_group_limit_queries(dint_query_index* qi, const dint_dict* f
         return DINT_ERR_ARG;
     group_limit_call c(filter, facets, n_queries, k, per_group, facet_counts, hit_groups, hit_group_matches, hit_group_ranks);
     if (!c.cursors(after, n_queries)) return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    std::vector<uint64_t> freq_sums(n_queries, 0);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (and_queries_impl checks the offsets and the terms before anything is written or launched; its counts are the
-    // survivors of the rounds: the matches)
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk,
-                                    nullptr, c.ranged(), c.filtered(), &c.fa, nullptr, c.cursor(), nullptr, nullptr, nullptr, nullptr, &c.gl);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    const int st = ranked_restricted_call(true, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    const std::vector<unsigned long long> h_matches(counts, counts + n_queries);
     group_limit_outputs(c.gl, c.pg, keys, n_queries, k, h_matches.data(), counts, matches, kept, skipped, scores, docids);
     return DINT_OK;
 }

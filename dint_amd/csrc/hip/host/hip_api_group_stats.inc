@@ -26,27 +26,21 @@ static bool group_stats_handles_ok(const dint_query_index* qi, const dint_doc_fi
 // dint_ranked_or_filtered_queries chooses, the map, the column and the caller's records, and the faceted call's rows where
 // the caller takes them.
 struct group_stats_call {
-    std::vector<dint_doc_range> all;
-    range_args rg;
-    filter_args fl;
+    restriction r;
     facet_args fa;
     group_stats_args gs;
+    ranked_extras x;
     group_stats_call(const dint_doc_filter* filter, const dint_doc_facets* facets, const dint_doc_values* values, size_t n_queries,
-                     dint_value_stats* group_stats, uint32_t* facet_counts) {
-        if (filter)
-            fl.filter = filter;
-        else
-            rg.ranges = ranges_or_all(nullptr, n_queries, all);
+                     dint_value_stats* group_stats, uint32_t* facet_counts)
+        : r(filter, nullptr, n_queries) {
         fa.facets = facets;
         fa.h_rows = facet_counts;
         gs.facets = facets;
         gs.values = values;
         gs.h_recs = group_stats;
+        x.fa = facet_counts ? &fa : nullptr;
+        x.gs = &gs;
     }
-    range_args* ranged() { return fl.filter ? nullptr : &rg; }
-    filter_args* filtered() { return fl.filter ? &fl : nullptr; }
-    facet_args* faceted() { return fa.h_rows ? &fa : nullptr; }
-    uint64_t blocks() const { return fl.filter ? fl.blocks : rg.blocks; }
 };
 
 int dint_ranked_or_group_stats_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
@@ -59,19 +53,11 @@ int dint_ranked_or_group_stats_queries(dint_query_index* qi, const dint_dict* fr
         !group_stats_handles_ok(qi, filter, facets, values, n_queries))
         return DINT_ERR_ARG;
     group_stats_call c(filter, facets, values, n_queries, group_stats, facet_counts);
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (or_queries_impl checks the offsets and the terms before anything is written or launched)
-    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk, nullptr, c.ranged(),
-                                   c.filtered(), c.faceted(), nullptr, nullptr, nullptr, nullptr, &c.gs);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    const int st = ranked_restricted_call(false, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    const std::vector<unsigned long long>& h_matches = filter ? c.fl.h_matches : c.rg.h_matches;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (matches) matches[q] = h_matches[q];
-        counts[q] = std::min<uint64_t>(h_matches[q], k);
-    }
-    unpack_keys(keys, n_queries, k, counts, scores, docids);
+    restricted_outputs(keys, n_queries, k, h_matches, counts, matches, scores, docids);
     return DINT_OK;
 }
 
@@ -85,19 +71,10 @@ int dint_ranked_and_group_stats_queries(dint_query_index* qi, const dint_dict* f
         !group_stats_handles_ok(qi, filter, facets, values, n_queries))
         return DINT_ERR_ARG;
     group_stats_call c(filter, facets, values, n_queries, group_stats, facet_counts);
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    std::vector<uint64_t> freq_sums(n_queries, 0);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (and_queries_impl checks the offsets and the terms before anything is written or launched; its counts are the
-    // survivors of the rounds, and the records are reduced over exactly those slots)
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk,
-                                    nullptr, c.ranged(), c.filtered(), c.faceted(), nullptr, nullptr, nullptr, nullptr, &c.gs);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    const int st = ranked_restricted_call(true, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (matches) matches[q] = counts[q];
-        counts[q] = std::min<uint64_t>(counts[q], k);
-    }
-    unpack_keys(keys, n_queries, k, counts, scores, docids);
+    restricted_outputs(keys, n_queries, k, h_matches, counts, matches, scores, docids);
     return DINT_OK;
 }

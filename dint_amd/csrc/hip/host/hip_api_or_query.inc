@@ -17,41 +17,11 @@
 // under the call's filter, the term records still describe the whole lists, the scoring launch is
 // ranked_or_filtered_score_kernel, which finds a block's page through the filter's live rank and counts the matches into
 // the call's counters; those come back with the last pass. Without fl nothing is planned or launched differently.
-// fa (dint_ranked_or_faceted_queries, hip_api_facets.inc), with rk and with rg or fl: the pass's page -> query table is staged
-// besides, and facet_count_kernel runs between the scoring launch and ranked_topk, over the pass's slots in cand; it adds
-// to the call's facet rows, cleared once per call, which come back with the last pass. Without fa nothing is planned or
-// launched differently.
-// ca (dint_ranked_or_collapsed_queries, hip_api_collapse.inc), with fa: behind facet_count_kernel, collapse_best_kernel and
-// collapse_keep_kernel over the pass's slots — a pass holds whole queries, so a query's slots are complete — and behind
-// ranked_topk collapse_hits_kernel over the pass's keys, at the pass's query offset; the table, the counters and the hits are
-// cleared once per call and come back with the last pass. Without ca nothing is planned or launched differently.
-// pg (dint_ranked_or_paged_queries, hip_api_paging.inc), with rk and with rg or fl: the pass's page -> query table is staged as
-// for fa, and page_after_kernel runs directly in front of ranked_topk — behind the collapse launches where ca is given — over
-// the pass's slots, at the pass's query offset; the cursor keys go up and the counters are cleared once per call, and the
-// counters come back with the last pass. Without pg nothing is planned or launched differently.
-// sv (dint_ranked_or_sorted_queries, hip_api_doc_values.inc), with rk and with rg or fl: the pass's page -> query table is staged
-// as for fa, value_after_kernel runs directly in front of ranked_topk, which sorts its runs by the column's value, and
-// sorted_hits_kernel behind it, both over the pass's slots at the pass's query offset; the cursor keys and flags go up and the
-// counters and hit scores are cleared once per call, and come back with the last pass. Without sv nothing is planned or
-// launched differently.
-// vs (dint_ranked_or_value_stats_queries, hip_api_value_stats.inc), with rk and with rg or fl: the pass's page -> query table is
-// staged as for fa, and value_stats_kernel runs between the scoring launch and ranked_topk, over the pass's slots at the pass's
-// query offset, hit_values_kernel behind the selection over the pass's keys; the records and the edges go up and the rows and
-// hit values are cleared once per call, and come back with the last pass. Without vs nothing is planned or launched differently.
-// gs (dint_ranked_or_group_stats_queries, hip_api_group_stats.inc), with rk and with rg or fl: the pass's page -> query table is
-// staged as for fa, and group_stats_kernel runs between the scoring launch and ranked_topk, over the pass's slots at the pass's
-// query offset; the records go up empty once per call and come back with the last pass. Without gs nothing is planned or
-// launched differently.
-// pa (dint_ranked_or_percentile_queries, hip_api_percentiles.inc), with rk and with rg or fl: the pass's page -> query table is
-// staged as for fa, and the four rounds of the select (percentile_launch) run between the scoring launch and ranked_topk, over
-// the pass's slots at the pass's query offset — a pass holds whole queries, so a query's select completes within its pass;
-// per_million goes up and the states are cleared once per call, and the counts and the values come back with the last pass.
-// Without pa nothing is planned or launched differently.
-// gl (dint_ranked_or_group_limit_queries, hip_api_group_limit.inc), with fa and never with ca: behind facet_count_kernel the
-// rounds 0 .. per_group - 1 of group_limit_round_kernel and group_limit_keep_kernel over the pass's slots — a pass holds whole
-// queries, so a query's rounds complete within its pass — in front of page_after_kernel where pg is given, and behind
-// ranked_topk group_limit_hits_kernel over the pass's keys, at the pass's query offset; the table, the counters and the hits
-// are cleared once per call and come back with the last pass. Without gl nothing is planned or launched differently.
+// x (the faceted, collapsed, paged, group-limited, sorted, value-stats, group-stats and percentile entries), with rk and with
+// rg or fl: its workspaces are cleared once per call, a pass stages its page -> query table besides and runs x's launches in
+// front of ranked_topk and behind it, over the pass's slots in cand at the pass's query offset — a pass holds whole queries,
+// so a query's slots are complete — and its results come back with the last pass (ranked_extras: the steps and their order).
+// Without any nothing is planned or launched differently.
 
 // What a ranked OR call with a minimum and exclusions adds to its passes, and what it gets back.
 struct or_bool_args {
@@ -110,22 +80,11 @@ struct or_pass_query {
 // or_range_layout staged behind the pass's own, and ranked_or_range_score_kernel scores, adding the matches to d_counts.
 // fl (with rk and d_counts, not ranged): a term record's pages are its list's live blocks, the record itself the whole
 // list's; nothing more is staged, and ranked_or_filtered_score_kernel scores, adding the matches to d_counts.
-// fa (with rk; its rows cleared): or_facet_layout staged behind the others, facet_count_kernel behind the scoring launch.
-// ca (with fa; its workspaces cleared): the two collapse launches behind that one, collapse_hits_kernel behind the selection.
-// pg (with rk; its keys up and its counters cleared): or_facet_layout staged as for fa, page_after_kernel in front of the selection.
-// sv (with rk; its keys up, its counters and hit scores cleared): or_facet_layout staged as for fa, value_after_kernel in front of
-// the selection, which runs by value, sorted_hits_kernel behind it.
-// vs (with rk; its records and edges up, its rows and hit values cleared): or_facet_layout staged as for fa, value_stats_kernel
-// behind the scoring launch, hit_values_kernel behind the selection.
-// gs (with rk; its records up): or_facet_layout staged as for fa, group_stats_kernel behind the scoring launch.
-// pa (with rk; its per_million up, its states cleared): or_facet_layout staged as for fa, the select's rounds behind the scoring launch.
-// gl (with fa; its workspaces cleared): the rounds and the keep launch behind facet_count_kernel, group_limit_hits_kernel behind the selection.
+// x (with rk; its workspaces cleared): or_facet_layout staged behind the others where x wants the page -> query table;
+// x.before_selection behind the scoring launch and xb's steps, x.after_selection behind the selection.
 static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const ranked_args* rk, const std::vector<or_pass_query>& qs,
                        size_t min_stage, unsigned long long* d_counts, size_t n_counts, uint32_t id0, size_t n_ids, hipStream_t s,
-                       or_bool_args* xb = nullptr, bool ranged = false, const filter_args* fl = nullptr, const facet_args* fa = nullptr,
-                       const collapse_args* ca = nullptr, const page_args* pg = nullptr, const sort_args* sv = nullptr,
-                       const value_stats_args* vs = nullptr, const group_stats_args* gs = nullptr,
-                       const percentile_args* pa = nullptr, const group_limit_args* gl = nullptr) {
+                       const ranked_extras& x, or_bool_args* xb = nullptr, bool ranged = false, const filter_args* fl = nullptr) {
     uint64_t n_pages = 0, n_terms = 0;
     for (const or_pass_query& q : qs) {
         n_terms += q.n;
@@ -138,8 +97,8 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
             if (q.n) n_steps = std::max<size_t>(n_steps, xb->not_at[q.id + 1] - xb->not_at[q.id]);
     const or_bool_layout B(L.words, xb ? n_pages : 0, xb ? n_terms : 0, n_steps * n_ids, n_steps);
     const or_range_layout R(B.words, ranged ? n_terms : 0);
-    const or_facet_layout F(R.words, fa || pg || sv || vs || gs || pa ? n_pages : 0);
-    const size_t up_words = F.words;  // (without xb, fa, pg, sv, vs, gs and pa and not ranged: L.words)
+    const or_facet_layout F(R.words, x.wants_page_query() ? n_pages : 0);
+    const size_t up_words = F.words;  // (without xb and x's table and not ranged: L.words)
     if (qi->stage(std::max<size_t>(up_words * 4, min_stage)) != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     uint32_t *page_block = qi->h(L.page_block), *page_term = qi->h(L.page_term), *term_order = qi->h(L.term_order);
     std::vector<uint32_t> page_query(rk ? n_pages : 0);  // (ranked_topk's: the pass's queries, from 0)
@@ -170,7 +129,7 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
             }
         }
     }
-    if ((fa || pg || sv || vs || gs || pa) && n_pages) std::memcpy(qi->h(F.page_query), page_query.data(), n_pages * 4);
+    if (x.wants_page_query() && n_pages) std::memcpy(qi->h(F.page_query), page_query.data(), n_pages * 4);
     if (xb) {
         if (n_pages) std::memcpy(qi->h(B.page_query), page_query.data(), n_pages * 4);
         std::memset(qi->h(B.not_first), 0, (B.words - B.not_first) * 4);
@@ -257,29 +216,15 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
                            d_counts + id0);
         if (hipGetLastError() != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     }
-    if (fa && facet_count_launch(qi, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    if (vs && value_stats_launch(qi, vs, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    if (gs && group_stats_launch(qi, gs, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    if (pa && percentile_launch(qi, pa, n_pages, qi->d(F.page_query), id0, n_ids, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    if (ca && collapse_launch(qi, ca, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    if (gl && group_limit_launch(qi, gl, fa, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    if (pg && page_after_launch(qi, pg, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    if (sv && value_after_launch(qi, sv, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    const int rst = ranked_topk(qi, *rk, page_query, n_ids, s, sv);
-    if (rst != DINT_OK) return stream_failed(s, rst);
-    if (ca && collapse_hits_launch(qi, ca, fa, n_ids, id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    if (gl && group_limit_hits_launch(qi, gl, fa, n_ids, id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    if (sv && sorted_hits_launch(qi, sv, n_pages, qi->d(F.page_query), id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    if (vs && hit_values_launch(qi, vs, n_ids, id0, s) != DINT_OK) return stream_failed(s, DINT_ERR_HIP);
-    return DINT_OK;
+    int rst = x.before_selection(qi, n_pages, qi->d(F.page_query), id0, n_ids, s);
+    if (rst == DINT_OK) rst = ranked_topk(qi, *rk, page_query, n_ids, s, x.sv);
+    if (rst == DINT_OK) rst = x.after_selection(qi, n_pages, qi->d(F.page_query), id0, n_ids, s);
+    return rst != DINT_OK ? stream_failed(s, rst) : DINT_OK;
 }
 
 static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
-                           size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream,
-                           const ranked_args* rk = nullptr, or_bool_args* xb = nullptr, range_args* rg = nullptr,
-                           filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr, page_args* pg = nullptr,
-                           sort_args* sv = nullptr, value_stats_args* vs = nullptr, group_stats_args* gs = nullptr,
-                           percentile_args* pa = nullptr, group_limit_args* gl = nullptr) {
+                           size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, const ranked_extras& x,
+                           const ranked_args* rk = nullptr, or_bool_args* xb = nullptr, range_args* rg = nullptr, filter_args* fl = nullptr) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -301,51 +246,14 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         fl->blocks = op.all;
         fl->h_matches.assign(n_queries, 0ull);
     }
-    facet_rows_begin(fa, n_queries);
-    collapse_begin(ca, n_queries);
-    page_begin(pg, n_queries);
-    sort_begin(sv, n_queries);
-    value_stats_begin(vs, n_queries);
-    group_stats_begin(gs, n_queries);
-    percentile_begin(pa, n_queries);
-    group_limit_begin(gl, n_queries);
+    x.begin(n_queries);
     if (op.all == 0) return DINT_OK;
 
     std::lock_guard<std::mutex> lock(qi->mutex);
     HIP_TRY(hipSetDevice(qi->docs->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (fa) {
-        const int cleared = facet_rows_clear(qi, fa, n_queries, s);
-        if (cleared != DINT_OK) return cleared;
-    }
-    if (ca) {
-        const int cleared = collapse_clear(qi, ca, fa, n_queries, s);
-        if (cleared != DINT_OK) return cleared;
-    }
-    if (pg) {
-        const int begun = page_begin_device(qi, pg, n_queries, s);
-        if (begun != DINT_OK) return begun;
-    }
-    if (sv) {
-        const int begun = sort_begin_device(qi, sv, n_queries, s);
-        if (begun != DINT_OK) return begun;
-    }
-    if (vs) {
-        const int cleared = value_stats_clear(qi, vs, n_queries, s);
-        if (cleared != DINT_OK) return cleared;
-    }
-    if (gs) {
-        const int cleared = group_stats_clear(qi, gs, n_queries, s);
-        if (cleared != DINT_OK) return cleared;
-    }
-    if (pa) {
-        const int cleared = percentile_clear(qi, pa, n_queries, s);
-        if (cleared != DINT_OK) return cleared;
-    }
-    if (gl) {
-        const int cleared = group_limit_clear(qi, gl, fa, n_queries, s);
-        if (cleared != DINT_OK) return cleared;
-    }
+    const int cleared = x.clear(qi, n_queries, s);
+    if (cleared != DINT_OK) return cleared;
     // the call's counters: counts[n_queries] then freq sums[n_queries], cleared once, added to by every pass
     if (!qi->freq_sums.ensure(2 * n_queries)) return DINT_ERR_HIP;
     unsigned long long* const d_counts = qi->freq_sums.p;
@@ -371,17 +279,11 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
         ranked_args pass_rk = rk ? *rk : ranked_args{};
         if (rk) pass_rk.keys += uint64_t(q0) * rk->k;  // (the keys of the pass's queries at their own offset)
         const int st = or_run_pass(qi, freqs_dict, rk ? &pass_rk : nullptr, qs, 2 * n_queries * sizeof(unsigned long long), d_counts,
-                                   n_queries, uint32_t(q0), q1 - q0, s, xb, rg != nullptr, fl, fa, ca, pg, sv, vs, gs, pa, gl);
+                                   n_queries, uint32_t(q0), q1 - q0, s, x, xb, rg != nullptr, fl);
         if (st != DINT_OK) return st;
     }
-    if (fa && facet_rows_back(fa, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
-    if (ca && collapse_back(ca, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
-    if (pg && page_back(pg, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
-    if (sv && sort_back(sv, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
-    if (vs && value_stats_back(vs, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
-    if (gs && group_stats_back(gs, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
-    if (pa && percentile_back(pa, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
-    if (gl && group_limit_back(gl, n_queries, s) != DINT_OK) return DINT_ERR_HIP;
+    const int back = x.back(n_queries, s);
+    if (back != DINT_OK) return back;
     if (fl) HIP_TRY(hipMemcpyAsync(fl->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (rg) HIP_TRY(hipMemcpyAsync(rg->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (xb) HIP_TRY(hipMemcpyAsync(xb->h_matches.data(), d_counts, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -405,11 +307,11 @@ static int or_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, co
 
 int dint_or_queries(dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries,
                     uint64_t* counts, void* stream) {
-    return or_queries_impl(qi, nullptr, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream);
+    return or_queries_impl(qi, nullptr, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, ranked_extras());
 }
 
 int dint_or_queries_freqs(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                           size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks_decoded, void* stream) {
     if (!freqs_args_ok(qi, freqs_dict, freq_sums)) return DINT_ERR_ARG;
-    return or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums, freq_blocks_decoded, stream);
+    return or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums, freq_blocks_decoded, stream, ranked_extras());
 }

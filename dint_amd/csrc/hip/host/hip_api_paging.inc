@@ -36,39 +36,21 @@ static void paged_outputs(const page_args& pg, const std::vector<unsigned long l
     unpack_keys(keys, n_queries, k, counts, scores, docids);
 }
 
-// What a plain paged entry threads through its call beside rk: the ranged call on null ranges or the filtered call, as
-// dint_ranked_or_filtered_queries chooses, and the cursors.
-struct paged_call {
-    std::vector<dint_doc_range> all;
-    range_args rg;
-    filter_args fl;
-    page_args pg;
-    paged_call(const dint_doc_filter* filter, size_t n_queries) {
-        if (filter)
-            fl.filter = filter;
-        else
-            rg.ranges = ranges_or_all(nullptr, n_queries, all);
-    }
-    range_args* ranged() { return fl.filter ? nullptr : &rg; }
-    filter_args* filtered() { return fl.filter ? &fl : nullptr; }
-    uint64_t blocks() const { return fl.filter ? fl.blocks : rg.blocks; }
-};
-
 int dint_ranked_or_paged_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
                                  const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
                                  const dint_rank_cursor* after, size_t n_queries, uint64_t* counts, uint64_t* matches, uint64_t* skipped,
                                  float* scores, uint32_t* docids, uint64_t* blocks_decoded, void* stream) {
     if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) || (filter && filter->qi != qi)) return DINT_ERR_ARG;
-    paged_call c(filter, n_queries);
-    if (!page_cursor_keys(after, n_queries, c.pg.keys)) return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (or_queries_impl checks the offsets and the terms before anything is written or launched)
-    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk, nullptr, c.ranged(),
-                                   c.filtered(), nullptr, nullptr, &c.pg);
+    page_args pg;
+    if (!page_cursor_keys(after, n_queries, pg.keys)) return DINT_ERR_ARG;
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    restriction r(filter, nullptr, n_queries);
+    ranked_extras x;
+    x.pg = &pg;
+    const int st = ranked_restricted_call(false, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, r, x,
+                                          blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    paged_outputs(c.pg, keys, n_queries, k, (filter ? c.fl.h_matches : c.rg.h_matches).data(), counts, matches, skipped, scores, docids);
+    paged_outputs(pg, keys, n_queries, k, h_matches.data(), counts, matches, skipped, scores, docids);
     return DINT_OK;
 }
 
@@ -77,19 +59,16 @@ int dint_ranked_and_paged_queries(dint_query_index* qi, const dint_dict* freqs_d
                                   const dint_rank_cursor* after, size_t n_queries, uint64_t* counts, uint64_t* matches, uint64_t* skipped,
                                   float* scores, uint32_t* docids, uint64_t* blocks_decoded, void* stream) {
     if (!ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) || (filter && filter->qi != qi)) return DINT_ERR_ARG;
-    paged_call c(filter, n_queries);
-    if (!page_cursor_keys(after, n_queries, c.pg.keys)) return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    std::vector<uint64_t> freq_sums(n_queries, 0);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (and_queries_impl checks the offsets and the terms before anything is written or launched; its counts are the
-    // survivors of the rounds, counted in front of the cursor's kill: the matches)
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk,
-                                    nullptr, c.ranged(), c.filtered(), nullptr, nullptr, &c.pg);
+    page_args pg;
+    if (!page_cursor_keys(after, n_queries, pg.keys)) return DINT_ERR_ARG;
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    restriction r(filter, nullptr, n_queries);
+    ranked_extras x;
+    x.pg = &pg;
+    const int st = ranked_restricted_call(true, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, r, x,
+                                          blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    const std::vector<unsigned long long> h_matches(counts, counts + n_queries);
-    paged_outputs(c.pg, keys, n_queries, k, h_matches.data(), counts, matches, skipped, scores, docids);
+    paged_outputs(pg, keys, n_queries, k, h_matches.data(), counts, matches, skipped, scores, docids);
     return DINT_OK;
 }
 
@@ -117,16 +96,13 @@ int dint_ranked_or_collapsed_paged_queries(dint_query_index* qi, const dint_dict
         return DINT_ERR_ARG;
     page_args pg;
     if (!page_cursor_keys(after, n_queries, pg.keys)) return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
     collapsed_call c(filter, facets, n_queries, k, facet_counts, hit_groups, hit_group_matches);
-    // (or_queries_impl checks the offsets and the terms before anything is written or launched)
-    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk, nullptr, c.ranged(),
-                                   c.filtered(), &c.fa, &c.ca, &pg);
+    c.x.pg = &pg;
+    const int st = ranked_restricted_call(false, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    collapsed_paged_outputs(c.ca, pg, keys, n_queries, k, (filter ? c.fl.h_matches : c.rg.h_matches).data(), counts, matches, collapsed, skipped,
-                            scores, docids);
+    collapsed_paged_outputs(c.ca, pg, keys, n_queries, k, h_matches.data(), counts, matches, collapsed, skipped, scores, docids);
     return DINT_OK;
 }
 
@@ -141,17 +117,12 @@ int dint_ranked_and_collapsed_paged_queries(dint_query_index* qi, const dint_dic
         return DINT_ERR_ARG;
     page_args pg;
     if (!page_cursor_keys(after, n_queries, pg.keys)) return DINT_ERR_ARG;
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    std::vector<uint64_t> freq_sums(n_queries, 0);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
     collapsed_call c(filter, facets, n_queries, k, facet_counts, hit_groups, hit_group_matches);
-    // (and_queries_impl checks the offsets and the terms before anything is written or launched; its counts are the
-    // survivors of the rounds: the matches)
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk,
-                                    nullptr, c.ranged(), c.filtered(), &c.fa, &c.ca, &pg);
+    c.x.pg = &pg;
+    const int st = ranked_restricted_call(true, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    const std::vector<unsigned long long> h_matches(counts, counts + n_queries);
     collapsed_paged_outputs(c.ca, pg, keys, n_queries, k, h_matches.data(), counts, matches, collapsed, skipped, scores, docids);
     return DINT_OK;
 }

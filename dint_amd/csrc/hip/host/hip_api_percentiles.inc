@@ -21,17 +21,13 @@ static bool percentile_host_args_ok(const dint_doc_values* values, const uint32_
 // What a percentile entry threads through its call beside rk: the ranged call on null ranges or the filtered call, as
 // dint_ranked_or_filtered_queries chooses, the select's arguments and, where stats is given, the value-stats call's.
 struct percentile_call {
-    std::vector<dint_doc_range> all;
-    range_args rg;
-    filter_args fl;
+    restriction r;
     value_stats_args vs;
     percentile_args pa;
+    ranked_extras x;
     percentile_call(const dint_doc_filter* filter, const dint_doc_values* values, const uint32_t* per_million, uint32_t n_percentiles,
-                    uint32_t k, size_t n_queries, uint64_t* value_counts, uint32_t* percentile_values, dint_value_stats* stats) {
-        if (filter)
-            fl.filter = filter;
-        else
-            rg.ranges = ranges_or_all(nullptr, n_queries, all);
+                    uint32_t k, size_t n_queries, uint64_t* value_counts, uint32_t* percentile_values, dint_value_stats* stats)
+        : r(filter, nullptr, n_queries) {
         pa.values = values;
         pa.per_million = per_million;
         pa.n_p = n_percentiles;
@@ -40,11 +36,9 @@ struct percentile_call {
         vs.values = values;
         vs.k = k;
         vs.h_stats = stats;
+        x.vs = stats ? &vs : nullptr;  // (null: nothing of the value-stats machinery runs)
+        x.pa = &pa;
     }
-    range_args* ranged() { return fl.filter ? nullptr : &rg; }
-    filter_args* filtered() { return fl.filter ? &fl : nullptr; }
-    value_stats_args* with_stats() { return vs.h_stats ? &vs : nullptr; }  // (null: nothing of the value-stats machinery runs)
-    uint64_t blocks() const { return fl.filter ? fl.blocks : rg.blocks; }
     // behind the call's last wait: the counts, a word each on the device, as the caller takes them
     void widen_counts(size_t n_queries) {
         for (size_t q = 0; q != n_queries; ++q) pa.h_value_counts[q] = pa.h_n[q];
@@ -60,20 +54,12 @@ int dint_ranked_or_percentile_queries(dint_query_index* qi, const dint_dict* fre
         !ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) || !value_stats_handles_ok(qi, filter, values))
         return DINT_ERR_ARG;
     percentile_call c(filter, values, per_million, n_percentiles, k, n_queries, value_counts, percentile_values, stats);
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (or_queries_impl checks the offsets and the terms before anything is written or launched)
-    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk, nullptr, c.ranged(),
-                                   c.filtered(), nullptr, nullptr, nullptr, nullptr, c.with_stats(), nullptr, &c.pa);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    const int st = ranked_restricted_call(false, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    const std::vector<unsigned long long>& h_matches = filter ? c.fl.h_matches : c.rg.h_matches;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (matches) matches[q] = h_matches[q];
-        counts[q] = std::min<uint64_t>(h_matches[q], k);
-    }
     c.widen_counts(n_queries);
-    unpack_keys(keys, n_queries, k, counts, scores, docids);
+    restricted_outputs(keys, n_queries, k, h_matches, counts, matches, scores, docids);
     return DINT_OK;
 }
 
@@ -86,20 +72,11 @@ int dint_ranked_and_percentile_queries(dint_query_index* qi, const dint_dict* fr
         !ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) || !value_stats_handles_ok(qi, filter, values))
         return DINT_ERR_ARG;
     percentile_call c(filter, values, per_million, n_percentiles, k, n_queries, value_counts, percentile_values, stats);
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    std::vector<uint64_t> freq_sums(n_queries, 0);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (and_queries_impl checks the offsets and the terms before anything is written or launched; its counts are the
-    // survivors of the rounds, and the select runs over exactly those slots)
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk,
-                                    nullptr, c.ranged(), c.filtered(), nullptr, nullptr, nullptr, nullptr, c.with_stats(), nullptr, &c.pa);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    const int st = ranked_restricted_call(true, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (matches) matches[q] = counts[q];
-        counts[q] = std::min<uint64_t>(counts[q], k);
-    }
     c.widen_counts(n_queries);
-    unpack_keys(keys, n_queries, k, counts, scores, docids);
+    restricted_outputs(keys, n_queries, k, h_matches, counts, matches, scores, docids);
     return DINT_OK;
 }

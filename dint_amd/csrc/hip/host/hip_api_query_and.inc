@@ -16,11 +16,9 @@ struct bool_steps {
 };
 
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
-                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split = true,
-                            const ranked_args* rk = nullptr, bool_steps* extra = nullptr, range_args* rg = nullptr,
-                            filter_args* fl = nullptr, facet_args* fa = nullptr, collapse_args* ca = nullptr,
-                            page_args* pg = nullptr, sort_args* sv = nullptr, value_stats_args* vs = nullptr,
-                            group_stats_args* gs = nullptr, percentile_args* pa = nullptr, group_limit_args* gl = nullptr);
+                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, const ranked_extras& x,
+                            bool may_split = true, const ranked_args* rk = nullptr, bool_steps* extra = nullptr, range_args* rg = nullptr,
+                            filter_args* fl = nullptr);
 
 // One AND call: what its stages share.
 struct and_call {
@@ -30,14 +28,7 @@ struct and_call {
     bool_steps* extra = nullptr;            // ranked_bool: excluded steps before the freqs pass, optional steps inside it
     range_args* rg = nullptr;               // a ranged call: candidates from the rarest list's blocks in range, the others killed
     filter_args* fl = nullptr;              // a filtered call: candidates from the rarest list's live blocks, the others killed
-    facet_args* fa = nullptr;               // a faceted call (ranked): the survivors' groups counted in front of the selection
-    collapse_args* ca = nullptr;            // a collapsed call (with fa): of every group only the best survivor is selected from
-    page_args* pg = nullptr;                // a paged call (ranked): only the survivors after every query's cursor are selected from
-    sort_args* sv = nullptr;                // a sorted call (ranked): the survivors are selected by a column's value, after every query's cursor
-    value_stats_args* vs = nullptr;         // a value-stats call (ranked): the survivors' values reduced in front of the selection
-    group_stats_args* gs = nullptr;         // a group-stats call (ranked): the survivors' values reduced per group in front of the selection
-    percentile_args* pa = nullptr;          // a percentile call (ranked): the survivors' values selected from in front of the selection
-    group_limit_args* gl = nullptr;         // a group-limited call (with fa, never with ca): of every group up to per_group survivors are selected from
+    ranked_extras x;                        // (ranked) what runs around the selection besides: the five steps of ranked_extras
     size_t n_queries = 0;
     uint64_t* counts = nullptr;
     hipStream_t s = nullptr;
@@ -153,7 +144,8 @@ static int and_mixed_split(const and_call& c, void* stream, bool* mixed) {
             sub_q.push_back(uint32_t(q));
         }
         std::vector<uint64_t> sub_counts(sub_q.size(), 0);
-        const int st = and_queries_impl(c.qi, nullptr, sub_terms.data(), sub_offs.data(), sub_q.size(), sub_counts.data(), nullptr, nullptr, stream, false);
+        const int st = and_queries_impl(c.qi, nullptr, sub_terms.data(), sub_offs.data(), sub_q.size(), sub_counts.data(), nullptr, nullptr, stream,
+                                        ranked_extras(), false);
         if (st != DINT_OK) return st;
         for (size_t k = 0; k != sub_q.size(); ++k) c.counts[sub_q[k]] = sub_counts[k];
     }
@@ -515,26 +507,9 @@ static int and_batch_rounds(and_call& c, bool searched0, unsigned long long* hos
 // as in the rounds above. The counts themselves travel to the host with the results.)
 // rk (ranked_and): a score per candidate slot, from 0.0f, summed by ranked_gather_kernel; then ranked_topk.
 // c.extra (ranked_bool): the optional terms' steps between the two; without it the launches are what they were.
-// c.fa (with rk): the facet rows cleared, then facet_count_kernel over the survivors in cand directly in front of
-// ranked_topk; the rows travel to the host with the sums.
-// c.ca (with c.fa): its workspaces cleared, collapse_best_kernel and collapse_keep_kernel behind facet_count_kernel — the
-// call is one pass, so every query's slots are complete — and collapse_hits_kernel behind ranked_topk.
-// c.pg (with rk): its keys sent and its counters cleared, then page_after_kernel directly in front of ranked_topk, behind the
-// collapse launches where there are any; the counters travel to the host with the sums.
-// c.sv (with rk): its keys and flags sent, its counters and hit scores cleared, value_after_kernel directly in front of
-// ranked_topk, which sorts its runs by the column's value, and sorted_hits_kernel behind it; the counters and the hit scores
-// travel to the host with the sums.
-// c.vs (with rk): its records and edges sent, its rows and hit values cleared, value_stats_kernel over the survivors directly
-// in front of ranked_topk and hit_values_kernel behind it; the records, the rows and the hit values travel to the host with
-// the sums.
-// c.gs (with rk): its records sent empty, group_stats_kernel over the survivors directly in front of ranked_topk; the records
-// travel to the host with the sums.
-// c.pa (with rk): its per_million sent and its states cleared, the four rounds of the select (percentile_launch) over the
-// survivors directly in front of ranked_topk — the call is one pass, so every query's slots are complete; the counts and the
-// values travel to the host with the sums.
-// c.gl (with c.fa, never with c.ca): its workspaces cleared, the rounds 0 .. per_group - 1 of group_limit_round_kernel and
-// group_limit_keep_kernel behind facet_count_kernel, in front of page_after_kernel where c.pg is given — the call is one pass,
-// so every query's slots are complete — and group_limit_hits_kernel behind ranked_topk. ----
+// c.x (with rk): its workspaces cleared behind the optional steps, its launches in front of ranked_topk and behind it, and
+// its results on their way back with the sums (ranked_extras: the steps and their order) — the call is one pass, so every
+// query's slots are complete. ----
 static int and_freqs_pass(and_call& c) {
     dint_query_index* qi = c.qi;
     const size_t n_queries = c.n_queries, n_terms = c.rounds + 1;
@@ -591,74 +566,14 @@ static int and_freqs_pass(and_call& c) {
         const int st = bool_should_pass(c);
         if (st != DINT_OK) return st;
     }
-    if (rk && c.fa) {
-        int st = facet_rows_clear(qi, c.fa, n_queries, c.s);
-        if (st == DINT_OK) st = facet_count_launch(qi, c.fa, c.n_pages, c.d_page_query, 0u, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
-    if (rk && c.fa && c.ca) {
-        int st = collapse_clear(qi, c.ca, c.fa, n_queries, c.s);
-        if (st == DINT_OK) st = collapse_launch(qi, c.ca, c.fa, c.n_pages, c.d_page_query, 0u, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
-    if (rk && c.fa && c.gl) {
-        int st = group_limit_clear(qi, c.gl, c.fa, n_queries, c.s);
-        if (st == DINT_OK) st = group_limit_launch(qi, c.gl, c.fa, c.n_pages, c.d_page_query, 0u, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
-    if (rk && c.pg) {
-        int st = page_begin_device(qi, c.pg, n_queries, c.s);
-        if (st == DINT_OK) st = page_after_launch(qi, c.pg, c.n_pages, c.d_page_query, 0u, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
-    if (rk && c.sv) {
-        int st = sort_begin_device(qi, c.sv, n_queries, c.s);
-        if (st == DINT_OK) st = value_after_launch(qi, c.sv, c.n_pages, c.d_page_query, 0u, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
-    if (rk && c.vs) {
-        int st = value_stats_clear(qi, c.vs, n_queries, c.s);
-        if (st == DINT_OK) st = value_stats_launch(qi, c.vs, c.n_pages, c.d_page_query, 0u, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
-    if (rk && c.gs) {
-        int st = group_stats_clear(qi, c.gs, n_queries, c.s);
-        if (st == DINT_OK) st = group_stats_launch(qi, c.gs, c.n_pages, c.d_page_query, 0u, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
-    if (rk && c.pa) {
-        int st = percentile_clear(qi, c.pa, n_queries, c.s);
-        if (st == DINT_OK) st = percentile_launch(qi, c.pa, c.n_pages, c.d_page_query, 0u, n_queries, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
     if (rk) {
-        const int st = ranked_topk(qi, *rk, c.page_query, n_queries, c.s, c.sv);
+        int st = c.x.clear(qi, n_queries, c.s);
+        if (st == DINT_OK) st = c.x.before_selection(qi, c.n_pages, c.d_page_query, 0u, n_queries, c.s);
+        if (st == DINT_OK) st = ranked_topk(qi, *rk, c.page_query, n_queries, c.s, c.x.sv);
+        if (st == DINT_OK) st = c.x.after_selection(qi, c.n_pages, c.d_page_query, 0u, n_queries, c.s);
+        if (st == DINT_OK) st = c.x.back(n_queries, c.s);
         if (st != DINT_OK) return c.failed(st);
     }
-    if (rk && c.vs) {
-        int st = hit_values_launch(qi, c.vs, n_queries, 0u, c.s);
-        if (st == DINT_OK) st = value_stats_back(c.vs, n_queries, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
-    if (rk && c.gs && group_stats_back(c.gs, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
-    if (rk && c.pa && percentile_back(c.pa, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
-    if (rk && c.sv) {
-        int st = sorted_hits_launch(qi, c.sv, c.n_pages, c.d_page_query, 0u, c.s);
-        if (st == DINT_OK) st = sort_back(c.sv, n_queries, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
-    if (rk && c.fa && c.ca) {
-        int st = collapse_hits_launch(qi, c.ca, c.fa, n_queries, 0u, c.s);
-        if (st == DINT_OK) st = collapse_back(c.ca, n_queries, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
-    if (rk && c.fa && c.gl) {
-        int st = group_limit_hits_launch(qi, c.gl, c.fa, n_queries, 0u, c.s);
-        if (st == DINT_OK) st = group_limit_back(c.gl, n_queries, c.s);
-        if (st != DINT_OK) return c.failed(st);
-    }
-    if (rk && c.fa && facet_rows_back(c.fa, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
-    if (rk && c.pg && page_back(c.pg, n_queries, c.s) != DINT_OK) return c.failed(DINT_ERR_HIP);
     c.h_sums.resize(n_queries);
     HIP_TRY(hipMemcpyAsync(c.h_sums.data(), qi->freq_sums.p, n_queries * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.s));
     c.h_freq_counts.resize(n_terms);
@@ -687,10 +602,8 @@ static int and_copy_back(and_call& c, uint64_t* freq_sums, uint64_t* freq_blocks
 // The call: the plan, then the one place that chooses the form — mixed split, workgroup-per-query batch, fused, round
 // tails or batch rounds — then, with a freqs dictionary, the freqs / ranked pass, and the copy back.
 static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
-                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, bool may_split,
-                            const ranked_args* rk, bool_steps* extra, range_args* rg, filter_args* fl, facet_args* fa,
-                            collapse_args* ca, page_args* pg, sort_args* sv, value_stats_args* vs, group_stats_args* gs,
-                            percentile_args* pa, group_limit_args* gl) {
+                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks, void* stream, const ranked_extras& x,
+                            bool may_split, const ranked_args* rk, bool_steps* extra, range_args* rg, filter_args* fl) {
     if (!qi || (n_queries && (!query_offsets || !counts))) return DINT_ERR_ARG;
     if (freq_blocks) *freq_blocks = 0;
     if (n_queries == 0) return DINT_OK;
@@ -702,14 +615,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     c.extra = extra;
     c.rg = rg;
     c.fl = fl;
-    c.fa = fa;
-    c.ca = ca;
-    c.pg = pg;
-    c.sv = sv;
-    c.vs = vs;
-    c.gs = gs;
-    c.pa = pa;
-    c.gl = gl;
+    c.x = x;
     c.n_queries = n_queries;
     c.counts = counts;
     c.s = static_cast<hipStream_t>(stream);
@@ -718,14 +624,7 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
     and_candidate_pages(c);
     if (rg) rg->blocks = c.n_pages;
     if (fl) fl->blocks = c.n_pages;
-    facet_rows_begin(fa, n_queries);
-    collapse_begin(ca, n_queries);
-    page_begin(pg, n_queries);
-    sort_begin(sv, n_queries);
-    value_stats_begin(vs, n_queries);
-    group_stats_begin(gs, n_queries);
-    percentile_begin(pa, n_queries);
-    group_limit_begin(gl, n_queries);
+    x.begin(n_queries);
     if (c.n_pages == 0) return DINT_OK;
     bool mixed = false;
     const int split = may_split ? and_mixed_split(c, stream, &mixed) : DINT_OK;
@@ -770,11 +669,11 @@ static int and_queries_impl(dint_query_index* qi, const dint_dict* freqs_dict, c
 
 int dint_and_queries(dint_query_index* qi, const uint32_t* terms, const uint64_t* query_offsets, size_t n_queries,
                      uint64_t* counts, void* stream) {
-    return and_queries_impl(qi, nullptr, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream);
+    return and_queries_impl(qi, nullptr, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, ranked_extras());
 }
 
 int dint_and_queries_freqs(dint_query_index* qi, const dint_dict* freqs_dict, const uint32_t* terms, const uint64_t* query_offsets,
                            size_t n_queries, uint64_t* counts, uint64_t* freq_sums, uint64_t* freq_blocks_decoded, void* stream) {
     if (!freqs_args_ok(qi, freqs_dict, freq_sums)) return DINT_ERR_ARG;
-    return and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums, freq_blocks_decoded, stream);
+    return and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums, freq_blocks_decoded, stream, ranked_extras());
 }

@@ -586,6 +586,91 @@ static int percentile_back(percentile_args* pa, size_t n_queries, hipStream_t s)
     return DINT_OK;
 }
 
+// What a ranked call threads through and_queries_impl / or_queries_impl besides its restriction: any of the *_args above, set
+// by name, null where the call has none (ca and gl come with fa, and never together). The five steps below are the only place
+// that lists them; a call runs them in this order, ranked_topk between the two in the middle. Every step returns the first
+// status that is not DINT_OK. AND is one pass over all the call's queries (id0 = 0, n_ids = n_queries); OR runs the two in
+// the middle per pass, over the pass's slots in cand and its n_ids whole queries from id0 on.
+struct ranked_extras {
+    facet_args* fa = nullptr;
+    collapse_args* ca = nullptr;
+    group_limit_args* gl = nullptr;
+    page_args* pg = nullptr;
+    sort_args* sv = nullptr;
+    value_stats_args* vs = nullptr;
+    group_stats_args* gs = nullptr;
+    percentile_args* pa = nullptr;
+
+    // a pass stages its page -> query table for the launches in front of the selection
+    bool wants_page_query() const { return fa || pg || sv || vs || gs || pa; }
+
+    // the call is planned and has refused nothing: the host outputs as a call without a match leaves them
+    void begin(size_t n_queries) const {
+        facet_rows_begin(fa, n_queries);
+        collapse_begin(ca, n_queries);
+        group_limit_begin(gl, n_queries);
+        page_begin(pg, n_queries);
+        sort_begin(sv, n_queries);
+        value_stats_begin(vs, n_queries);
+        group_stats_begin(gs, n_queries);
+        percentile_begin(pa, n_queries);
+    }
+    // under the index's lock, once per call, in front of its first launch: the device workspaces sized, sent and cleared
+    int clear(dint_query_index* qi, size_t n_queries, hipStream_t s) const {
+        int st = DINT_OK;
+        if (fa) st = facet_rows_clear(qi, fa, n_queries, s);
+        if (ca && st == DINT_OK) st = collapse_clear(qi, ca, fa, n_queries, s);
+        if (gl && st == DINT_OK) st = group_limit_clear(qi, gl, fa, n_queries, s);
+        if (pg && st == DINT_OK) st = page_begin_device(qi, pg, n_queries, s);
+        if (sv && st == DINT_OK) st = sort_begin_device(qi, sv, n_queries, s);
+        if (vs && st == DINT_OK) st = value_stats_clear(qi, vs, n_queries, s);
+        if (gs && st == DINT_OK) st = group_stats_clear(qi, gs, n_queries, s);
+        if (pa && st == DINT_OK) st = percentile_clear(qi, pa, n_queries, s);
+        return st;
+    }
+    // The launches in front of ranked_topk, over the n_pages pages of qi->cand; d_page_query[page] + id0: the page's query of
+    // the call. The one order:
+    //  - fa counts every match, so it precedes ca and gl;
+    //  - ca and gl precede pg, so the cursor applies to the kept documents;
+    //  - the readers (fa, vs, gs, pa) precede those that take slots out of cand (ca, gl, pg, sv), so statistics are over all
+    //    matches.
+    int before_selection(dint_query_index* qi, uint64_t n_pages, const uint32_t* d_page_query, uint32_t id0, size_t n_ids, hipStream_t s) const {
+        int st = DINT_OK;
+        if (fa) st = facet_count_launch(qi, fa, n_pages, d_page_query, id0, s);
+        if (vs && st == DINT_OK) st = value_stats_launch(qi, vs, n_pages, d_page_query, id0, s);
+        if (gs && st == DINT_OK) st = group_stats_launch(qi, gs, n_pages, d_page_query, id0, s);
+        if (pa && st == DINT_OK) st = percentile_launch(qi, pa, n_pages, d_page_query, id0, n_ids, s);
+        if (ca && st == DINT_OK) st = collapse_launch(qi, ca, fa, n_pages, d_page_query, id0, s);
+        if (gl && st == DINT_OK) st = group_limit_launch(qi, gl, fa, n_pages, d_page_query, id0, s);
+        if (pg && st == DINT_OK) st = page_after_launch(qi, pg, n_pages, d_page_query, id0, s);
+        if (sv && st == DINT_OK) st = value_after_launch(qi, sv, n_pages, d_page_query, id0, s);
+        return st;
+    }
+    // ... and behind it, over the keys it selected for the n_ids queries (qi->topk_out); no call has two of these
+    int after_selection(const dint_query_index* qi, uint64_t n_pages, const uint32_t* d_page_query, uint32_t id0, size_t n_ids,
+                        hipStream_t s) const {
+        int st = DINT_OK;
+        if (ca) st = collapse_hits_launch(qi, ca, fa, n_ids, id0, s);
+        if (gl && st == DINT_OK) st = group_limit_hits_launch(qi, gl, fa, n_ids, id0, s);
+        if (sv && st == DINT_OK) st = sorted_hits_launch(qi, sv, n_pages, d_page_query, id0, s);
+        if (vs && st == DINT_OK) st = hit_values_launch(qi, vs, n_ids, id0, s);
+        return st;
+    }
+    // the way back, on the stream, in front of the call's last wait
+    int back(size_t n_queries, hipStream_t s) const {
+        int st = DINT_OK;
+        if (fa) st = facet_rows_back(fa, n_queries, s);
+        if (ca && st == DINT_OK) st = collapse_back(ca, n_queries, s);
+        if (gl && st == DINT_OK) st = group_limit_back(gl, n_queries, s);
+        if (pg && st == DINT_OK) st = page_back(pg, n_queries, s);
+        if (sv && st == DINT_OK) st = sort_back(sv, n_queries, s);
+        if (vs && st == DINT_OK) st = value_stats_back(vs, n_queries, s);
+        if (gs && st == DINT_OK) st = group_stats_back(gs, n_queries, s);
+        if (pa && st == DINT_OK) st = percentile_back(pa, n_queries, s);
+        return st;
+    }
+};
+
 // the *_queries_freqs entries: a freqs dictionary of the index's device and kind, and somewhere for the sums
 static bool freqs_args_ok(const dint_query_index* qi, const dint_dict* freqs_dict, const uint64_t* freq_sums) {
     return freqs_dict && freq_sums && (!qi || (freqs_dict->device == qi->docs->device && freqs_dict->kind == qi->docs->kind));

@@ -178,8 +178,8 @@ int dint_ranked_bool_queries(dint_query_index* qi, const dint_dict* freqs_dict, 
     std::vector<uint64_t> freq_sums(n_queries, 0);
     const ranked_args rk = ranked_args_of(wd, k, keys.data());
     uint64_t must_claims = 0;
-    const int st = and_queries_impl(qi, freqs_dict, must_terms, must_offsets, n_queries, counts, freq_sums.data(), &must_claims, stream, false, &rk,
-                                    &x);
+    const int st = and_queries_impl(qi, freqs_dict, must_terms, must_offsets, n_queries, counts, freq_sums.data(), &must_claims, stream,
+                                    ranked_extras(), false, &rk, &x);
     if (st != DINT_OK) return st;
     if (blocks_decoded) {
         *blocks_decoded = must_claims;

@@ -40,7 +40,8 @@ int dint_ranked_or_bool_queries(dint_query_index* qi, const dint_dict* freqs_dic
 
     std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
     const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    const int st = or_queries_impl(qi, freqs_dict, should_terms, should_offsets, n_queries, counts, nullptr, nullptr, stream, &rk, &x);
+    const int st = or_queries_impl(qi, freqs_dict, should_terms, should_offsets, n_queries, counts, nullptr, nullptr, stream, ranked_extras(),
+                                   &rk, &x);
     if (st != DINT_OK) return st;
     if (blocks_decoded) {
         *blocks_decoded = x.eager_blocks;

@@ -62,7 +62,8 @@ static int maxscore_seeds(maxscore_pass_state& m) {
     std::vector<unsigned long long> seed_keys(m.nq * k, 0ull);
     ranked_args seed_rk = m.rk;
     seed_rk.keys = seed_keys.data();
-    const int st = or_run_pass(m.qi, m.freqs_dict, &seed_rk, seeds, /*min_stage*/ 0, /*no counters*/ nullptr, 0, /*ids*/ 0u, m.nq, m.s);
+    const int st = or_run_pass(m.qi, m.freqs_dict, &seed_rk, seeds, /*min_stage*/ 0, /*no counters*/ nullptr, 0, /*ids*/ 0u, m.nq, m.s,
+                               ranked_extras());
     if (st != DINT_OK) return st;
     HIP_TRY(hipStreamSynchronize(m.s));  // (the one wait for theta)
     for (size_t i = 0; i != m.nq; ++i) {

@@ -13,7 +13,7 @@ int dint_ranked_or_queries(dint_query_index* qi, const dint_dict* freqs_dict, co
     std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
     const ranked_args rk = ranked_args_of(wd, k, keys.data());
     // (or_queries_impl checks the offsets and the terms before anything is launched)
-    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk);
+    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, ranked_extras(), &rk);
     if (st != DINT_OK) return st;
     counts_from_keys(keys, n_queries, k, counts);
     unpack_keys(keys, n_queries, k, counts, scores, docids);

@@ -191,7 +191,8 @@ int dint_ranked_and_queries(dint_query_index* qi, const dint_dict* freqs_dict, c
     std::vector<uint64_t> freq_sums(n_queries, 0);
     const ranked_args rk = ranked_args_of(wd, k, keys.data());
     // (and_queries_impl checks the offsets and the terms before anything is launched)
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk);
+    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, ranked_extras(),
+                                    false, &rk);
     if (st != DINT_OK) return st;
     for (size_t q = 0; q != n_queries; ++q) counts[q] = std::min<uint64_t>(counts[q], k);
     unpack_keys(keys, n_queries, k, counts, scores, docids);

@@ -25,16 +25,12 @@ static bool value_stats_handles_ok(const dint_query_index* qi, const dint_doc_fi
 // What a value-stats entry threads through its call beside rk: the ranged call on null ranges or the filtered call, as
 // dint_ranked_or_filtered_queries chooses, and the column, the edges and the caller's outputs.
 struct value_stats_call {
-    std::vector<dint_doc_range> all;
-    range_args rg;
-    filter_args fl;
+    restriction r;
     value_stats_args vs;
+    ranked_extras x;
     value_stats_call(const dint_doc_filter* filter, const dint_doc_values* values, const uint32_t* edges, uint32_t n_edges, uint32_t k,
-                     size_t n_queries, dint_value_stats* stats, uint32_t* bucket_counts, uint32_t* hit_values) {
-        if (filter)
-            fl.filter = filter;
-        else
-            rg.ranges = ranges_or_all(nullptr, n_queries, all);
+                     size_t n_queries, dint_value_stats* stats, uint32_t* bucket_counts, uint32_t* hit_values)
+        : r(filter, nullptr, n_queries) {
         vs.values = values;
         vs.edges = edges;
         vs.n_edges = n_edges;
@@ -42,10 +38,8 @@ struct value_stats_call {
         vs.h_stats = stats;
         vs.h_rows = bucket_counts;
         vs.h_hit_values = hit_values;
+        x.vs = &vs;
     }
-    range_args* ranged() { return fl.filter ? nullptr : &rg; }
-    filter_args* filtered() { return fl.filter ? &fl : nullptr; }
-    uint64_t blocks() const { return fl.filter ? fl.blocks : rg.blocks; }
 };
 
 int dint_ranked_or_value_stats_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
@@ -57,19 +51,11 @@ int dint_ranked_or_value_stats_queries(dint_query_index* qi, const dint_dict* fr
         !ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) || !value_stats_handles_ok(qi, filter, values))
         return DINT_ERR_ARG;
     value_stats_call c(filter, values, edges, n_edges, k, n_queries, stats, bucket_counts, hit_values);
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (or_queries_impl checks the offsets and the terms before anything is written or launched)
-    const int st = or_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, nullptr, nullptr, stream, &rk, nullptr, c.ranged(),
-                                   c.filtered(), nullptr, nullptr, nullptr, nullptr, &c.vs);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    const int st = ranked_restricted_call(false, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    const std::vector<unsigned long long>& h_matches = filter ? c.fl.h_matches : c.rg.h_matches;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (matches) matches[q] = h_matches[q];
-        counts[q] = std::min<uint64_t>(h_matches[q], k);
-    }
-    unpack_keys(keys, n_queries, k, counts, scores, docids);
+    restricted_outputs(keys, n_queries, k, h_matches, counts, matches, scores, docids);
     return DINT_OK;
 }
 
@@ -82,19 +68,10 @@ int dint_ranked_and_value_stats_queries(dint_query_index* qi, const dint_dict* f
         !ranked_args_ok(qi, freqs_dict, wd, k, query_offsets, n_queries, counts, scores) || !value_stats_handles_ok(qi, filter, values))
         return DINT_ERR_ARG;
     value_stats_call c(filter, values, edges, n_edges, k, n_queries, stats, bucket_counts, hit_values);
-    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull);
-    std::vector<uint64_t> freq_sums(n_queries, 0);
-    const ranked_args rk = ranked_args_of(wd, k, keys.data());
-    // (and_queries_impl checks the offsets and the terms before anything is written or launched; its counts are the
-    // survivors of the rounds, and the values are reduced over exactly those slots)
-    const int st = and_queries_impl(qi, freqs_dict, terms, query_offsets, n_queries, counts, freq_sums.data(), nullptr, stream, false, &rk,
-                                    nullptr, c.ranged(), c.filtered(), nullptr, nullptr, nullptr, nullptr, &c.vs);
+    std::vector<unsigned long long> keys(uint64_t(n_queries) * k, 0ull), h_matches;
+    const int st = ranked_restricted_call(true, qi, freqs_dict, ranked_args_of(wd, k, keys.data()), terms, query_offsets, n_queries, counts, c.r,
+                                          c.x, blocks_decoded, h_matches, stream);
     if (st != DINT_OK) return st;
-    if (blocks_decoded) *blocks_decoded = c.blocks();
-    for (size_t q = 0; q != n_queries; ++q) {
-        if (matches) matches[q] = counts[q];
-        counts[q] = std::min<uint64_t>(counts[q], k);
-    }
-    unpack_keys(keys, n_queries, k, counts, scores, docids);
+    restricted_outputs(keys, n_queries, k, h_matches, counts, matches, scores, docids);
     return DINT_OK;
 }
