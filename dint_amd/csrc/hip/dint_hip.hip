@@ -3,7 +3,7 @@
 // host/ by subsystem and are included here in order — common helpers, handles and the query calls' staged layouts first,
 // then the extern "C" block (opened in host/hip_api_common.inc, closed at the end of this file): dictionary, vroom
 // decode, in-index decode, the query index and its page decodes, query planning, AND, OR, ranked AND, ranked OR and
-// pruned ranked OR queries, docID-range, document-filter, faceted, collapsed, paged, group-limited, sorted, value-stats, group-stats and percentile ranked queries, scores of given documents, maxima from the index, the index checked against its collection,
+// pruned ranked OR queries, docID-range, document-filter, faceted, collapsed, paged, group-limited, sorted, value-stats, group-stats, percentile and top-values ranked queries, scores of given documents, maxima from the index, the index checked against its collection,
 // statistics, host-pointer calls, list cache.
 #include "dint_hip.h"
 
@@ -45,6 +45,7 @@
 #include "dint_value_stats_kernels.hpp"
 #include "dint_group_stats_kernels.hpp"
 #include "dint_percentile_kernels.hpp"
+#include "dint_top_values_kernels.hpp"
 #include "dint_score_documents_kernels.hpp"
 #include "dint_wand_kernels.hpp"
 #include "dint_check_kernels.hpp"
@@ -78,6 +79,7 @@
 #include "host/hip_api_value_stats.inc"
 #include "host/hip_api_group_stats.inc"
 #include "host/hip_api_percentiles.inc"
+#include "host/hip_api_top_values.inc"
 #include "host/hip_api_score_documents.inc"
 #include "host/hip_api_wand.inc"
 #include "host/hip_api_check.inc"

@@ -17,7 +17,7 @@
 // under the call's filter, the term records still describe the whole lists, the scoring launch is
 // ranked_or_filtered_score_kernel, which finds a block's page through the filter's live rank and counts the matches into
 // the call's counters; those come back with the last pass. Without fl nothing is planned or launched differently.
-// x (the faceted, collapsed, paged, group-limited, sorted, value-stats, group-stats and percentile entries), with rk and with
+// x (the faceted, collapsed, paged, group-limited, sorted, value-stats, group-stats, percentile and top-values entries), with rk and with
 // rg or fl: its workspaces are cleared once per call, a pass stages its page -> query table besides and runs x's launches in
 // front of ranked_topk and behind it, over the pass's slots in cand at the pass's query offset — a pass holds whole queries,
 // so a query's slots are complete — and its results come back with the last pass (ranked_extras: the steps and their order).
@@ -216,7 +216,7 @@ static int or_run_pass(dint_query_index* qi, const dint_dict* freqs_dict, const 
                            d_counts + id0);
         if (hipGetLastError() != hipSuccess) return stream_failed(s, DINT_ERR_HIP);
     }
-    int rst = x.before_selection(qi, n_pages, qi->d(F.page_query), id0, n_ids, s);
+    int rst = x.before_selection(qi, n_pages, page_query, qi->d(F.page_query), id0, n_ids, s);
     if (rst == DINT_OK) rst = ranked_topk(qi, *rk, page_query, n_ids, s, x.sv);
     if (rst == DINT_OK) rst = x.after_selection(qi, n_pages, qi->d(F.page_query), id0, n_ids, s);
     return rst != DINT_OK ? stream_failed(s, rst) : DINT_OK;

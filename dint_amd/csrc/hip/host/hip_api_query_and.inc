@@ -568,7 +568,7 @@ static int and_freqs_pass(and_call& c) {
     }
     if (rk) {
         int st = c.x.clear(qi, n_queries, c.s);
-        if (st == DINT_OK) st = c.x.before_selection(qi, c.n_pages, c.d_page_query, 0u, n_queries, c.s);
+        if (st == DINT_OK) st = c.x.before_selection(qi, c.n_pages, c.page_query, c.d_page_query, 0u, n_queries, c.s);
         if (st == DINT_OK) st = ranked_topk(qi, *rk, c.page_query, n_queries, c.s, c.x.sv);
         if (st == DINT_OK) st = c.x.after_selection(qi, c.n_pages, c.d_page_query, 0u, n_queries, c.s);
         if (st == DINT_OK) st = c.x.back(n_queries, c.s);

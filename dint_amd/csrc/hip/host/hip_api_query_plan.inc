@@ -586,6 +586,140 @@ static int percentile_back(percentile_args* pa, size_t n_queries, hipStream_t s)
     return DINT_OK;
 }
 
+// The runs and tasks of a selection over the pages of a pass (ranked_topk over the candidate slots, top_values_launch over
+// the hash tables): query q's pages are the pages p with page_query[p] == q (consecutive), a page holds page_words keys, and
+// the query's keys are cut into runs of R. Pass 0 sorts every run; pass p >= 1 merges run a + 2^(p-1) into run a, a = 0, 2^p,
+// 2 * 2^p, ..., until run 0 of every query holds its best R. words(): the tables as the kernels read them (topk_layout).
+struct topk_runs {
+    std::vector<uint32_t> page_first, pages;
+    std::vector<unsigned long long> key_base;
+    std::vector<topk_task> tasks;
+    std::vector<size_t> pass_first;
+    uint64_t n_keys = 0;
+    topk_runs(const std::vector<uint32_t>& page_query, size_t n_queries, uint32_t page_words, uint32_t R, bool with_tasks = true)
+        : page_first(n_queries, 0), pages(n_queries, 0), key_base(n_queries, 0), pass_first(1, 0) {
+        for (size_t p = 0; p != page_query.size(); ++p) {
+            const uint32_t q = page_query[p];
+            if (pages[q] == 0) page_first[q] = uint32_t(p);
+            pages[q] += 1;
+        }
+        if (!with_tasks) return;
+        std::vector<uint32_t> runs(n_queries, 0);
+        uint32_t most_runs = 0;
+        for (size_t q = 0; q != n_queries; ++q) {
+            runs[q] = uint32_t((uint64_t(pages[q]) * page_words + R - 1) / R);
+            key_base[q] = n_keys;
+            n_keys += uint64_t(runs[q]) * R;
+            most_runs = std::max(most_runs, runs[q]);
+        }
+        for (size_t q = 0; q != n_queries; ++q)
+            for (uint32_t a = 0; a != runs[q]; ++a) tasks.push_back({uint32_t(q), a, 0u});
+        pass_first.push_back(tasks.size());
+        for (uint64_t half = 1; half < most_runs; half <<= 1) {
+            for (size_t q = 0; q != n_queries; ++q)
+                for (uint64_t a = 0; a + half < runs[q]; a += 2 * half) tasks.push_back({uint32_t(q), uint32_t(a), uint32_t(a + half)});
+            pass_first.push_back(tasks.size());
+        }
+    }
+    std::vector<uint32_t> words(const topk_layout& L) const {
+        std::vector<uint32_t> h(L.words, 0);
+        if (!tasks.empty()) std::memcpy(staged(h.data(), L.tasks), tasks.data(), tasks.size() * sizeof(topk_task));
+        if (!pages.empty()) {
+            std::memcpy(staged(h.data(), L.page_first), page_first.data(), pages.size() * 4);
+            std::memcpy(staged(h.data(), L.pages), pages.data(), pages.size() * 4);
+            std::memcpy(staged(h.data(), L.key_base), key_base.data(), pages.size() * 8);
+        }
+        return h;
+    }
+};
+
+// A top-values call (hip_api_top_values.inc): the column and how many of its values the caller takes per query, and where the
+// call's results live on the device — grow-only workspaces of the query index: per query of the call its valued matches and
+// its distinct values, a word each, and the call's overflow word behind them; per (query, i) the selected key; and, per pass,
+// the hash tables of the pass's queries (two 64-bit words per slot: a query of P pages owns the 512 P words from word 512 *
+// its first page on) and a selection's tasks and keys of their own — ranked_topk runs later on the same stream. The counters,
+// the overflow word and the keys are cleared once per call under the lock (top_values_clear); a pass clears its tables,
+// counts and selects (top_values_launch), and everything comes back once. Where a call takes a null one nothing is planned or
+// launched differently.
+struct top_values_args {
+    const dint_doc_values* values = nullptr;
+    uint32_t n_top = 0;
+    std::vector<uint32_t> h_words;            // out: per query the valued matches, per query the distinct values, the overflow word
+    std::vector<unsigned long long> h_keys;   // out: n_queries * n_top selected keys, count << 32 | ~value, 0 past a query's last
+    std::vector<std::vector<uint32_t>> sent;  // a pass's tables on their way up (pageable: kept until the call's last wait)
+    uint32_t *d_n = nullptr, *d_distinct = nullptr, *d_overflow = nullptr;  // (set by top_values_clear)
+    unsigned long long* d_out = nullptr;
+};
+// the call is planned and has refused nothing: no query has a valued match or a value until a pass says otherwise
+static void top_values_begin(top_values_args* tv, size_t n_queries) {
+    if (!tv) return;
+    tv->h_words.assign(2 * n_queries + 1, 0u);
+    tv->h_keys.assign(n_queries * tv->n_top, 0ull);
+}
+// under the index's lock, once per call, in front of its first launch: the counters, the overflow word and the keys clear
+static int top_values_clear(dint_query_index* qi, top_values_args* tv, size_t n_queries, hipStream_t s) {
+    const size_t n_out = n_queries * tv->n_top;
+    if (!qi->top_values_words.ensure(2 * n_queries + 1) || !qi->top_values_out.ensure(std::max<size_t>(1, n_out))) return DINT_ERR_HIP;
+    tv->d_n = qi->top_values_words.p;
+    tv->d_distinct = tv->d_n + n_queries;
+    tv->d_overflow = tv->d_distinct + n_queries;
+    tv->d_out = qi->top_values_out.p;
+    HIP_TRY(hipMemsetAsync(tv->d_n, 0, (2 * n_queries + 1) * 4, s));
+    if (n_out) HIP_TRY(hipMemsetAsync(tv->d_out, 0, n_out * sizeof(unsigned long long), s));
+    return DINT_OK;
+}
+// The count and the selection over the n_pages pages of qi->cand, in front of ranked_topk; page_query[page] (the host's copy
+// of d_page_query) + q0: the page's query of the call, and the pass holds the n_ids whole queries from q0 on. On the stream:
+// the pass's tables of runs go up, its hash tables clear, top_values_count_kernel fills them, and — n_top != 0 —
+// top_values_sort_runs_kernel, the passes of topk_merge_kernel and topk_out_kernel select every query's n_top best words into
+// the call's keys at the pass's offset. R = max(256, the power of two >= n_top) divides no table unevenly but for R = 1024 and
+// an odd number of pages: the words past the capacity count as empty.
+static int top_values_launch(dint_query_index* qi, top_values_args* tv, uint64_t n_pages, const std::vector<uint32_t>& page_query,
+                             const uint32_t* d_page_query, uint32_t q0, size_t n_ids, hipStream_t s) {
+    uint32_t R = kPageSlots;
+    while (R < tv->n_top) R <<= 1;
+    const topk_runs runs(page_query, n_ids, kTopValuesPageWords, R, tv->n_top != 0);
+    for (uint32_t pages : runs.pages)
+        if (uint64_t(pages) * kTopValuesPageWords > 0xFFFFFFFFull) return DINT_ERR_NOMEM;  // (a capacity is a word on the device)
+    const topk_layout L(runs.tasks.size(), n_ids);
+    const uint64_t n_words = n_pages * kTopValuesPageWords;
+    if (!qi->top_values_in.ensure(L.words) || !qi->top_values_table.ensure(n_words) ||
+        !qi->top_values_keys.ensure(std::max<uint64_t>(1, runs.n_keys)))
+        return DINT_ERR_HIP;
+    tv->sent.push_back(runs.words(L));
+    HIP_TRY(hipMemcpyAsync(qi->top_values_in.p, tv->sent.back().data(), L.words * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(qi->top_values_table.p, 0, n_words * sizeof(unsigned long long), s));
+    const topk_task* const d_tasks = staged<const topk_task>(qi->top_values_in.p, L.tasks);
+    const uint32_t* const d_page_first = staged(qi->top_values_in.p, L.page_first);
+    const uint32_t* const d_pages = staged(qi->top_values_in.p, L.pages);
+    const unsigned long long* const d_base = staged<const unsigned long long>(qi->top_values_in.p, L.key_base);
+    hipLaunchKernelGGL(top_values_count_kernel, dim3(uint32_t(n_pages)), dim3(kPageSlots), 0, s, qi->cand.p, n_pages * kPageSlots, d_page_query,
+                       q0, tv->values->view(), d_page_first, d_pages, qi->top_values_table.p, tv->d_n, tv->d_distinct, tv->d_overflow);
+    if (tv->n_top == 0) return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+    const uint32_t tb = 256;
+    for (size_t p = 0; p + 1 < runs.pass_first.size(); ++p) {
+        const size_t n_tasks = runs.pass_first[p + 1] - runs.pass_first[p];
+        if (n_tasks == 0) continue;
+        if (p == 0)
+            hipLaunchKernelGGL(top_values_sort_runs_kernel, dim3(uint32_t(n_tasks)), dim3(tb), R * sizeof(unsigned long long), s, d_tasks,
+                               d_page_first, d_pages, d_base, qi->top_values_table.p, R, qi->top_values_keys.p);
+        else
+            hipLaunchKernelGGL(topk_merge_kernel, dim3(uint32_t(n_tasks)), dim3(tb), R * sizeof(unsigned long long), s,
+                               d_tasks + runs.pass_first[p], d_base, R, qi->top_values_keys.p);
+    }
+    const uint64_t n_out = uint64_t(n_ids) * tv->n_top;
+    hipLaunchKernelGGL(topk_out_kernel, dim3(uint32_t((n_out + tb - 1) / tb)), dim3(tb), 0, s, d_base, d_pages, qi->top_values_keys.p,
+                       uint32_t(n_ids), tv->n_top, tv->d_out + uint64_t(q0) * tv->n_top);
+    return hipGetLastError() != hipSuccess ? DINT_ERR_HIP : DINT_OK;
+}
+// ... and the counters', the overflow word's and the keys' way back, on the stream, in front of the call's last wait
+static int top_values_back(top_values_args* tv, size_t n_queries, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(tv->h_words.data(), tv->d_n, (2 * n_queries + 1) * 4, hipMemcpyDeviceToHost, s));
+    if (tv->n_top)
+        HIP_TRY(hipMemcpyAsync(tv->h_keys.data(), tv->d_out, n_queries * tv->n_top * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    return DINT_OK;
+}
+
 // What a ranked call threads through and_queries_impl / or_queries_impl besides its restriction: any of the *_args above, set
 // by name, null where the call has none (ca and gl come with fa, and never together). The five steps below are the only place
 // that lists them; a call runs them in this order, ranked_topk between the two in the middle. Every step returns the first
@@ -600,9 +734,10 @@ struct ranked_extras {
     value_stats_args* vs = nullptr;
     group_stats_args* gs = nullptr;
     percentile_args* pa = nullptr;
+    top_values_args* tv = nullptr;
 
     // a pass stages its page -> query table for the launches in front of the selection
-    bool wants_page_query() const { return fa || pg || sv || vs || gs || pa; }
+    bool wants_page_query() const { return fa || pg || sv || vs || gs || pa || tv; }
 
     // the call is planned and has refused nothing: the host outputs as a call without a match leaves them
     void begin(size_t n_queries) const {
@@ -614,6 +749,7 @@ struct ranked_extras {
         value_stats_begin(vs, n_queries);
         group_stats_begin(gs, n_queries);
         percentile_begin(pa, n_queries);
+        top_values_begin(tv, n_queries);
     }
     // under the index's lock, once per call, in front of its first launch: the device workspaces sized, sent and cleared
     int clear(dint_query_index* qi, size_t n_queries, hipStream_t s) const {
@@ -626,20 +762,23 @@ struct ranked_extras {
         if (vs && st == DINT_OK) st = value_stats_clear(qi, vs, n_queries, s);
         if (gs && st == DINT_OK) st = group_stats_clear(qi, gs, n_queries, s);
         if (pa && st == DINT_OK) st = percentile_clear(qi, pa, n_queries, s);
+        if (tv && st == DINT_OK) st = top_values_clear(qi, tv, n_queries, s);
         return st;
     }
     // The launches in front of ranked_topk, over the n_pages pages of qi->cand; d_page_query[page] + id0: the page's query of
-    // the call. The one order:
+    // the call (page_query: the host's copy, the pass's queries from 0). The one order:
     //  - fa counts every match, so it precedes ca and gl;
     //  - ca and gl precede pg, so the cursor applies to the kept documents;
-    //  - the readers (fa, vs, gs, pa) precede those that take slots out of cand (ca, gl, pg, sv), so statistics are over all
+    //  - the readers (fa, vs, gs, pa, tv) precede those that take slots out of cand (ca, gl, pg, sv), so statistics are over all
     //    matches.
-    int before_selection(dint_query_index* qi, uint64_t n_pages, const uint32_t* d_page_query, uint32_t id0, size_t n_ids, hipStream_t s) const {
+    int before_selection(dint_query_index* qi, uint64_t n_pages, const std::vector<uint32_t>& page_query, const uint32_t* d_page_query,
+                         uint32_t id0, size_t n_ids, hipStream_t s) const {
         int st = DINT_OK;
         if (fa) st = facet_count_launch(qi, fa, n_pages, d_page_query, id0, s);
         if (vs && st == DINT_OK) st = value_stats_launch(qi, vs, n_pages, d_page_query, id0, s);
         if (gs && st == DINT_OK) st = group_stats_launch(qi, gs, n_pages, d_page_query, id0, s);
         if (pa && st == DINT_OK) st = percentile_launch(qi, pa, n_pages, d_page_query, id0, n_ids, s);
+        if (tv && st == DINT_OK) st = top_values_launch(qi, tv, n_pages, page_query, d_page_query, id0, n_ids, s);
         if (ca && st == DINT_OK) st = collapse_launch(qi, ca, fa, n_pages, d_page_query, id0, s);
         if (gl && st == DINT_OK) st = group_limit_launch(qi, gl, fa, n_pages, d_page_query, id0, s);
         if (pg && st == DINT_OK) st = page_after_launch(qi, pg, n_pages, d_page_query, id0, s);
@@ -667,6 +806,7 @@ struct ranked_extras {
         if (vs && st == DINT_OK) st = value_stats_back(vs, n_queries, s);
         if (gs && st == DINT_OK) st = group_stats_back(gs, n_queries, s);
         if (pa && st == DINT_OK) st = percentile_back(pa, n_queries, s);
+        if (tv && st == DINT_OK) st = top_values_back(tv, n_queries, s);
         return st;
     }
 };

@@ -79,40 +79,12 @@ static int ranked_topk(dint_query_index* qi, const ranked_args& rk, const std::v
                        hipStream_t s, const sort_args* sv) {
     uint32_t R = kPageSlots;
     while (R < rk.k) R <<= 1;
-    std::vector<uint32_t> q_page_first(n_queries, 0), q_pages(n_queries, 0);
-    for (size_t p = 0; p != page_query.size(); ++p) {
-        const uint32_t q = page_query[p];
-        if (q_pages[q] == 0) q_page_first[q] = uint32_t(p);
-        q_pages[q] += 1;
-    }
-    std::vector<unsigned long long> key_base(n_queries, 0);
-    std::vector<uint32_t> runs(n_queries, 0);
-    uint64_t n_keys = 0;
-    uint32_t most_runs = 0;
-    for (size_t q = 0; q != n_queries; ++q) {
-        runs[q] = uint32_t((uint64_t(q_pages[q]) * kPageSlots + R - 1) / R);
-        key_base[q] = n_keys;
-        n_keys += uint64_t(runs[q]) * R;
-        most_runs = std::max(most_runs, runs[q]);
-    }
-    // tasks: pass 0 sorts every run; pass p >= 1 merges run a + 2^(p-1) into run a, a = 0, 2^p, 2 * 2^p, ...
-    std::vector<topk_task> tasks;
-    std::vector<size_t> pass_first(1, 0);
-    for (size_t q = 0; q != n_queries; ++q)
-        for (uint32_t a = 0; a != runs[q]; ++a) tasks.push_back({uint32_t(q), a, 0u});
-    pass_first.push_back(tasks.size());
-    for (uint64_t half = 1; half < most_runs; half <<= 1) {
-        for (size_t q = 0; q != n_queries; ++q)
-            for (uint64_t a = 0; a + half < runs[q]; a += 2 * half) tasks.push_back({uint32_t(q), uint32_t(a), uint32_t(a + half)});
-        pass_first.push_back(tasks.size());
-    }
-    // (the inputs, topk_layout, in pageable memory of this frame: hence the wait)
-    const topk_layout L(tasks.size(), n_queries);
-    std::vector<uint32_t> h(L.words, 0);
-    std::memcpy(staged(h.data(), L.tasks), tasks.data(), tasks.size() * sizeof(topk_task));
-    std::memcpy(staged(h.data(), L.page_first), q_page_first.data(), n_queries * 4);
-    std::memcpy(staged(h.data(), L.pages), q_pages.data(), n_queries * 4);
-    std::memcpy(staged(h.data(), L.key_base), key_base.data(), n_queries * 8);
+    // (the runs, the tasks and their tables, topk_layout, in pageable memory of this frame: hence the wait)
+    const topk_runs runs(page_query, n_queries, kPageSlots, R);
+    const std::vector<size_t>& pass_first = runs.pass_first;
+    const uint64_t n_keys = runs.n_keys;
+    const topk_layout L(runs.tasks.size(), n_queries);
+    const std::vector<uint32_t> h = runs.words(L);
     if (!qi->topk_in.ensure(L.words) || !qi->topk_keys.ensure(std::max<uint64_t>(1, n_keys)) ||
         !qi->topk_out.ensure(uint64_t(n_queries) * rk.k))
         return DINT_ERR_HIP;

@@ -94,6 +94,12 @@ struct dint_query_index {
     // the percentile ranked calls (hip_api_percentiles.inc): per (query, percentile) of the call a row of 256 counters; the
     // call's per_million and behind them per (query, percentile) the select's state and the answer, then per query its count
     device_buffer<uint32_t> percentile_rows, percentile_words;
+    // the top-values ranked calls (hip_api_top_values.inc): per slot of a pass two words of its query's hash table; per query
+    // of the call its valued matches, then its distinct values, then the call's overflow word; a selection of their own over
+    // the tables — the tasks, the runs' keys and per (query, i) of the call the selected key (the ranked selection runs later
+    // on the same stream, in topk_in / topk_keys / topk_out)
+    device_buffer<unsigned long long> top_values_table, top_values_keys, top_values_out;
+    device_buffer<uint32_t> top_values_words, top_values_in;
     // dint_check_index (hip_api_check.inc): every block of a list but its last holds 256 postings (the in-index layout:
     // block j of a list is its positions [256 j, 256 j + n)); two pinned staging buffers of a pass's expected postings
     // and their device copies, alternating

@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     "dint_ranked_or_value_stats_queries", "dint_ranked_and_value_stats_queries",
     "dint_ranked_or_group_stats_queries", "dint_ranked_and_group_stats_queries",
     "dint_ranked_or_percentile_queries", "dint_ranked_and_percentile_queries",
+    "dint_ranked_or_top_values_queries", "dint_ranked_and_top_values_queries",
     "dint_wand_data_create_with_max_weights", "dint_ranked_or_maxscore_queries", "dint_score_documents",
     "dint_index_max_weights", "dint_wand_data_set_block_max_weights", "dint_check_index", "dint_count_ngrams", "dint_select_ngrams", "dint_last_kernel_clock_mhz",
 )
@@ -216,6 +217,10 @@ def _load():
     # value_counts, percentile_values, stats, blocks_decoded, stream)
     lib.dint_ranked_or_percentile_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_ranked_and_percentile_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    # (qi, freqs, wand, k, terms, offsets, filter, values, n_top, n_queries, counts, matches, scores, docids, value_counts,
+    # distinct_counts, top_n, top_values, top_counts, blocks_decoded, stream)
+    lib.dint_ranked_or_top_values_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.dint_ranked_and_top_values_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_wand_data_create_with_max_weights.argtypes = [C.c_int, vp, u64, vp, sz, C.POINTER(vp)]
     lib.dint_ranked_or_maxscore_queries.argtypes = [vp, vp, vp, u32, vp, vp, sz, vp, vp, vp, C.POINTER(u64), vp]
     lib.dint_score_documents.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.POINTER(u64), vp]
@@ -1181,6 +1186,44 @@ class QueryIndex:
         return self._ranked_percentiles("dint_ranked_and_percentile_queries", freqs_dict, wand, queries, values, percentiles, filter, k,
                                         with_stats)
 
+    def _ranked_top_values(self, fn: str, freqs_dict: "Dictionary", wand: "WandData", queries, values, n_top: int, doc_filter, k: int):
+        terms, offs = _pack_queries(queries)
+        n, n_top = len(queries), int(n_top)
+        counts = np.zeros(n, dtype=np.uint64)
+        matches = np.zeros(n, dtype=np.uint64)
+        scores = np.zeros((n, k), dtype=np.float32)
+        docids = np.zeros((n, k), dtype=np.uint32)
+        value_counts = np.zeros(n, dtype=np.uint64)
+        distinct_counts = np.zeros(n, dtype=np.uint64)
+        top_n = np.zeros(n, dtype=np.uint32)
+        top_values = np.zeros((n, max(n_top, 0)), dtype=np.uint32)
+        top_counts = np.zeros((n, max(n_top, 0)), dtype=np.uint32)
+        blocks = C.c_uint64()
+        _check(getattr(_lib, fn)(self._h, freqs_dict._h, wand._h, k, terms.ctypes.data, offs.ctypes.data,
+                                 doc_filter._h if doc_filter is not None else None, values._h, n_top, n, counts.ctypes.data,
+                                 matches.ctypes.data, scores.ctypes.data, docids.ctypes.data, value_counts.ctypes.data,
+                                 distinct_counts.ctypes.data, top_n.ctypes.data, top_values.ctypes.data if n_top else None,
+                                 top_counts.ctypes.data if n_top else None, C.byref(blocks), self._stream()), fn)
+        return counts, scores, docids, matches, blocks.value, value_counts, distinct_counts, top_n, top_values, top_counts
+
+    def ranked_or_top_values_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, values: "DocValues", n_top: int,
+                                     filter=None, k: int = 10):
+        """ranked_or_filtered_queries with the most frequent values of a column over every match and the number of different
+        ones (dint_ranked_or_top_values_queries): values is a DocValues on this index's device, n_top 0
+        to TOP_VALUES_MAX (0: the counts only; the library refuses more), filter a DocFilter of this index or None
+        (unrestricted) -> (counts, scores, docids, matches, blocks_decoded) as ranked_or_filtered_queries returns them with
+        with_stats for (queries, filter, k), bit for bit, and behind them value_counts u64[n]: the matches d < values.num_docs of
+        every query, distinct_counts u64[n]: the different values among them, top_n u32[n] = min(n_top, distinct), and
+        top_values, top_counts u32[n, n_top]: [q, i], i < top_n[q], the values by count descending, then value ascending, and
+        their counts; 0 past top_n[q]."""
+        return self._ranked_top_values("dint_ranked_or_top_values_queries", freqs_dict, wand, queries, values, n_top, filter, k)
+
+    def ranked_and_top_values_queries(self, freqs_dict: "Dictionary", wand: "WandData", queries, values: "DocValues", n_top: int,
+                                      filter=None, k: int = 10):
+        """ranked_and_filtered_queries with the most frequent values of a column over every match and the number of different
+        ones (dint_ranked_and_top_values_queries): arguments and outputs as ranked_or_top_values_queries, over the intersection."""
+        return self._ranked_top_values("dint_ranked_and_top_values_queries", freqs_dict, wand, queries, values, n_top, filter, k)
+
     def ranked_pages(self, entry: str, freqs_dict: "Dictionary", wand: "WandData", queries, k: int = 10, filter=None, facets=None,
                      after=None, max_pages=None, values=None, descending: bool = True, per_group=None):
         """Walks a batch page by page: entry is "or", "and", "or_collapsed" or "and_collapsed" (the
@@ -1603,6 +1646,7 @@ def _pack_value_edges(edges):
 
 
 PERCENTILES_MAX = 16  # DINT_PERCENTILES_MAX (include/dint_hip.h)
+TOP_VALUES_MAX = 1024  # DINT_TOP_VALUES_MAX
 
 
 def _pack_percentiles(percentiles):

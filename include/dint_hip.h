@@ -1087,6 +1087,52 @@ int dint_ranked_and_percentile_queries(dint_query_index* qi, const dint_dict* fr
                                        uint64_t* counts, uint64_t* matches, float* scores, uint32_t* docids, uint64_t* value_counts,
                                        uint32_t* percentile_values, dint_value_stats* stats, uint64_t* blocks_decoded, void* stream);
 
+/* ---- the most frequent values of a column over the matches of the ranked queries, and how many different ones there are ----
+ * Adds: what a cursor engine computes with a terms collector and a cardinality collector beside its top-k collector — the top
+ * 10 authors, hosts or prices of the results, the number of distinct sellers — for a batch of queries, in the call that ranks
+ * them, EXACTLY. Facet counts need the column mapped to at most DINT_FACETS_MAX_GROUPS dense group ids in advance and return a
+ * row of n_groups counters per query; a column is an arbitrary u32 per document and may have as many values as documents.
+ * dint_ranked_or_top_values_queries / dint_ranked_and_top_values_queries take the arguments of the filtered calls (filter
+ * nullable: unrestricted), the column (a dint_doc_values), n_top (0 .. DINT_TOP_VALUES_MAX) and the outputs (HOST):
+ *   counts, matches, scores, docids, *blocks_decoded   bit for bit what dint_ranked_or_filtered_queries /
+ *                    dint_ranked_and_filtered_queries return for the same arguments (filter null: the unfiltered answer with
+ *                    the matches counted); the plan depends neither on the column nor on n_top; matches, docids and
+ *                    blocks_decoded are nullable
+ *   value_counts[q]  the matches of query q that have a value, over EVERY match, not over the top k: the number the
+ *                    percentile and value-stats calls report. A match d HAS A VALUE iff d < the column's num_docs
+ *   distinct_counts[q]  the number of different values among them
+ *   top_n[q]         min(n_top, distinct_counts[q])
+ *   top_values[q * n_top + i], top_counts[q * n_top + i], i < top_n[q]: the values in the order COUNT DESCENDING, THEN VALUE
+ *                    ASCENDING, and how many valued matches have each; 0 past top_n[q]. n_top == 0 asks for the counts only:
+ *                    top_values and top_counts may then be null, and no selection is launched
+ * Every quantity is an integer count: exact, order-independent, the same from run to run and equal to a sort-and-count on the
+ * host.
+ * DINT_ERR_ARG, before anything is written or launched: whatever the filtered calls refuse; a null values or one on another
+ * device than the index; a filter of another index; n_top > DINT_TOP_VALUES_MAX; a null value_counts, distinct_counts or top_n;
+ * a null top_values or top_counts with n_top > 0. Terms, query_offsets, the handle's lock and the stream are as for the
+ * filtered calls. Besides the filtered call's launches a call runs, per OR pass / per AND call and in front of the selection:
+ * a clear of the pass's hash tables — per query 16 bytes per candidate slot, 64-bit words `value << 32 | count` at a load of
+ * at most 1/2 —, one launch that gathers one word of the column per live slot, merges equal values in a page-local LDS table
+ * and inserts each of the page's distinct values into its query's table once, and — n_top > 0 — a selection over the tables
+ * in the ranked selection's manner (runs sorted, merged pairwise) with workspaces of its own. The tables, the selection's
+ * tasks and keys, the counters (8 bytes a query) and the selected keys (8 bytes * n_queries * n_top) are grow-only workspaces of
+ * the query index; everything returns once, in front of the call's last wait. Every probe sequence
+ * on the device is bounded by its table's capacity; a table that ran full all the same — a mistake of the library's, never of
+ * the caller's — ends the call with DINT_ERR_NOMEM behind its last wait.
+ * Approximate sketches, top values per facet group, strings (the caller maps them to u32, as for every column), merging top
+ * lists across shards and the boolean, pruned, collapsed and paged forms are out of scope. */
+#define DINT_TOP_VALUES_MAX 1024u /* = DINT_RANKED_MAX_K */
+int dint_ranked_or_top_values_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                      const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                      const dint_doc_values* values, uint32_t n_top, size_t n_queries, uint64_t* counts, uint64_t* matches,
+                                      float* scores, uint32_t* docids, uint64_t* value_counts, uint64_t* distinct_counts, uint32_t* top_n,
+                                      uint32_t* top_values, uint32_t* top_counts, uint64_t* blocks_decoded, void* stream);
+int dint_ranked_and_top_values_queries(dint_query_index* qi, const dint_dict* freqs_dict, const dint_wand_data* wd, uint32_t k,
+                                       const uint32_t* terms, const uint64_t* query_offsets, const dint_doc_filter* filter,
+                                       const dint_doc_values* values, uint32_t n_top, size_t n_queries, uint64_t* counts, uint64_t* matches,
+                                       float* scores, uint32_t* docids, uint64_t* value_counts, uint64_t* distinct_counts, uint32_t* top_n,
+                                       uint32_t* top_values, uint32_t* top_counts, uint64_t* blocks_decoded, void* stream);
+
 /* ---- the wand data's BM25 maxima from the index, on the device; block maxima for the pruned call --------------
  * Replaces: the max_term_weight half of wand_data's constructor (include/ds2i/wand_data.hpp:18-57, src/create_wand_data.cpp),
  * which walks the uncompressed collection posting by posting, by one decode of the INDEX: a caller that has only what this

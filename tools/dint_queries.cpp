@@ -1,13 +1,14 @@
 // dint_queries — the reference's `queries` tool (src/queries.cpp:15-153) for the DINT index types, on the device path.
 //
 //   dint_queries <index_type> <query_type> <index_filename> [<wand_filename>] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N]
-//                [--per-group N] [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] [--percentiles p1,p2,...] < query_log
+//                [--per-group N] [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] [--percentiles p1,p2,...] [--top-values N] < query_log
 //   index_type: single_rect_dint | single_packed_dint | multi_packed_dint        (include/index_types.hpp:73-79)
 //   query_type: and | and_freq | or | or_freq | ranked_and | ranked_or | ranked_or_maxscore | ranked_or_blockmax | ranked_bool |
 //               ranked_or_bool | ranked_or_range | ranked_and_range | ranked_or_filtered | ranked_and_filtered |
 //               ranked_or_faceted | ranked_and_faceted | ranked_or_collapsed | ranked_and_collapsed | ranked_or_paged |
 //               ranked_and_paged | ranked_or_sorted | ranked_and_sorted | ranked_or_value_stats | ranked_and_value_stats |
 //               ranked_or_group_stats | ranked_and_group_stats | ranked_or_percentiles | ranked_and_percentiles |
+//               ranked_or_top_values | ranked_and_top_values |
 //               ranked_or_group_limit | ranked_and_group_limit, several
 //               separated by ':'
 //               (src/queries.cpp:93-111);
@@ -93,6 +94,14 @@
 //               and keys are ranked_or's, and the JSON line carries besides "matches", "value_n" (the matches that have a
 //               value, over the log), "per_million" (the ranks as parsed) and "percentile_sum" (per requested percentile the
 //               sum of its values over the log's queries);
+//               ranked_or_top_values / ranked_and_top_values (dint_ranked_or_top_values_queries,
+//               dint_ranked_and_top_values_queries: ranked_or / ranked_and with the most frequent values of a column over every
+//               match and the number of different ones) need --values FILE as the sorted types do and
+//               --top-values N — 0 to 1024 values per query, 0: the counts only — and take either --filter FILE or
+//               --value-range lo:hi; each must be the only type of its run; the query lines, output and keys are ranked_or's, and
+//               the JSON line carries besides "matches", "value_n" (the matches that have a value), "distinct" (the different
+//               values, query by query) and "top_count_sum" (the counts of the listed values), each summed over the log, and
+//               "n_top";
 //               wand and maxscore are out of scope and always print it
 //   index_filename: what dint_create_freq_index wrote (dint/index_file.hpp)
 //   wand_filename: what dint_create_wand_data wrote (include/dint_host.h), a positional argument as in src/queries.cpp:133-137
@@ -133,7 +142,7 @@ static double now_us() {
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N] [--per-group N] [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] [--percentiles p1,p2,...] < query_log"
+        std::cerr << argv[0] << " <index_type> <query_type> <index_filename> [wand_filename] [--batch] [--runs R] [--filter FILE] [--facets FILE] [--pages N] [--per-group N] [--values FILE] [--order asc|desc] [--value-range lo:hi] [--edges e1,e2,...] [--percentiles p1,p2,...] [--top-values N] < query_log"
                   << std::endl;
         return 1;
     }
@@ -148,6 +157,7 @@ int main(int argc, char** argv) {
         std::string order_name;             // ranked_*_sorted: asc | desc ("": not given)
         const char* edges_text = nullptr;   // ranked_*_value_stats: the bucket boundaries
         const char* percentiles_text = nullptr;  // ranked_*_percentiles: the ranks, in percent
+        const char* top_values_text = nullptr;   // ranked_*_top_values: the values listed per query
         bool batch = false;
         size_t runs = 10 + 1;  // src/queries.cpp:13
         size_t pages = 0;      // ranked_*_paged: the pages walked per query (0: not given)
@@ -163,6 +173,7 @@ int main(int argc, char** argv) {
             else if (a == "--value-range" && i + 1 < argc) value_range = argv[++i];
             else if (a == "--edges" && i + 1 < argc) edges_text = argv[++i];
             else if (a == "--percentiles" && i + 1 < argc) percentiles_text = argv[++i];
+            else if (a == "--top-values" && i + 1 < argc) top_values_text = argv[++i];
             else if (a == "--pages" && i + 1 < argc) pages = size_t(std::max(1, std::atoi(argv[++i])));
             else if (a == "--per-group" && i + 1 < argc) per_group = std::max(0, std::atoi(argv[++i]));
             else if (!wand_filename && a.rfind("--", 0) != 0) wand_filename = argv[i];
@@ -238,6 +249,10 @@ int main(int argc, char** argv) {
         for (const char* pct : {"ranked_or_percentiles", "ranked_and_percentiles"})
             if (!is_pct && (":" + query_type + ":").find(std::string(":") + pct + ":") != std::string::npos)
                 throw std::runtime_error(std::string(pct) + " answers its whole log under --values: it must be the only query type of a run");
+        const bool is_topv = query_type == "ranked_or_top_values" || query_type == "ranked_and_top_values";
+        for (const char* topv : {"ranked_or_top_values", "ranked_and_top_values"})
+            if (!is_topv && (":" + query_type + ":").find(std::string(":") + topv + ":") != std::string::npos)
+                throw std::runtime_error(std::string(topv) + " answers its whole log under --values: it must be the only query type of a run");
         if (is_gstats && !facets_filename) {
             std::cerr << query_type << " needs --facets FILE (every line `d g` or `lo:hi g`: document d, or every document of [lo, hi), is in group g)"
                       << std::endl;
@@ -246,12 +261,13 @@ int main(int argc, char** argv) {
         if (!is_paged && !is_sorted && !is_glimit && pages) throw std::runtime_error("--pages goes with ranked_or_paged, ranked_and_paged, ranked_or_sorted and ranked_and_sorted only");
         if (is_paged && !pages) pages = 2;
         if ((is_sorted || is_glimit) && !pages) pages = 1;
-        if (!is_sorted && !is_vstats && !is_gstats && !is_pct && (values_filename || value_range || !order_name.empty()))
+        if (!is_sorted && !is_vstats && !is_gstats && !is_pct && !is_topv && (values_filename || value_range || !order_name.empty()))
             throw std::runtime_error("--values, --order and --value-range go with ranked_or_sorted and ranked_and_sorted only");
-        if ((is_vstats || is_gstats || is_pct) && !order_name.empty()) throw std::runtime_error("--order goes with ranked_or_sorted and ranked_and_sorted only");
+        if ((is_vstats || is_gstats || is_pct || is_topv) && !order_name.empty()) throw std::runtime_error("--order goes with ranked_or_sorted and ranked_and_sorted only");
         if (!is_vstats && edges_text) throw std::runtime_error("--edges goes with ranked_or_value_stats and ranked_and_value_stats only");
         if (!is_pct && percentiles_text) throw std::runtime_error("--percentiles goes with ranked_or_percentiles and ranked_and_percentiles only");
-        if ((is_sorted || is_vstats || is_gstats || is_pct) && !values_filename) {
+        if (!is_topv && top_values_text) throw std::runtime_error("--top-values goes with ranked_or_top_values and ranked_and_top_values only");
+        if ((is_sorted || is_vstats || is_gstats || is_pct || is_topv) && !values_filename) {
             std::cerr << query_type << " needs --values FILE (every line `d v` or `lo:hi v`: document d, or every document of [lo, hi), has value v)"
                       << std::endl;
             return 1;
@@ -261,12 +277,24 @@ int main(int argc, char** argv) {
                       << std::endl;
             return 1;
         }
+        uint32_t n_top = 0;
+        if (is_topv) {
+            const std::string digits = top_values_text ? top_values_text : "";
+            if (digits.empty() || digits.size() > 4 || digits.find_first_not_of("0123456789") != std::string::npos ||
+                std::stoul(digits) > DINT_TOP_VALUES_MAX) {
+                std::cerr << query_type << " needs --top-values N (0 to " << DINT_TOP_VALUES_MAX << ": the values listed per query, 0: the counts only)"
+                          << std::endl;
+                return 1;
+            }
+            n_top = uint32_t(std::stoul(digits));
+        }
         if (!order_name.empty() && order_name != "asc" && order_name != "desc") throw std::runtime_error("--order is asc or desc");
         const uint32_t sort_order = order_name == "asc" ? DINT_SORT_ASC : DINT_SORT_DESC;
         if (value_range && filter_filename) throw std::runtime_error("--value-range and --filter exclude each other: a run has one filter");
         if (is_sorted && facets_filename) throw std::runtime_error("--facets does not go with the ranked_*_sorted types");
         if (is_vstats && facets_filename) throw std::runtime_error("--facets does not go with the ranked_*_value_stats types");
         if (is_pct && facets_filename) throw std::runtime_error("--facets does not go with the ranked_*_percentiles types");
+        if (is_topv && facets_filename) throw std::runtime_error("--facets does not go with the ranked_*_top_values types");
         std::vector<uint32_t> per_million;
         if (percentiles_text) per_million = tool::parse_percentiles(percentiles_text);
         std::vector<uint32_t> value_edges;
@@ -274,14 +302,14 @@ int main(int argc, char** argv) {
         uint32_t range_lo = 0, range_hi = 0;
         if (value_range) tool::parse_value_range(value_range, range_lo, range_hi);
         tool::doc_values_column values_column;
-        if (is_sorted || is_vstats || is_gstats || is_pct) {
+        if (is_sorted || is_vstats || is_gstats || is_pct || is_topv) {
             std::ifstream vf(values_filename);
             if (!vf) throw std::runtime_error(std::string("could not open the values file ") + values_filename);
             values_column = tool::parse_doc_values(vf);
         }
         if (!needs_facets && !is_paged && !is_gstats && !is_glimit && facets_filename)
             throw std::runtime_error("--facets goes with the ranked_*_faceted, ranked_*_collapsed and ranked_*_paged types only");
-        if (!is_filtered && !needs_facets && !is_paged && !is_sorted && !is_vstats && !is_gstats && !is_pct && !is_glimit && filter_filename)
+        if (!is_filtered && !needs_facets && !is_paged && !is_sorted && !is_vstats && !is_gstats && !is_pct && !is_topv && !is_glimit && filter_filename)
             throw std::runtime_error("--filter goes with the ranked_*_filtered, ranked_*_faceted, ranked_*_collapsed, ranked_*_paged and ranked_*_sorted types only");
         const bool uses_facets = needs_facets || is_gstats || is_glimit || (is_paged && facets_filename);  // (a paged type: the collapsed paged entry)
         tool::doc_facets_map facets_map;
@@ -412,7 +440,7 @@ int main(int argc, char** argv) {
         dint_doc_filter* doc_filter = nullptr;  // ranked_*_filtered: the run's filter
         if (filter_filename) dint_ok(dint_doc_filter_create(qi, filter_bits.words.data(), filter_bits.num_docs, &doc_filter), "dint_doc_filter_create");
         dint_doc_values* doc_values = nullptr;  // ranked_*_sorted, ranked_*_value_stats, ranked_*_group_stats: the run's column, and with --value-range the filter from it
-        if (is_sorted || is_vstats || is_gstats || is_pct) {
+        if (is_sorted || is_vstats || is_gstats || is_pct || is_topv) {
             dint_ok(dint_doc_values_create(0, values_column.values.data(), values_column.num_docs, &doc_values), "dint_doc_values_create");
             if (value_range) dint_ok(dint_doc_filter_create_from_values(qi, doc_values, range_lo, range_hi, &doc_filter), "dint_doc_filter_create_from_values");
         }
@@ -447,6 +475,10 @@ int main(int argc, char** argv) {
         std::vector<uint64_t> value_counts;
         std::vector<uint32_t> percentile_values;
         const size_t n_pct = per_million.size();
+        // ranked_*_top_values: a call's distinct values and listed values per query (the valued matches go to value_counts), and
+        // the lists themselves, n_top per query
+        std::vector<uint64_t> distinct_counts;
+        std::vector<uint32_t> top_ns, top_list_values, top_list_counts;
 
         std::vector<std::string> types;
         for (size_t a = 0; a <= query_type.size();) {
@@ -471,7 +503,8 @@ int main(int argc, char** argv) {
             const bool is_or_vstats = t == "ranked_or_value_stats" && wand, is_and_vstats = t == "ranked_and_value_stats" && wand;
             const bool is_or_gstats = t == "ranked_or_group_stats" && wand, is_and_gstats = t == "ranked_and_group_stats" && wand;
             const bool is_or_pct = t == "ranked_or_percentiles" && wand, is_and_pct = t == "ranked_and_percentiles" && wand;
-            const bool is_ranked = (t == "ranked_and" && wand) || is_or_pct || is_and_pct || is_or_gstats || is_and_gstats || is_or_vstats || is_and_vstats || is_or_sorted || is_and_sorted || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
+            const bool is_or_topv = t == "ranked_or_top_values" && wand, is_and_topv = t == "ranked_and_top_values" && wand;
+            const bool is_ranked = (t == "ranked_and" && wand) || is_or_topv || is_and_topv || is_or_pct || is_and_pct || is_or_gstats || is_and_gstats || is_or_vstats || is_and_vstats || is_or_sorted || is_and_sorted || is_or_paged || is_and_paged || is_ranked_or || is_maxscore || is_ranked_bool || is_ranked_or_bool ||
                                    is_or_range || is_and_range || is_or_filtered || is_and_filtered || is_or_faceted || is_and_faceted ||
                                    is_or_collapsed || is_and_collapsed || is_or_glimit || is_and_glimit;
             if (t != "and" && t != "and_freq" && t != "or" && t != "or_freq" && !is_ranked) {
@@ -648,6 +681,19 @@ int main(int argc, char** argv) {
                                     percentile_values.data() + at * n_pct, nullptr, nullptr, nullptr),
                                 "dint_ranked_*_percentile_queries");
                     }
+                } else if (is_or_topv || is_and_topv) {
+                    if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
+                    facet_matches.resize(n);
+                    value_counts.resize(n);
+                    distinct_counts.resize(n);
+                    top_ns.resize(n);
+                    top_list_values.resize(n * n_top);
+                    top_list_counts.resize(n * n_top);
+                    dint_ok((is_or_topv ? dint_ranked_or_top_values_queries : dint_ranked_and_top_values_queries)(
+                                qi, freqs_dict, wand, kTopK, q_terms, q_offs, doc_filter, doc_values, n_top, n, q_counts, facet_matches.data(),
+                                top_scores.data(), nullptr, value_counts.data(), distinct_counts.data(), top_ns.data(),
+                                n_top ? top_list_values.data() : nullptr, n_top ? top_list_counts.data() : nullptr, nullptr, nullptr),
+                            "dint_ranked_*_top_values_queries");
                 } else if (is_maxscore) {
                     if (top_scores.size() < n * kTopK) top_scores.resize(n * kTopK);
                     dint_ok(dint_ranked_or_maxscore_queries(qi, freqs_dict, is_blockmax ? wand_blockmax : wand, kTopK, q_terms, q_offs, n, q_counts, top_scores.data(), nullptr,
@@ -708,6 +754,15 @@ int main(int argc, char** argv) {
                     for (size_t j = 0; j != n_pct; ++j) sums[j] += percentile_values[q * n_pct + j];
                 }
             };
+            // a top-values type: the log's valued matches, distinct values (query by query) and listed counts (the first run's)
+            uint64_t log_distinct = 0, log_top_counts = 0;
+            auto merge_top_values = [&](uint64_t& into_n, uint64_t& into_distinct, uint64_t& into_counts, size_t n) {
+                for (size_t q = 0; q != n; ++q) {
+                    into_n += value_counts[q];
+                    into_distinct += distinct_counts[q];
+                    for (size_t i = 0; i != top_ns[q]; ++i) into_counts += top_list_counts[q * n_top + i];
+                }
+            };
             for (size_t run = 0; run != runs; ++run) {  // op_perftest
                 for (size_t i = 0; i != queries.size(); ++i) {
                     auto const& q = queries[i];
@@ -720,7 +775,8 @@ int main(int argc, char** argv) {
                     if (run == 0 && is_vstats && is_ranked) merge_stats(log_stats, bucket_totals, 1);
                     if (run == 0 && is_gstats && is_ranked) merge_groups(group_totals, 1);
                     if (run == 0 && is_pct && is_ranked) merge_percentiles(log_value_n, percentile_sums, 1);
-                    if (run == 0 && (needs_facets || is_paged || is_glimit || is_sorted || is_vstats || is_gstats || is_pct)) {
+                    if (run == 0 && is_topv && is_ranked) merge_top_values(log_value_n, log_distinct, log_top_counts, 1);
+                    if (run == 0 && (needs_facets || is_paged || is_glimit || is_sorted || is_vstats || is_gstats || is_pct || is_topv)) {
                         all_matches += facet_matches[0];
                         if (is_collapsed || is_glimit || (is_paged && doc_facets)) all_collapsed += collapsed_counts[0];
                         for (size_t g = 0; g != facet_totals.size(); ++g) facet_totals[g] += facet_rows[g];
@@ -772,6 +828,13 @@ int main(int argc, char** argv) {
                     for (size_t q = 0; q != queries.size(); ++q) batch_matches += facet_matches[q];
                     if (batch_matches != all_matches || batch_value_n != log_value_n || batch_sums != percentile_sums)
                         throw std::runtime_error("the batch call and the one-query calls selected other percentiles");
+                } else if (is_topv) {  // ... and count the same values
+                    uint64_t batch_value_n = 0, batch_distinct = 0, batch_top_counts = 0, batch_matches = 0;
+                    merge_top_values(batch_value_n, batch_distinct, batch_top_counts, queries.size());
+                    for (size_t q = 0; q != queries.size(); ++q) batch_matches += facet_matches[q];
+                    if (batch_matches != all_matches || batch_value_n != log_value_n || batch_distinct != log_distinct ||
+                        batch_top_counts != log_top_counts)
+                        throw std::runtime_error("the batch call and the one-query calls counted other values");
                 } else if (is_gstats) {  // ... and reduce the same values per group
                     std::vector<dint_value_stats> batch_groups(n_groups, dint_value_stats{0, 0, 0xFFFFFFFFu, 0});
                     merge_groups(batch_groups, queries.size());
@@ -814,6 +877,9 @@ int main(int argc, char** argv) {
                 std::cout << "], \"percentile_sum\": [";
                 for (size_t j = 0; j != n_pct; ++j) std::cout << (j ? ", " : "") << percentile_sums[j];
                 std::cout << "]";
+            } else if (is_topv) {
+                std::cout << ", \"matches\": " << all_matches << ", \"value_n\": " << log_value_n << ", \"distinct\": " << log_distinct
+                          << ", \"top_count_sum\": " << log_top_counts << ", \"n_top\": " << n_top;
             } else if (is_vstats) {
                 std::cout << ", \"matches\": " << all_matches << ", \"value_n\": " << log_stats.n << ", \"value_sum\": " << log_stats.sum
                           << ", \"value_min\": " << log_stats.min << ", \"value_max\": " << log_stats.max << ", \"buckets\": [";
